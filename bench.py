@@ -13,7 +13,9 @@ takes RANK / LOCAL_RANK / WORLD_SIZE from the environment instead.  `--dry-run` 
 stub and RCCL for gloo so that the launcher / sharding / reduction logic runs on a CPU-only box (tests).
 
 FLOPs follow the reference convention 4*B*H*Sq*Skv*D (tests/test_interface.py:121-125).
-The JSON line also carries
+A plain run sets up, settles, warms up, times the K steps and prints the line (`value`, `ms_per_step`, ...); `--dump-outputs DIR`
+also writes the output of the last timed step (float32 .npy, a seeded sample of its rows where it is large).  With `--full` the
+JSON line also carries
   roofline     -- the dominant kernel (the fused attention kernel) alone: algorithmic FLOPs per launch / its average
                   launch duration measured with HIP events on the launch stream INSIDE the step, against the 5.0 PFLOP/s
                   dense fp8 MFMA peak;
@@ -62,8 +64,12 @@ def parse(argv=None):
     ap.add_argument("--causal", action="store_true")
     ap.add_argument("--fp8", default="e4m3", choices=["e4m3", "e5m2"])
     ap.add_argument("--precision", default="auto", choices=["auto", "fast", "accurate"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the sustained run and the C3 / C5 configs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the roofline, live traffic, CPU baseline, accuracy and the other configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR as float32 .npy (a seeded sample of rows above 48 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the sustained run and the C3 / C5 configs")
     ap.add_argument("--settle", type=float, default=0.3,
                     help="seconds of untimed steps BEFORE the W warm-up steps (the idle GPU sits at ~100 MHz and needs ~40 ms of "
                          "load to reach its sustained, power-capped state; 0 = time the cold burst)")
@@ -71,7 +77,10 @@ def parse(argv=None):
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not collect roofline.traffic with rocprofv3 PMC passes of this command (two short child runs in front of the "
                          "measurement); the figure is then read from profiles/traffic.json")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def flops(B, H, Sq, Skv, D, causal):
@@ -335,6 +344,30 @@ def kernel_label(D, fp8, causal, fused_q):
     return f"qattn::attn_fwd_kernel_v4<D={D}, {fp8}, {'causal' if causal else 'full'}, head-wise, byte-exp> (+ two-term launch for early causal rows)"
 
 
+DUMP_BYTES = 48 << 20   # --dump-outputs: float32 bytes written per run, over all ranks
+
+
+def dump_outputs(out_dir, out, rank, world):
+    """--dump-outputs: the output of the last timed step ([B,H,S,D], exact in float32) as `out.npy`; above this rank's share of
+    DUMP_BYTES, a fixed seeded sample of its rows instead: `out_sample.npy` [n, D] and `out_sample_rows.npy`, the rows' flat
+    indices b*H*S + h*S + s (float64).  Under N ranks every file name ends in `_rank<r>`."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    budget = DUMP_BYTES // world // 4   # float32 elements of this rank
+    if out.numel() <= budget:
+        np.save(os.path.join(out_dir, f"out{tag}.npy"), out.detach().float().cpu().numpy())
+        return
+    rows = out.detach().reshape(-1, out.shape[-1])
+    g = torch.Generator(device="cpu")
+    g.manual_seed(0)
+    idx = torch.randperm(rows.shape[0], generator=g)[:budget // rows.shape[1]].sort().values
+    np.save(os.path.join(out_dir, f"out_sample{tag}.npy"), rows[idx.to(rows.device)].float().cpu().numpy())
+    np.save(os.path.join(out_dir, f"out_sample_rows{tag}.npy"), idx.double().numpy())
+
+
 def run_rank(args):
     import torch
 
@@ -404,16 +437,20 @@ def run_rank(args):
             fn()
         fence()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             fn()
+        last = fn()   # the last timed step keeps its output (--dump-outputs)
         fence()
-        return time.perf_counter() - t0
+        return time.perf_counter() - t0, last
 
     if dry:
-        elapsed = timed(step, args.warmup, args.steps)
+        elapsed, last_out = timed(step, args.warmup, args.steps)
     else:
         with qa.config.patch(cfg):
-            elapsed = timed(step, args.warmup, args.steps, args.settle)
+            elapsed, last_out = timed(step, args.warmup, args.steps, args.settle)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out, rank, world)
+    del last_out
     ranks_seen = 1
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -448,8 +485,8 @@ def run_rank(args):
     line["value"] = f_gpu * world * args.steps / elapsed / 1e12
     line["frac_of_fp8_mfma_peak"] = line["value"] / (FP8_PEAK_TFLOPS * world)
 
-    # ---- the dominant kernel (roofline), on rank 0
-    if rank == 0:
+    # ---- --full: the dominant kernel (roofline) and everything else beside the headline, on rank 0
+    if rank == 0 and args.full:
         L = _native.lib()
         fp8_dtype = _native.FP8_DTYPE[args.fp8]
 
@@ -801,6 +838,7 @@ def run_rank(args):
                 print(f"[bench] practical-peak probe skipped: {exc}", file=sys.stderr)
         if not args.no_cpu_baseline and world == 1:  # reported on rank 0 at N=1 only
             line["cpu_baseline"] = cpu_baseline(args, q, k, v)
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()
@@ -813,7 +851,7 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
     # single-GPU run, not a rank of a launcher: the PMC passes for roofline.traffic run as child processes BEFORE anything here touches the GPU
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.dry_run and not args.no_live_traffic:
+    if args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.dry_run and not args.no_live_traffic:
         args.live_traffic = live_traffic(args)
     sys.exit(run_rank(args))
 

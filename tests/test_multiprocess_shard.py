@@ -107,3 +107,27 @@ def test_bench_under_torch_distributed_run_dry_run():
     assert len(lines) == 1, p.stdout
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["config"]["global_batch"] == 8
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_dry_run_dumps_the_last_step_output(gpus, tmp_path):
+    """--dump-outputs DIR: every rank writes what its last timed step returned, in float32 (the --dry-run host stub: SDPA of the
+    rank's shard of the seeded inputs); --steps sets the number of timed steps and must be at least 1."""
+    from quantumattention_amd.utils.shard import batch_shard, synthetic_qkv
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dry-run", "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    names = ["out.npy"] if gpus == 1 else [f"out_rank{r}.npy" for r in range(gpus)]
+    assert sorted(os.listdir(tmp_path)) == names
+    for r, name in enumerate(names):
+        got = np.load(tmp_path / name)
+        q, k, v = synthetic_qkv(batch_shard(4 * gpus, r, gpus), 2, 64, 64)
+        assert got.dtype == np.float32
+        np.testing.assert_allclose(got, torch.nn.functional.scaled_dot_product_attention(q, k, v).float().numpy(), rtol=1e-5, atol=1e-6)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "0"], capture_output=True, text=True,
+                       timeout=120, env=env, cwd=ROOT)
+    assert p.returncode != 0 and "--steps must be >= 1" in p.stderr

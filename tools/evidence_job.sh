@@ -5,12 +5,13 @@
 #   cp profiles/${R}_c2/traffic.json profiles/traffic.json; python tools/pmc_table.py profiles/${R}_c2 profiles/${R}_c3 profiles/${R}_c5 > profiles/$R/pmc_table_c2_c3_c5.md
 R=${ROUND_TAG:-r06}
 mkdir -p gpurun_out/$R
+LOGS=$_   # (the directory just made)
 export TMPDIR=/tmp
 timeout 2400 python -m pytest tests -q -m gpu > gpurun_out/$R/pytest_gpu.log 2>&1
 tail -3 gpurun_out/$R/pytest_gpu.log
 python __graft_entry__.py smoke > gpurun_out/$R/smoke.log 2>&1
 tail -1 gpurun_out/$R/smoke.log
-python bench.py --steps 20 --warmup 5 > gpurun_out/$R/bench_steps20_warmup5.json 2> gpurun_out/$R/bench_steps20_warmup5.err
+python bench.py --full --steps 20 --warmup 5 > $LOGS/bench_steps20_warmup5.json 2> $LOGS/bench_steps20_warmup5.err
 rm -rf gpurun_out/prof_${R}_c2 gpurun_out/prof_${R}_c3 gpurun_out/prof_${R}_c5
 bash tools/profile_bench.sh ${R}_c2 > gpurun_out/$R/prof_c2.log 2>&1
 bash tools/profile_bench.sh ${R}_c3 --causal > gpurun_out/$R/prof_c3.log 2>&1
