@@ -17,6 +17,9 @@ from .quantum_attn_interface import (
     fp8_token_wise_attn_func_with_fallback,
 )
 
+# packed variable-length sequences (flash-attn's varlen call shape): a package attribute beyond the reference's seven exported names
+from .varlen import fp8_attn_varlen_func  # noqa: E402
+
 __version__ = "0.1.0"
 
 __all__ = [

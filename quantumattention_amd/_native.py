@@ -37,6 +37,7 @@ EXPORTS = (
     "qattn_attention_stamp_bytes", "qattn_fp8_quant_attention_forward_stamped", "qattn_mfma_probe_bytes", "qattn_mfma_probe",
     "qattn_fp8_attention_rowmajor_workspace_bytes", "qattn_fp8_attention_forward_rowmajor", "qattn_describe_path",
     "qattn_fp8_quant_attention_forward_strided", "qattn_pack16_strided", "qattn_attention_forward_16_strided",
+    "qattn_varlen_tensor_bytes", "qattn_fp8_quant_attention_varlen_workspace_bytes", "qattn_fp8_quant_attention_varlen_forward",
 )
 
 
@@ -135,6 +136,13 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_attention_forward_rowmajor.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, i, f, i, i, vp, sz, vp]
     L.qattn_describe_path.restype = i
     L.qattn_describe_path.argtypes = [i, i, i, i, i, i, ctypes.POINTER(PathDesc)]
+    L.qattn_varlen_tensor_bytes.restype = sz
+    L.qattn_varlen_tensor_bytes.argtypes = [i, i, i, i, i]
+    L.qattn_fp8_quant_attention_varlen_workspace_bytes.restype = sz
+    L.qattn_fp8_quant_attention_varlen_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    L.qattn_fp8_quant_attention_varlen_forward.restype = i
+    L.qattn_fp8_quant_attention_varlen_forward.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f,
+                                                           vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -566,3 +574,51 @@ def measure_mfma_peak(device=None, *, seconds: float = 0.3, iters: int = 20000, 
         clock = float((st[:, 0] / st[:, 1] * 0.1).median())
     return {"TFLOPs": fl.value / (med * 1e-3) / 1e12, "in_kernel_clock_ghz": clock, "ms_per_launch": med, "launches": len(laps),
             "waves": nw.value, "operands": "constant 1.0" if constant else "random e4m3, |x| in [2^-2, 2^2)"}
+
+
+def varlen_strided_ok(t: torch.Tensor) -> bool:
+    """A packed [total, H, D] view the varlen kernels address directly (include/qattn_varlen.h): the rule of `_strided_ok` -- head_dim
+    innermost and dense, the token and head strides non-negative multiples of 8 elements, base 16-byte aligned."""
+    if t.is_contiguous():
+        return True
+    return (t.stride(2) == 1 and all(t.shape[i] == 1 or (t.stride(i) >= 0 and t.stride(i) % 8 == 0) for i in (0, 1))
+            and t.data_ptr() % 16 == 0)
+
+
+def fp8_quant_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,
+                               seqused_k: Optional[torch.Tensor] = None, *, is_causal: bool = False, fp8_dtype=torch.float8_e4m3fn,
+                               numerics: str = "compiled", sm_scale: float = 0.0, return_lse: bool = False, return_quant: bool = False):
+    """Packed variable-length sequences (qattn_fp8_quant_attention_varlen_forward): q [total_q, Hq, D], k / v [total_k, Hkv, D] bf16 / fp16,
+    int32 cu_seqlens_* [B+1], optional int32 seqused_k [B] -> out [total_q, Hq, D] (and lse fp32 [Hq, total_q]).  The caller has validated
+    the arguments (varlen.py); views that `varlen_strided_ok` accepts are read in place, others copied.  return_quant (test output): also
+    (q8, k8, scale_q, scale_k) -- q8 the row-major per-sequence slabs (uint8, Hq D cu_q[i] bytes in), k8 the KFRAG images (Hkv D (cu_k[i] + 64 i)).
+    Returns out, or a tuple of out, [lse], [q8, k8, scale_q, scale_k]."""
+    q, k, v = (t if varlen_strided_ok(t) else t.contiguous() for t in (q, k, v))
+    total_q, Hq, D = q.shape
+    total_k, Hkv = k.shape[0], k.shape[1]
+    B = cu_seqlens_q.shape[0] - 1
+    strides = None
+    if not (q.is_contiguous() and k.is_contiguous() and v.is_contiguous()):
+        dense = lambda t: (t.shape[1] * D, D)     # (a dimension of size 1 has no stride of its own)
+        strides = (ctypes.c_longlong * 6)(*[t.stride(i) if t.shape[i] > 1 else dense(t)[i] for t in (q, k, v) for i in (0, 1)])
+    L = lib()
+    dev = q.device
+    with torch.cuda.device(dev):
+        out = torch.empty((total_q, Hq, D), dtype=q.dtype, device=dev)
+        lse = torch.empty((Hq, total_q), dtype=torch.float32, device=dev) if return_lse else None
+        q8 = k8 = sq = sk = None
+        if return_quant:
+            q8 = torch.empty((max(L.qattn_varlen_tensor_bytes(LAYOUT_ROWMAJOR, B, Hq, total_q, D), 1),), dtype=torch.uint8, device=dev)
+            k8 = torch.empty((max(L.qattn_varlen_tensor_bytes(LAYOUT_KFRAG, B, Hkv, total_k, D), 1),), dtype=torch.uint8, device=dev)
+            sq = torch.empty((B, Hq), dtype=torch.float32, device=dev)
+            sk = torch.empty((B, Hkv), dtype=torch.float32, device=dev)
+        ws_bytes = L.qattn_fp8_quant_attention_varlen_workspace_bytes(B, Hq, Hkv, total_q, total_k, D)
+        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+        rc = L.qattn_fp8_quant_attention_varlen_forward(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), strides, fmt_of(q.dtype), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(),
+            cu_seqlens_k.data_ptr(), _ptr(seqused_k), B, Hq, Hkv, total_q, total_k, D, fmt_of(fp8_dtype), _numerics(numerics), int(is_causal),
+            float(sm_scale), _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), ws.data_ptr(), ws_bytes, _stream(q))
+    _check(rc, "qattn_fp8_quant_attention_varlen_forward")
+    if not (return_lse or return_quant):
+        return out
+    return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) if return_quant else ())

@@ -101,9 +101,15 @@ __device__ __forceinline__ Vec pv16_operand(v2i32 lo, v2i32 hi) {
 
 // One 256-row query block.  TOKEN: per-row q scales / per-key k scales (standalone entry only); Q16: the fused step's bf16 Q rows,
 // quantised here with the pre-pass's quant8 sequence (the same q8 bytes as every other pass of the kernel).
-template <int D, int NW, int QK_FMT, int V16_FMT, bool CAUSAL, bool TOKEN, bool Q16, int NS = kPv16Slots, bool PP = false, typename DrawIssue, typename DrawFinish>
+// RESOLVED = false: block number `bid` of a whole-tensor launch, mapped to (head, query block) by map_block; true: bid IS the head b Hq + h
+// and resolved_qb the query block (pv16_block_pass_at below: the variable-length kernel, qattn_varlen.hip, resolves its blocks itself).
+// (A compile-time switch inside this function rather than a second function around it: the whole-tensor kernels keep their instructions
+// exactly -- with map_block moved to a caller, or into a callable, they were re-scheduled; tools/isa_diff.py.)
+template <int D, int NW, int QK_FMT, int V16_FMT, bool CAUSAL, bool TOKEN, bool Q16, int NS = kPv16Slots, bool PP = false, bool RESOLVED = false,
+          typename DrawIssue, typename DrawFinish>
 __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned char* smem, int tid, int bid, DrawIssue&& draw_issue_hook,
-                                                DrawFinish&& draw_finish_hook) {   // hooks around the row stores: the D = 128 kernel requests its next block there
+                                                DrawFinish&& draw_finish_hook,   // hooks around the row stores: the D = 128 kernel requests its next block there
+                                                int resolved_qb = 0) {
     static_assert((D == 64 || D == 128 || D == 256) && NW == 8, "the DMA split is written for 8 waves");
     static_assert(!Q16 || D == 128, "the fused in-kernel form belongs to the D = 128 kernel");
     typedef Pv16Type<V16_FMT> T;
@@ -134,7 +140,12 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
     const int ql = lane & 31, hh = lane >> 5;
 
     int head, qb;
-    map_block(p, bid, p.nqb, CAUSAL, head, qb);
+    if constexpr (RESOLVED) {
+        head = bid;
+        qb = resolved_qb;
+    } else {
+        map_block(p, bid, p.nqb, CAUSAL, head, qb);
+    }
     const int b = head / p.Hq, h = head % p.Hq;
     const long bh = (long)b * p.Hq + h;
     const long kv_head = (long)b * p.Hkv + h / (p.Hq / p.Hkv);
@@ -556,6 +567,12 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
     if (p.lse && hh == 0 && qvalid) p.lse[bh * p.lse_stride + qrow] = (0.6931471805599453f * (m_run * c) + __logf(l_tot)) * p.lse_mul;
 #endif
     if (p.path && hh == 0 && qvalid) p.path[bh * p.Sq + qrow] = (unsigned char)QATTN_PATH_V16;
+}
+// the same for query block qb of head `head` = b Hq + h
+template <int D, int NW, int QK_FMT, int V16_FMT, bool CAUSAL, bool TOKEN, bool Q16, int NS = kPv16Slots, bool PP = false, typename DrawIssue, typename DrawFinish>
+__device__ __forceinline__ void pv16_block_pass_at(const AttnParams& p, unsigned char* smem, int tid, int head, int qb, DrawIssue&& draw_issue_hook,
+                                                   DrawFinish&& draw_finish_hook) {
+    pv16_block_pass<D, NW, QK_FMT, V16_FMT, CAUSAL, TOKEN, Q16, NS, PP, true>(p, smem, tid, head, draw_issue_hook, draw_finish_hook, qb);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -163,3 +163,42 @@ def _(t, token_wise, fp8_format="e4m3", numerics="compiled"):
     q = torch.empty(t.shape, dtype=_native.fp8_dtype_of(fp8_format), device=t.device)
     s = torch.empty(t.shape[:3] if token_wise else t.shape[:2], dtype=torch.float32, device=t.device)
     return q, s
+
+
+@_custom_op("quantumattention_amd::fp8_varlen_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_varlen_attention_forward(
+    query: torch.Tensor,
+    key: torch.Tensor,
+    value: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    cu_seqlens_k: torch.Tensor,
+    seqused_k: Optional[torch.Tensor] = None,
+    max_seqlen_q: int = 0,
+    max_seqlen_k: int = 0,
+    is_causal: bool = False,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    return_lse: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """Packed variable-length sequences (include/qattn_varlen.h): query [total_q, Hq, D], key / value [total_k, Hkv, D] bf16 / fp16, int32
+    cu_seqlens_* [B+1], optional int32 seqused_k [B]; per-(sequence, head) fp8 scales, 16-bit P on the 16-bit value.  Returns (out
+    [total_q, Hq, D], lse fp32 [Hq, total_q] -- or an empty [0] tensor without return_lse).  max_seqlen_*: signature compatibility only
+    (the kernels read every length on the device).  Arguments are validated by varlen.fp8_attn_varlen_func."""
+    del max_seqlen_q, max_seqlen_k
+    res = _native.fp8_quant_attention_varlen(
+        query, key, value, cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous(), None if seqused_k is None else seqused_k.contiguous(),
+        is_causal=is_causal, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics, sm_scale=0.0 if scale is None else float(scale),
+        return_lse=return_lse)
+    if return_lse:
+        return res
+    return res, torch.empty((0,), dtype=torch.float32, device=query.device)
+
+
+@_register_fake("quantumattention_amd::fp8_varlen_attention_forward")
+def _(query, key, value, cu_seqlens_q, cu_seqlens_k, seqused_k=None, max_seqlen_q=0, max_seqlen_k=0, is_causal=False, fp8_format="e4m3",
+      numerics="compiled", return_lse=False, *, scale=None):
+    out = query.new_empty((query.shape[0], query.shape[1], value.shape[2]), dtype=value.dtype)
+    lse = query.new_empty((query.shape[1], query.shape[0]) if return_lse else (0,), dtype=torch.float32)
+    return out, lse

@@ -1,0 +1,129 @@
+"""Variable-length (packed) FP8 attention: `fp8_attn_varlen_func`, the call shape of flash-attn's `flash_attn_varlen_func`.
+
+B sequences of different lengths travel packed along the token axis -- q [total_q, Hq, D], k / v [total_k, Hkv, D] -- with int32 offset
+tables cu_seqlens_q / cu_seqlens_k [B+1]; an optional int32 seqused_k [B] counts the keys each sequence uses from its start, so that a
+padded [B, S_pad, H, D] K / V can be passed as a [B S_pad, H, D] view with cu_seqlens_k = arange(B+1) S_pad and seqused_k = k_lens,
+without a copy (Wan-style cross-attention).
+
+Numerics (include/qattn_varlen.h): q and k are quantised head-wise PER (sequence, head) -- exactly `dynamically_quantize_fp8` of each
+sequence on its own, under config.attention.fp8_format / quant_numerics, over the used keys only -- and P.V runs on the reference
+kernel's own numerics, 16-bit P on the original 16-bit value (every row is QATTN_PATH_V16).  config.attention.precision and
+pv_precision do not apply.  Row r of sequence i equals, bit for bit, `fp8_attention_forward_rowmajor(..., pv_16bit=True)` on that
+sequence alone.  `causal` masks top-left per sequence (key j <= query r), as the dense entry and torch SDPA's is_causal; flash-attn >= 2.1
+aligns the diagonal bottom-right when L_q != L_k -- the two agree for self-attention (cu_seqlens_q == cu_seqlens_k).
+"""
+import math
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from . import nn
+from .utils import checks
+
+_INDEX_DTYPE = torch.int32
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, (int, torch.SymInt)) and not isinstance(x, bool)
+
+
+def varlen_input_reason(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None,
+                        seqused_k=None) -> Optional[str]:
+    """The first rule the arguments break, or None.  Shapes, dtypes and devices only: the tables' CONTENTS are read on the device
+    (no host synchronisation), where every extent is clamped to its tensor (include/qattn_varlen.h)."""
+    if dropout_p != 0.0:
+        return "NYI: dropout_p must be 0.0"
+    if not all(isinstance(t, Tensor) for t in (q, k, v)) or q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        return "NYI: query, key and value must be 3-D packed tensors [total_tokens, heads, head_dim]"
+    if any(t.requires_grad for t in (q, k, v)):
+        return "NYI: query, key, and value must be leaf tensors (no backward)"
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        return f"Expected query to have dtype torch.float16 or torch.bfloat16, but got query.dtype: {q.dtype} instead."
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        return f"Expected query, key and value to share a dtype, but got {q.dtype}, {k.dtype}, {v.dtype} instead."
+    if q.shape[-1] != k.shape[-1] or q.shape[-1] != v.shape[-1]:
+        return f"Expect query, key and value to have the same head dimension but got {q.shape[-1]}, {k.shape[-1]} and {v.shape[-1]}."
+    if q.shape[-1] not in nn._HIP_SUPPORTED_HEAD_DIMS:
+        return f"Unsupported head dimension: {q.shape[-1]}"
+    if k.shape != v.shape:
+        return f"Expect key and value to have the same shape but got {tuple(k.shape)} and {tuple(v.shape)}."
+    if k.shape[1] == 0 or q.shape[1] % k.shape[1] != 0:
+        return f"Expect the number of query heads to be a multiple of the key/value heads but got Hq={q.shape[1]} and Hkv={k.shape[1]}."
+    if q.device != k.device or q.device != v.device:
+        return f"Expected query, key, and value to be on the same device, but got {q.device}, {k.device} and {v.device} instead."
+    if q.device.type != "cuda":
+        return "Expected query, key, and value to be on a CUDA device"
+    for name, t in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if not isinstance(t, Tensor) or t.dtype != _INDEX_DTYPE or t.dim() != 1 or t.shape[0] < 2:
+            return f"Expected {name} to be a 1-D torch.int32 tensor of length B+1 >= 2"
+        if t.device != q.device:
+            return f"Expected {name} to be on {q.device}, but got {t.device} instead."
+    if cu_seqlens_q.shape[0] != cu_seqlens_k.shape[0]:
+        return f"Expected cu_seqlens_q and cu_seqlens_k of the same length B+1, but got {cu_seqlens_q.shape[0]} and {cu_seqlens_k.shape[0]}."
+    if seqused_k is not None:
+        if not isinstance(seqused_k, Tensor) or seqused_k.dtype != _INDEX_DTYPE or seqused_k.dim() != 1:
+            return "Expected seqused_k to be a 1-D torch.int32 tensor of length B"
+        if seqused_k.shape[0] != cu_seqlens_q.shape[0] - 1:
+            return f"Expected seqused_k of length B = {cu_seqlens_q.shape[0] - 1}, but got {seqused_k.shape[0]}."
+        if seqused_k.device != q.device:
+            return f"Expected seqused_k to be on {q.device}, but got {seqused_k.device} instead."
+    if not (_is_int(max_seqlen_q) and _is_int(max_seqlen_k)) or max_seqlen_q < 0 or max_seqlen_k < 0:
+        return "Expected max_seqlen_q and max_seqlen_k to be non-negative host ints"
+    if softmax_scale is not None and not (isinstance(softmax_scale, (int, float)) and math.isfinite(softmax_scale) and softmax_scale > 0):
+        return f"softmax_scale must be a finite number > 0 (or None for 1/sqrt(head_dim)), got {softmax_scale!r}"
+    return None
+
+
+def _varlen_eager(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, causal, return_lse):
+    """config.attention.force_eager_fallback: the per-sequence loop of the eager fp8 definition (eager quantiser per sequence and head,
+    de-quantise, aten SDPA: nn._fp8_attention_eager), with the log-sum-exp of the same de-quantised scores."""
+    fp8_dtype = nn._fp8_dtype()
+    total_q, Hq, D = q.shape
+    scale = 1.0 / math.sqrt(D) if softmax_scale is None else float(softmax_scale)
+    cq, ck = cu_seqlens_q.tolist(), cu_seqlens_k.tolist()
+    used = None if seqused_k is None else seqused_k.tolist()
+    out = torch.zeros((total_q, Hq, D), dtype=q.dtype, device=q.device)
+    lse = torch.full((Hq, total_q), -math.inf, dtype=torch.float32, device=q.device)
+    for i in range(len(cq) - 1):
+        lq = cq[i + 1] - cq[i]
+        lk = ck[i + 1] - ck[i] if used is None else min(used[i], ck[i + 1] - ck[i])
+        if lq <= 0 or lk <= 0:
+            continue   # (no key: zero rows, LSE -inf)
+        qi = q[cq[i]:cq[i + 1]].transpose(0, 1)[None]
+        ki, vi = (t[ck[i]:ck[i] + lk].transpose(0, 1)[None] for t in (k, v))
+        q8, sq = nn._dynamically_quantize_fp8(qi, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+        k8, sk = nn._dynamically_quantize_fp8(ki, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+        o = nn._eager_fp8_attention(q8, k8, vi, sq, sk, causal, softmax_scale)
+        out[cq[i]:cq[i + 1]] = o[0].transpose(0, 1)
+        if return_lse:
+            dq = q8.float() * sq[..., None, None]
+            dk = nn._expand_kv_heads(k8.float() * sk[..., None, None], Hq)
+            s = (dq @ dk.transpose(-1, -2)) * scale
+            if causal:
+                s = s.masked_fill(torch.ones(lq, lk, dtype=torch.bool, device=q.device).triu(1), -math.inf)
+            lse[:, cq[i]:cq[i + 1]] = torch.logsumexp(s[0], dim=-1)
+    return (out, lse) if return_lse else out
+
+
+def fp8_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None, causal=False,
+                         *, seqused_k=None, return_lse=False):
+    """FP8 attention over packed variable-length sequences; flash-attn's `flash_attn_varlen_func` argument order (module docstring).
+    q [total_q, Hq, D], k / v [total_k, Hkv, D] bf16 / fp16 (one dtype), D in {64, 128, 256}, Hq a multiple of Hkv; strided views with
+    head_dim innermost are read in place.  cu_seqlens_q / cu_seqlens_k: int32 [B+1] on the device; max_seqlen_*: host ints, accepted for
+    signature compatibility.  seqused_k: optional int32 [B], keys used per sequence (keys beyond it influence no output bit).
+    Returns out [total_q, Hq, D] in the input dtype, or (out, lse) with return_lse (fp32 [Hq, total_q], natural log-sum-exp).  A sequence
+    with no query has no rows; one with queries and no key gives zero rows and an LSE of -inf.  Unsupported input raises ValueError(reason)."""
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = varlen_input_reason(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, seqused_k)
+        if reason is None:
+            ok, reason = nn._pre_check_can_use_hip_attention(device=q.device)
+            reason = None if ok else reason
+        if reason:
+            raise ValueError(reason)
+    if checks.config_value("attention.force_eager_fallback") and not torch.compiler.is_dynamo_compiling():
+        return _varlen_eager(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, causal, return_lse)
+    out, lse = nn._ops().fp8_varlen_attention_forward(
+        q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal),
+        checks.config_value("attention.fp8_format"), checks.config_value("attention.quant_numerics"), bool(return_lse), scale=softmax_scale)
+    return (out, lse) if return_lse else out
