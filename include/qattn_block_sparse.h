@@ -1,0 +1,48 @@
+/*
+ * qattn_block_sparse.h -- block-sparse FP8 attention: a boolean mask over (query block, key block) tiles of 128 x 128 elements says which
+ * tiles are attended; the kernel visits only those (ABI 8 addition; names found by symbol, include/qattn.h unchanged).
+ *
+ * q [B, Hq, Sq, D], k / v [B, Hkv, Skv, D], dense row-major, bf16 or fp16 (in_fmt), D in {64, 128, 256}, Hq a multiple of Hkv.
+ * block_mask: one byte per tile (0 = off, anything else = on), element [b, h, i, j] at byte b s[0] + h s[1] + i s[2] + j s[3] for
+ * b < B, h < Hq, i < ceil(Sq / 128), j < ceil(Skv / 128) (mask_strides: 4 non-negative element strides; 0 broadcasts; NULL = dense).
+ * Tile (i, j) on: query rows 128 i .. 128 i + 127 attend keys 128 j .. 128 j + 127 (the last block of each axis may be ragged).
+ *
+ * Numerics, bit for bit:
+ *   scale_q / q8, scale_k / k8 = the head-wise quant pre-pass (qattn_quant_fp8, QATTN_SCALE_HEAD, `numerics`) of the WHOLE q / k -- keys of
+ *   tiles nobody attends still count toward k's scale.  For query block i with listed key blocks J_i (ascending): gather k8 and v at the
+ *   keys of J_i in ascending order; rows 128 i .. 128 i + 127 of out and lse equal those of qattn_fp8_attention_forward_rowmajor(q8,
+ *   k8_gathered, v_gathered, ..., pv_fmt = in_fmt, is_causal = 0, QATTN_LSE_NATURAL) on the full q8 (PATH TABLE row separate16: FP8 Q K^T,
+ *   16-bit P on the ORIGINAL 16-bit V).  Keys of blocks that query block i does not list influence none of its output bits (the K scale
+ *   aside); a query block with no key block gets zero rows and an LSE of -inf.  sm_scale <= 0: 1/sqrt(D).
+ *
+ *   out       dense [B, Hq, Sq, D] in in_fmt;  lse: NULL or fp32 [B, Hq, Sq] natural log-sum-exp.
+ *   q8 / k8   NULL (then q8 lives in the workspace; k8 is not written) or row-major fp8 [B, Hq, Sq, D] / [B, Hkv, Skv, D] outputs;
+ *   scale_q / scale_k   NULL (workspace) or fp32 [B, Hq] / [B, Hkv] outputs.
+ *
+ * Launches: the quant pre-pass of q and of k, the mask-to-list kernel, the attention kernel.  The mask is read on the device only: no host
+ * synchronisation, no allocation, graph-capture safe (a captured call follows later contents of the mask).  Errors (before any device
+ * call): QATTN_ERR_INVALID_ARG (NULL q / k / v / out / block_mask, a non-positive extent, negative mask strides, bases off 16 bytes, bad
+ * enums), _UNSUPPORTED_DIM (D not in {64, 128, 256}, Hq % Hkv != 0, a key list that does not fit the kernel's LDS: Skv > 2^19 at D = 256),
+ * _UNSUPPORTED_FMT, _WORKSPACE.
+ */
+#ifndef QATTN_BLOCK_SPARSE_H_
+#define QATTN_BLOCK_SPARSE_H_
+
+#include "qattn.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define QATTN_BLOCK_SPARSE_BLOCK 128   /* rows / keys per mask block, both axes */
+
+size_t qattn_fp8_block_sparse_attention_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Skv, int D);
+int qattn_fp8_block_sparse_attention_forward(const void* q, const void* k, const void* v, int in_fmt, void* out, float* lse,
+                                             const void* block_mask, const long long* mask_strides, int B, int Hq, int Hkv, int Sq, int Skv,
+                                             int D, int fp8_fmt, int numerics, float sm_scale, void* q8, void* k8, float* scale_q,
+                                             float* scale_k, void* workspace, size_t workspace_bytes, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* QATTN_BLOCK_SPARSE_H_ */

@@ -38,7 +38,9 @@ EXPORTS = (
     "qattn_fp8_attention_rowmajor_workspace_bytes", "qattn_fp8_attention_forward_rowmajor", "qattn_describe_path",
     "qattn_fp8_quant_attention_forward_strided", "qattn_pack16_strided", "qattn_attention_forward_16_strided",
     "qattn_varlen_tensor_bytes", "qattn_fp8_quant_attention_varlen_workspace_bytes", "qattn_fp8_quant_attention_varlen_forward",
+    "qattn_fp8_block_sparse_attention_workspace_bytes", "qattn_fp8_block_sparse_attention_forward",
 )
+BLOCK_SPARSE_BLOCK = 128   # QATTN_BLOCK_SPARSE_BLOCK (include/qattn_block_sparse.h): rows / keys per mask block
 
 
 class PathDesc(ctypes.Structure):
@@ -143,6 +145,10 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_quant_attention_varlen_forward.restype = i
     L.qattn_fp8_quant_attention_varlen_forward.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f,
                                                            vp, vp, vp, vp, vp, sz, vp]
+    L.qattn_fp8_block_sparse_attention_workspace_bytes.restype = sz
+    L.qattn_fp8_block_sparse_attention_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    L.qattn_fp8_block_sparse_attention_forward.restype = i
+    L.qattn_fp8_block_sparse_attention_forward.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -619,6 +625,40 @@ def fp8_quant_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
             cu_seqlens_k.data_ptr(), _ptr(seqused_k), B, Hq, Hkv, total_q, total_k, D, fmt_of(fp8_dtype), _numerics(numerics), int(is_causal),
             float(sm_scale), _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), ws.data_ptr(), ws_bytes, _stream(q))
     _check(rc, "qattn_fp8_quant_attention_varlen_forward")
+    if not (return_lse or return_quant):
+        return out
+    return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) if return_quant else ())
+
+
+def fp8_block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask: torch.Tensor, *, fp8_dtype=torch.float8_e4m3fn,
+                               numerics: str = "compiled", sm_scale: float = 0.0, return_lse: bool = False, return_quant: bool = False):
+    """Block-sparse attention (qattn_fp8_block_sparse_attention_forward): q [B,Hq,Sq,D], k / v [B,Hkv,Skv,D] bf16 / fp16; block_mask bool,
+    broadcastable to [B, Hq, ceil(Sq/128), ceil(Skv/128)] and read through its strides (an expanded view costs no copy) -> out [B,Hq,Sq,D]
+    (and lse fp32 [B,Hq,Sq]).  return_quant (test output): also (q8, k8, scale_q, scale_k), row-major fp8 and fp32 [B,H].
+    Returns out, or a tuple of out, [lse], [q8, k8, scale_q, scale_k]."""
+    B, Hq, Hkv, Sq, Skv, D = _check_qkv(q, k, v)
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    nb = BLOCK_SPARSE_BLOCK
+    m = block_mask.expand(B, Hq, -(-Sq // nb), -(-Skv // nb))
+    _require(m.dtype == torch.bool and m.device == q.device, f"block_mask must be a torch.bool tensor on {q.device}")
+    strides = (ctypes.c_longlong * 4)(*[m.stride(i) if m.shape[i] > 1 else 0 for i in range(4)])   # (0: broadcast)
+    L = lib()
+    dev = q.device
+    with torch.cuda.device(dev):
+        out = torch.empty((B, Hq, Sq, D), dtype=q.dtype, device=dev)
+        lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev) if return_lse else None
+        q8 = k8 = sq = sk = None
+        if return_quant:
+            q8 = torch.empty((B, Hq, Sq, D), dtype=fp8_dtype, device=dev)
+            k8 = torch.empty((B, Hkv, Skv, D), dtype=fp8_dtype, device=dev)
+            sq = torch.empty((B, Hq), dtype=torch.float32, device=dev)
+            sk = torch.empty((B, Hkv), dtype=torch.float32, device=dev)
+        ws_bytes = L.qattn_fp8_block_sparse_attention_workspace_bytes(B, Hq, Hkv, Sq, Skv, D)
+        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+        rc = L.qattn_fp8_block_sparse_attention_forward(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), fmt_of(q.dtype), out.data_ptr(), _ptr(lse), m.data_ptr(), strides, B, Hq, Hkv, Sq, Skv, D,
+            fmt_of(fp8_dtype), _numerics(numerics), float(sm_scale), _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), ws.data_ptr(), ws_bytes, _stream(q))
+    _check(rc, "qattn_fp8_block_sparse_attention_forward")
     if not (return_lse or return_quant):
         return out
     return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) if return_quant else ())

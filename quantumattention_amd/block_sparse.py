@@ -1,0 +1,115 @@
+"""Block-sparse FP8 attention: `fp8_block_sparse_attn_func`, the call that sliding-tile, radial, Sparse-VideoGen and SpargeAttn-style
+methods need -- a boolean mask over (query block, key block) tiles of BLOCK_M x BLOCK_N = 128 x 128 elements, of which the kernel visits
+only the tiles that are on.
+
+q [B, Hq, Sq, D], k / v [B, Hkv, Skv, D]; block_mask bool, broadcastable to [B, Hq, ceil(Sq/128), ceil(Skv/128)] and read on the device
+through its strides (a [1, 1, nQB, nKB] mask expanded over batch and heads is not copied; no host synchronisation, graph-capture safe).
+
+Numerics (include/qattn_block_sparse.h): q and k are quantised head-wise over the WHOLE tensors -- the bytes and scales of
+`dynamically_quantize_fp8(x, reduction_dim=[2, 3])` under config.attention.fp8_format / quant_numerics, so keys of masked blocks still
+count toward k's scale -- and P.V runs on the reference kernel's own numerics, 16-bit P on the original 16-bit V (as
+`fp8_attn_varlen_func`; config.attention.precision and pv_precision do not apply).  Key blocks are visited in ascending order: rows
+128 i .. 128 i + 127 equal, bit for bit, `fp8_attention_forward_rowmajor(q8, k8[J_i], v[J_i], ..., pv_16bit=True)` on the keys of the
+blocks J_i that query block i lists, gathered in ascending order.  A query block that lists no key block gives zero rows and an LSE of -inf.
+"""
+import math
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from . import nn
+from .utils import checks
+
+BLOCK_M = 128   # query rows per mask block
+BLOCK_N = 128   # keys per mask block
+
+
+def _cdiv(a, b):
+    return (a + b - 1) // b
+
+
+def block_sparse_input_reason(q, k, v, block_mask, scale=None) -> Optional[str]:
+    """The first rule the arguments break, or None.  Shapes, dtypes and devices only: the mask's CONTENTS are read on the device."""
+    if not all(isinstance(t, Tensor) for t in (q, k, v)) or q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        return "NYI: query, key and value must be 4-D tensors [B, heads, seq_len, head_dim]"
+    if any(t.requires_grad for t in (q, k, v)):
+        return "NYI: query, key, and value must be leaf tensors (no backward)"
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        return f"Expected query to have dtype torch.float16 or torch.bfloat16, but got query.dtype: {q.dtype} instead."
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        return f"Expected query, key and value to share a dtype, but got {q.dtype}, {k.dtype}, {v.dtype} instead."
+    if q.shape[-1] != k.shape[-1] or q.shape[-1] != v.shape[-1]:
+        return f"Expect query, key and value to have the same head dimension but got {q.shape[-1]}, {k.shape[-1]} and {v.shape[-1]}."
+    if q.shape[-1] not in nn._HIP_SUPPORTED_HEAD_DIMS:
+        return f"Unsupported head dimension: {q.shape[-1]}"
+    if k.shape != v.shape:
+        return f"Expect key and value to have the same shape but got {tuple(k.shape)} and {tuple(v.shape)}."
+    if k.shape[0] != q.shape[0]:
+        return f"Expect query and key/value to have the same batch size but got {q.shape[0]} and {k.shape[0]}."
+    if k.shape[1] == 0 or q.shape[1] % k.shape[1] != 0:
+        return f"Expect the number of query heads to be a multiple of the key/value heads but got Hq={q.shape[1]} and Hkv={k.shape[1]}."
+    if q.shape[0] == 0 or q.shape[2] == 0 or k.shape[2] == 0:
+        return "Expected a non-empty batch, query sequence and key sequence"
+    if q.device != k.device or q.device != v.device:
+        return f"Expected query, key, and value to be on the same device, but got {q.device}, {k.device} and {v.device} instead."
+    if q.device.type != "cuda":
+        return "Expected query, key, and value to be on a CUDA device"
+    if not isinstance(block_mask, Tensor) or block_mask.dtype != torch.bool:
+        return f"Expected block_mask to be a torch.bool tensor, but got {getattr(block_mask, 'dtype', type(block_mask))}"
+    if block_mask.device != q.device:
+        return f"Expected block_mask to be on {q.device}, but got {block_mask.device} instead."
+    want = (q.shape[0], q.shape[1], _cdiv(q.shape[2], BLOCK_M), _cdiv(k.shape[2], BLOCK_N))
+    shape = tuple(block_mask.shape)
+    if len(shape) > 4 or not all(s == 1 or s == w for s, w in zip(reversed(shape), reversed(want))):
+        return (f"Expected block_mask to broadcast to [B, Hq, ceil(Sq/{BLOCK_M}), ceil(Skv/{BLOCK_N})] = {list(want)}, but got shape "
+                f"{list(shape)}.")
+    if scale is not None and not (isinstance(scale, (int, float)) and not isinstance(scale, bool) and math.isfinite(scale) and scale > 0):
+        return f"scale must be a finite number > 0 (or None for 1/sqrt(head_dim)), got {scale!r}"
+    return None
+
+
+def _block_sparse_eager(q, k, v, block_mask, scale, return_lse):
+    """config.attention.force_eager_fallback: the torch definition -- the eager quantiser over the whole q and k (head-wise), de-quantise,
+    expand the block mask to elements, fp32 attention with the masked scores at -inf; rows that see no key come out as zero (not NaN)
+    with an LSE of -inf."""
+    fp8_dtype = nn._fp8_dtype()
+    B, Hq, Sq, D = q.shape
+    Skv = k.shape[2]
+    sm = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    q8, sq = nn._dynamically_quantize_fp8(q, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+    k8, sk = nn._dynamically_quantize_fp8(k, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+    dq = q8.float() * sq[..., None, None]
+    dk = nn._expand_kv_heads(k8.float() * sk[..., None, None], Hq)
+    dv = nn._expand_kv_heads(v.float(), Hq)
+    m = block_mask.expand(B, Hq, _cdiv(Sq, BLOCK_M), _cdiv(Skv, BLOCK_N))
+    m = m.repeat_interleave(BLOCK_M, dim=2)[:, :, :Sq].repeat_interleave(BLOCK_N, dim=3)[..., :Skv]
+    s = (dq @ dk.transpose(-1, -2)) * sm
+    s = s.masked_fill(~m, -math.inf)
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - lse.clamp_min(torch.finfo(torch.float32).min)[..., None])   # (a row without keys: exp(-inf) = 0)
+    out = (p @ dv).to(q.dtype)
+    return (out, lse) if return_lse else out
+
+
+def fp8_block_sparse_attn_func(q, k, v, block_mask, *, scale=None, return_lse=False):
+    """FP8 attention over the (128-row query block, 128-key block) tiles that `block_mask` turns on (module docstring).
+    q [B, Hq, Sq, D], k / v [B, Hkv, Skv, D] bf16 / fp16 (one dtype), D in {64, 128, 256}, Hq a multiple of Hkv; block_mask bool on the same
+    device, broadcastable to [B, Hq, ceil(Sq/128), ceil(Skv/128)].  scale: softmax scale (None: 1/sqrt(D)).
+    Returns out [B, Hq, Sq, D] in the input dtype, or (out, lse) with return_lse (fp32 [B, Hq, Sq], natural log-sum-exp).  A query block
+    with no key block gives zero rows and an LSE of -inf.  Unsupported input raises ValueError(reason)."""
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = block_sparse_input_reason(q, k, v, block_mask, scale)
+        if reason is None:
+            ok, reason = nn._pre_check_can_use_hip_attention(device=q.device)
+            reason = None if ok else reason
+        if reason:
+            raise ValueError(reason)
+    if checks.config_value("attention.force_eager_fallback") and not torch.compiler.is_dynamo_compiling():
+        return _block_sparse_eager(q, k, v, block_mask, scale, return_lse)
+    B, Hq, Sq = q.shape[0], q.shape[1], q.shape[2]
+    mask = block_mask.expand(B, Hq, _cdiv(Sq, BLOCK_M), _cdiv(k.shape[2], BLOCK_N))   # (a view: broadcast dimensions keep stride 0)
+    out, lse = nn._ops().fp8_block_sparse_attention_forward(
+        q, k, v, mask, checks.config_value("attention.fp8_format"), checks.config_value("attention.quant_numerics"), bool(return_lse),
+        scale=scale)
+    return (out, lse) if return_lse else out

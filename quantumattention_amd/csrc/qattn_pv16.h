@@ -105,13 +105,20 @@ __device__ __forceinline__ Vec pv16_operand(v2i32 lo, v2i32 hi) {
 // and resolved_qb the query block (pv16_block_pass_at below: the variable-length kernel, qattn_varlen.hip, resolves its blocks itself).
 // (A compile-time switch inside this function rather than a second function around it: the whole-tensor kernels keep their instructions
 // exactly -- with map_block moved to a caller, or into a callable, they were re-scheduled; tools/isa_diff.py.)
+// SPARSE (block-sparse attention, qattn_block_sparse.hip; RESOLVED, non-causal, head-wise scales only): the sweep walks the workgroup's
+// key-block list `sparse_list` = {n, e_0 .. e_n-1}, e = (key block j << 2) | (bit 0: rows 0 .. 127 list j, bit 1: rows 128 .. 255), ascending
+// in j, instead of chunks 0 .. nchunks-1.  Sweep position u is chunk 2 j + (u & 1) of entry u >> 1 (the head's last, ragged block may hold
+// one chunk only: it is the list's last entry).  Only listed chunks are DMA'd; a wave computes a position only if its own 128-row half
+// lists the block (wave-uniform: waves 0-3 / 4-7).  A wave's arithmetic is then that of the dense pass on its own listed keys gathered
+// in ascending order; the only extra operations are products with P = 0 on V chunks the wave lists (exact no-ops on finite V).
 template <int D, int NW, int QK_FMT, int V16_FMT, bool CAUSAL, bool TOKEN, bool Q16, int NS = kPv16Slots, bool PP = false, bool RESOLVED = false,
-          typename DrawIssue, typename DrawFinish>
+          bool SPARSE = false, typename DrawIssue, typename DrawFinish>
 __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned char* smem, int tid, int bid, DrawIssue&& draw_issue_hook,
                                                 DrawFinish&& draw_finish_hook,   // hooks around the row stores: the D = 128 kernel requests its next block there
-                                                int resolved_qb = 0) {
+                                                int resolved_qb = 0, const int* sparse_list = nullptr) {
     static_assert((D == 64 || D == 128 || D == 256) && NW == 8, "the DMA split is written for 8 waves");
     static_assert(!Q16 || D == 128, "the fused in-kernel form belongs to the D = 128 kernel");
+    static_assert(!SPARSE || (RESOLVED && !CAUSAL && !TOKEN && !Q16), "the block-sparse sweep: resolved blocks, no causal mask, head-wise scales");
     typedef Pv16Type<V16_FMT> T;
     typedef typename T::vec vec16;
     constexpr int CH = 64 * D;          // fp8 K chunk
@@ -157,7 +164,22 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
     const unsigned char* kg = p.k + kv_head * (long)p.nchunks * CH;
     const unsigned char* vg = v16_head(p, b, h / (p.Hq / p.Hkv), kv_head, RB);   // (the caller's V may be a strided view: rows vrs bytes apart)
     const long vrs = v16_row_stride(p, RB);
-    const int n_wg = CAUSAL ? min(p.nchunks, (min(q0_wg + QWG, p.Sq) - 1) / 64 + 1) : p.nchunks;
+    // SPARSE: the list into LDS behind the ring (the waves read their entries from there), and the number of sweep positions
+    int* const slist = reinterpret_cast<int*>(smem + NS * STAGE);
+    int sp_chunks = 0;
+    if constexpr (SPARSE) {
+        const int n_ent = min(max(__builtin_amdgcn_readfirstlane(sparse_list[0]), 0), ceil_div(p.Skv, 128));
+        for (int i = tid; i < n_ent; i += NW * 64) slist[i] = sparse_list[1 + i];
+        __syncthreads();
+        if (n_ent > 0) sp_chunks = 2 * n_ent - (2 * (__builtin_amdgcn_readfirstlane(slist[n_ent - 1]) >> 2) + 1 >= p.nchunks ? 1 : 0);
+    }
+    // sweep position u -> chunk index; SPARSE: whether this wave's half lists the block of position u (0 <= u < n_wg)
+    auto chunk_of = [&](int u) -> int {
+        if constexpr (SPARSE) return 2 * (__builtin_amdgcn_readfirstlane(slist[max(u, 0) >> 1]) >> 2) + (u & 1);
+        else return u;
+    };
+    auto sp_listed = [&](int u) -> bool { return (__builtin_amdgcn_readfirstlane(slist[u >> 1]) >> (wave >> 2)) & 1; };
+    const int n_wg = SPARSE ? sp_chunks : CAUSAL ? min(p.nchunks, (min(q0_wg + QWG, p.Sq) - 1) / 64 + 1) : p.nchunks;
     const int n_w = CAUSAL ? min(n_wg, (q0 + kQPerWave - 1) / 64 + 1) : p.nchunks;
 
     // ---- one ring stage by LDS-DMA: K chunk t (KP pieces of 1 KiB over the waves) and V rows 64 t .. 64 t + 63 (VPW pieces of RPP rows per wave)
@@ -243,7 +265,7 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
     const float* skt = TOKEN ? p.sk + kv_head * p.Skv : nullptr;
     // the ring's first stages, requested behind the Q loads (the counter is in order: waiting for a stage never waits for Q's successors)
     int issued = 0;
-    for (; issued < (PP ? NS : 2) && issued < n_wg; issued++) dma_stage(issued, issued);
+    for (; issued < (PP ? NS : 2) && issued < n_wg; issued++) dma_stage(chunk_of(issued), issued);
     // ---- per-lane pieces of the transposed-read addresses (T10): lane 4 q4 + p4 of a 16-lane group supplies row R + q4, the 8 bytes
     // at element 4 p4 of the group's 16 columns; the group's columns are d = 32 m + 16 cg .. + 15 (cg = group & 1), its rows start at
     // R = 32 tt + 16 s + 4 hh (elements 0..3 of the operand) and R + 8 (elements 4..7) -- the key order in which the S^T accumulator
@@ -429,10 +451,10 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
             wait_younger(issued - 1 - t);
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            if (issued < n_wg) { dma_stage(issued, issued % NS); issued++; }
-            if (t < n_w) {   // wave-uniform (causal: waves whose rows end earlier keep the barrier cadence)
+            if (issued < n_wg) { dma_stage(chunk_of(issued), issued % NS); issued++; }
+            if (SPARSE ? sp_listed(t) : t < n_w) {   // wave-uniform (causal: waves whose rows end earlier keep the barrier cadence)
                 qk(t, slot);
-                softmax(t, no_hook);
+                softmax(chunk_of(t), no_hook);
                 pv(slot);
             }
             slot = slot == NS - 1 ? 0 : slot + 1;
@@ -491,8 +513,16 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
         };
         // One code path for every trip: the first one multiplies chunk 0's V by P = 0 (pb starts as zeros), the wave's last one computes a
         // QK^T nobody reads (on whatever the slot holds).  Separate PV-only / QK^T-only paths cost registers the loop does not have.
+        // SPARSE: a wave runs the trip if it lists position u (QK^T(u)) or u - 1 (PV(u - 1): the slot of u - 1 is refilled at trip u + 1, so a
+        // listed position's PV never waits for the wave's next listed one).  Without a PV due, the product takes P = 0 (pb is zeroed after
+        // every trip without a softmax) on V(u), a chunk the wave lists -- as the dense first trip takes it on chunk 0.
         auto products = [&](int u) {
-            if (u <= n_w) pv_qk(u >= 1 ? (u - 1) % NS : 0, u % NS);
+            if constexpr (SPARSE) {
+                const bool prev = u >= 1 && sp_listed(u - 1), cur = u < n_wg && sp_listed(u);
+                if (prev || cur) pv_qk(prev ? (u - 1) % NS : u % NS, u % NS);
+            } else {
+                if (u <= n_w) pv_qk(u >= 1 ? (u - 1) % NS : 0, u % NS);
+            }
         };
         {
             const v4i z = {0, 0, 0, 0};
@@ -509,8 +539,13 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
         // 670 and the pass got 3 % slower (profiles/r04/pv16_phase_stamps.log).
         auto softmax_and_dma = [&](int u, bool do_softmax, int t) {
             asm volatile("" ::: "memory");
-            if (u >= 2 && issued < n_wg) { dma_stage(issued, issued % NS); issued++; }   // (stage u - 2's slot: free since the last barrier but one)
+            if (u >= 2 && issued < n_wg) { dma_stage(chunk_of(issued), issued % NS); issued++; }   // (stage u - 2's slot: free since the last barrier but one)
             if (do_softmax) softmax(t, no_hook);
+            else if constexpr (SPARSE) {
+                const v4i z = {0, 0, 0, 0};
+#pragma unroll
+                for (int i = 0; i < 4; i++) __builtin_memcpy(&pb[i >> 1][i & 1], &z, 16);
+            }
         };
         auto mid = [&]() {
             __builtin_amdgcn_s_barrier();
@@ -533,7 +568,7 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
                 PV16_T(0);
                 mid();
                 PV16_T(2);
-                softmax_and_dma(u, u < n_w, u);
+                softmax_and_dma(u, SPARSE ? u < n_wg && sp_listed(u) : u < n_w, chunk_of(u));
                 PV16_T(1);
                 tail(u);
                 PV16_T(3);
@@ -541,7 +576,7 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
         } else {
 #pragma nounroll
             for (int u = 0; u <= n_wg; u++) {
-                softmax_and_dma(u, u >= 1 && u - 1 < n_w, u - 1);
+                softmax_and_dma(u, SPARSE ? u >= 1 && sp_listed(u - 1) : u >= 1 && u - 1 < n_w, chunk_of(u - 1));
                 PV16_T(1);
                 mid();
                 PV16_T(2);
@@ -561,10 +596,12 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
     const float l_lo = bcast_low16(lsum[0]), l_hi = bcast_low16(lsum[1]);
     const float l_tot = (lane & 16) ? l_hi : l_lo;
     const unsigned ticket = draw_issue_hook();
-    store_o_rows<MB>(p.out, p.out_fmt, o, 1.0f / l_tot, out_row_offset(p, bh, qrow, MB * 64), hh, qvalid);
+    // (SPARSE: a half that lists no key block ends with o = 0 and l_tot = 0: zero rows, LSE -inf)
+    store_o_rows<MB>(p.out, p.out_fmt, o, SPARSE ? (l_tot > 0.0f ? 1.0f / l_tot : 0.0f) : 1.0f / l_tot, out_row_offset(p, bh, qrow, MB * 64), hh, qvalid);
     draw_finish_hook(ticket);
 #ifndef QATTN_PV16_STAMP
-    if (p.lse && hh == 0 && qvalid) p.lse[bh * p.lse_stride + qrow] = (0.6931471805599453f * (m_run * c) + __logf(l_tot)) * p.lse_mul;
+    if (p.lse && hh == 0 && qvalid)
+        p.lse[bh * p.lse_stride + qrow] = SPARSE && !(l_tot > 0.0f) ? -INFINITY : (0.6931471805599453f * (m_run * c) + __logf(l_tot)) * p.lse_mul;
 #endif
     if (p.path && hh == 0 && qvalid) p.path[bh * p.Sq + qrow] = (unsigned char)QATTN_PATH_V16;
 }

@@ -202,3 +202,34 @@ def _(query, key, value, cu_seqlens_q, cu_seqlens_k, seqused_k=None, max_seqlen_
     out = query.new_empty((query.shape[0], query.shape[1], value.shape[2]), dtype=value.dtype)
     lse = query.new_empty((query.shape[1], query.shape[0]) if return_lse else (0,), dtype=torch.float32)
     return out, lse
+
+
+@_custom_op("quantumattention_amd::fp8_block_sparse_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_block_sparse_attention_forward(
+    query: torch.Tensor,
+    key: torch.Tensor,
+    value: torch.Tensor,
+    block_mask: torch.Tensor,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    return_lse: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """Block-sparse attention (include/qattn_block_sparse.h): query [B, Hq, Sq, D], key / value [B, Hkv, Skv, D] bf16 / fp16, block_mask
+    bool [B, Hq, ceil(Sq/128), ceil(Skv/128)] (an expanded view is read through its strides); head-wise fp8 scales over the whole tensors,
+    16-bit P on the 16-bit value.  Returns (out [B, Hq, Sq, D], lse fp32 [B, Hq, Sq] -- or an empty [0] tensor without return_lse).
+    Arguments are validated by block_sparse.fp8_block_sparse_attn_func."""
+    res = _native.fp8_block_sparse_attention(query, key, value, block_mask, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics,
+                                             sm_scale=0.0 if scale is None else float(scale), return_lse=return_lse)
+    if return_lse:
+        return res
+    return res, torch.empty((0,), dtype=torch.float32, device=query.device)
+
+
+@_register_fake("quantumattention_amd::fp8_block_sparse_attention_forward")
+def _(query, key, value, block_mask, fp8_format="e4m3", numerics="compiled", return_lse=False, *, scale=None):
+    B, Hq, Sq = query.shape[0], query.shape[1], query.shape[2]
+    out = query.new_empty((B, Hq, Sq, value.shape[3]), dtype=value.dtype)
+    lse = query.new_empty((B, Hq, Sq) if return_lse else (0,), dtype=torch.float32)
+    return out, lse

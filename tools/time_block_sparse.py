@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""Time block-sparse attention (quantumattention_amd.fp8_block_sparse_attn_func, include/qattn_block_sparse.h) against the dense calls:
+  sparse:randP   random block masks of density P (P = 1.0: all tiles on), one draw per (b, h)
+  sparse:band    a diagonal band of +-round(0.07 nKB) key blocks plus the first two key blocks as global columns (density ~0.15)
+  pv16           the bit-identical dense path: dynamically_quantize_fp8 of q and k, then the 16-bit-V rowmajor call (kernel attn_pv16_kernel)
+  auto           the dense fused step fp8_attn_func(q, k, v) with the default precision "auto"
+Shapes: wan = B1 H40 S32760 D128 bf16 (Wan 2.1 14B 480p), b2 = B2 H24 S4096 D128 bf16.
+Step times: HIP events around blocks of `--iters` back-to-back calls, the candidates interleaved block by block over `--rounds` rounds
+(median).  Kernel times: run one candidate at a time under `rocprofv3 --kernel-trace --output-format csv -d DIR -- python
+tools/time_block_sparse.py --cands ...`, then `--summarize DIR` prints the median / min duration of every kernel.
+Prints one JSON line per shape."""
+import argparse
+import csv
+import glob
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = {"wan": (1, 40, 32760, 128), "b2": (2, 24, 4096, 128)}
+ALL = "sparse:rand1.0,sparse:rand0.5,sparse:rand0.25,sparse:rand0.1,sparse:band,pv16,auto"
+
+
+def step_ms(fns, iters, rounds, warmup=2):
+    """ms per call of each of `fns`: blocks of `iters` calls, the candidates interleaved block by block, median over the rounds"""
+    import torch
+
+    for fn in fns:
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    laps = [[] for _ in fns]
+    for _ in range(rounds):
+        for i, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            laps[i].append((e0, e1))
+    torch.cuda.synchronize()
+    return [sorted(a.elapsed_time(b) / iters for a, b in lap)[rounds // 2] for lap in laps]
+
+
+def make_mask(B, H, S, kind, g):
+    import torch
+
+    nb = (S + 127) // 128
+    if kind == "band":
+        w = max(1, round(0.07 * nb))
+        i, j = torch.arange(nb, device="cuda")[:, None], torch.arange(nb, device="cuda")[None, :]
+        return (((i - j).abs() <= w) | (j < 2)).expand(B, H, nb, nb).contiguous()
+    return torch.rand(B, H, nb, nb, generator=g, device="cuda") < float(kind[4:])
+
+
+def run_shape(name, cands, iters, rounds):
+    import torch
+
+    import quantumattention_amd as qa
+    from quantumattention_amd import _native
+
+    B, H, S, D = SHAPES[name]
+    g = torch.Generator(device="cuda").manual_seed(0)
+    q, k, v = (torch.randn(B, H, S, D, generator=g, device="cuda", dtype=torch.float32).to(torch.bfloat16) for _ in range(3))
+    fns, res = [], {"shape": name, "B": B, "H": H, "S": S, "D": D, "dense_flops": 4.0 * B * H * S * S * D}
+    for c in cands:
+        if c.startswith("sparse:"):
+            m = make_mask(B, H, S, c[7:], g)
+            res[f"density[{c}]"] = float(m.float().mean())
+            fns.append(lambda m=m: qa.fp8_block_sparse_attn_func(q, k, v, m))
+        elif c == "pv16":
+            def pv16():
+                q8, sq = qa.dynamically_quantize_fp8(q, reduction_dim=[2, 3])
+                k8, sk = qa.dynamically_quantize_fp8(k, reduction_dim=[2, 3])
+                return _native.fp8_attention_forward_rowmajor(q8, k8, v, sq, sk, is_causal=False, pv_16bit=True)
+            fns.append(pv16)
+        elif c == "auto":
+            fns.append(lambda: qa.fp8_attn_func(q, k, v))
+        else:
+            raise SystemExit(f"unknown candidate {c!r}")
+    for c, ms in zip(cands, step_ms(fns, iters, rounds)):
+        res[f"step_ms[{c}]"] = ms
+    return res
+
+
+def summarize(d):
+    """median / min duration per kernel of the rocprofv3 kernel traces under d"""
+    durs = {}
+    for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
+        for r in csv.DictReader(open(f)):
+            durs.setdefault(r["Kernel_Name"], []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    for name, x in sorted(durs.items(), key=lambda kv: -statistics.median(kv[1])):
+        if "qattn" in name:
+            print(f"  {name[:96]:96s} n {len(x):3d} median {statistics.median(x):10.1f} us  min {min(x):10.1f}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="wan,b2")
+    ap.add_argument("--cands", default=ALL)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--summarize", default="")
+    args = ap.parse_args()
+    if args.summarize:
+        summarize(args.summarize)
+        return
+    from quantumattention_amd import _native
+
+    assert _native.lib().qattn_check_device() == 0, "needs the MI355X"
+    for s in args.shapes.split(","):
+        print(json.dumps(run_shape(s, args.cands.split(","), args.iters, args.rounds)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
