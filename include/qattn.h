@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define QATTN_ABI_VERSION 8   /* 7: lse / row_path on ..._forward_ex, ..._rowmajor, qattn_describe_path; 8: qattn_strided.h */
+#define QATTN_ABI_VERSION 8   /* 7: lse / row_path, ..._rowmajor, qattn_describe_path; 8: qattn_strided.h, qattn_smooth.h */
 
 #define QATTN_FMT_E4M3 0 /* OCP float8_e4m3fn (torch.float8_e4m3fn) */
 #define QATTN_FMT_E5M2 1 /* OCP float8_e5m2   (torch.float8_e5m2)   */

@@ -39,6 +39,7 @@ EXPORTS = (
     "qattn_fp8_quant_attention_forward_strided", "qattn_pack16_strided", "qattn_attention_forward_16_strided",
     "qattn_varlen_tensor_bytes", "qattn_fp8_quant_attention_varlen_workspace_bytes", "qattn_fp8_quant_attention_varlen_forward",
     "qattn_fp8_block_sparse_attention_workspace_bytes", "qattn_fp8_block_sparse_attention_forward",
+    "qattn_fp8_quant_attention_smooth_workspace_bytes", "qattn_fp8_quant_attention_forward_smooth",
 )
 BLOCK_SPARSE_BLOCK = 128   # QATTN_BLOCK_SPARSE_BLOCK (include/qattn_block_sparse.h): rows / keys per mask block
 
@@ -149,6 +150,10 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_block_sparse_attention_workspace_bytes.argtypes = [i, i, i, i, i, i]
     L.qattn_fp8_block_sparse_attention_forward.restype = i
     L.qattn_fp8_block_sparse_attention_forward.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, vp, vp, vp, vp, vp, sz, vp]
+    L.qattn_fp8_quant_attention_smooth_workspace_bytes.restype = sz
+    L.qattn_fp8_quant_attention_smooth_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    L.qattn_fp8_quant_attention_forward_smooth.restype = i   # (..._forward_strided's arguments + float* k_mean: include/qattn_smooth.h)
+    L.qattn_fp8_quant_attention_forward_smooth.argtypes = L.qattn_fp8_quant_attention_forward_strided.argtypes + [vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -453,14 +458,18 @@ def fp8_quant_attention_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tenso
                                 amax_k: Optional[torch.Tensor] = None, amax_v: Optional[torch.Tensor] = None,
                                 ssq_q: Optional[torch.Tensor] = None, ssq_k: Optional[torch.Tensor] = None,
                                 return_lse: bool = False, lse_layout: int = LSE_NATURAL, return_path: bool = False,
-                                output_layout: str = "contiguous"):
+                                output_layout: str = "contiguous", smooth_k: bool = False, return_quant: bool = False):
     """16-bit q, k, v -> attention output: the quant pre-pass and the attention launch(es) in ONE C call
     (qattn_fp8_quant_attention_forward_ex); the pre-pass skips Q where the attention kernel quantises it itself.
     amax_* / ssq_*: per-head abs-max / sum of squares a producer of q, k, v already has (head-wise scaling only): the
     abs-max launch then skips those tensors, or is skipped.
     return_lse: also the per-row log-sum-exp [B,Hq,Sq] (the vector the reference defines, tk/attention.py:333-346), written by the same
     launch as the output.  return_path: also the uint8 [B,Hq,Sq] PATH_* code of every row (test / debug output).
+    smooth_k: key smoothing (qattn_fp8_quant_attention_forward_smooth, include/qattn_smooth.h): K is quantised as fp32(k) - its channel mean
+    over the sequence; amax_k / ssq_k describe the unsmoothed K and are refused.  return_quant (test / debug output): also a dict of what
+    the call left behind -- k8 (KFRAG bytes), scale_q, scale_k, scale_v and, with smooth_k, k_mean fp32 [B,Hkv,D] -- as the last element.
     Returns out, or (out, lse), (out, path), (out, lse, path)."""
+    _require(not smooth_k or (amax_k is None and ssq_k is None), "amax_k / ssq_k describe the unsmoothed key: not with smooth_k")
     B, Hq, Hkv, Sq, Skv, D = _check_qkv(q, k, v)
     # strided views (q = x.view(B, S, H, D).transpose(1, 2), slices of a packed QKV projection, ...) go to the kernels as they are
     # (include/qattn_strided.h); only what the kernels cannot address -- a head_dim that is not innermost and dense, rows off 16 bytes -- is copied
@@ -485,20 +494,28 @@ def fp8_quant_attention_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tenso
         sq = torch.empty((B, Hq) if mode == SCALE_HEAD else (B, Hq, Sq), dtype=torch.float32, device=dev)
         sk = torch.empty((B, Hkv) if mode == SCALE_HEAD else (B, Hkv, Skv), dtype=torch.float32, device=dev)
         sv = torch.empty((B, Hkv), dtype=torch.float32, device=dev)
-        ws_bytes = L.qattn_fp8_quant_attention_workspace_bytes(B, Hq, Hkv, Sq)
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        if not smooth_k:
+            ws_bytes = L.qattn_fp8_quant_attention_workspace_bytes(B, Hq, Hkv, Sq)
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
         lse = torch.empty((B, Hq, L.qattn_lse_row_stride(Sq, lse_layout)), dtype=torch.float32, device=dev) if return_lse else None
         path = torch.empty((B, Hq, Sq), dtype=torch.uint8, device=dev) if return_path else None
-        rc = L.qattn_fp8_quant_attention_forward_strided(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), strides, fmt_of(q.dtype), out.data_ptr(), q8.data_ptr(), kf.data_ptr(),
-            vf.data_ptr(), sq.data_ptr(), sk.data_ptr(), sv.data_ptr(), _ptr(amax_q), _ptr(amax_k), _ptr(amax_v), _ptr(ssq_q),
-            _ptr(ssq_k), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype), mode,
-            _numerics(numerics), int(is_causal), float(sm_scale), _precision(precision), _ptr(lse), lse_layout, _ptr(path),
-            ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_quant_attention_forward_strided")
-    if not (return_lse or return_path):
+        args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), strides, fmt_of(q.dtype), out.data_ptr(), q8.data_ptr(), kf.data_ptr(),
+                vf.data_ptr(), sq.data_ptr(), sk.data_ptr(), sv.data_ptr(), _ptr(amax_q), _ptr(amax_k), _ptr(amax_v), _ptr(ssq_q),
+                _ptr(ssq_k), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype), mode,
+                _numerics(numerics), int(is_causal), float(sm_scale), _precision(precision), _ptr(lse), lse_layout, _ptr(path))
+        k_mean = None
+        if smooth_k:
+            k_mean = torch.empty((B, Hkv, D), dtype=torch.float32, device=dev)
+            ws_bytes = L.qattn_fp8_quant_attention_smooth_workspace_bytes(B, Hq, Hkv, Sq, Skv, D)
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            rc = L.qattn_fp8_quant_attention_forward_smooth(*args, ws.data_ptr(), ws_bytes, _stream(q), k_mean.data_ptr())
+        else:
+            rc = L.qattn_fp8_quant_attention_forward_strided(*args, ws.data_ptr(), ws_bytes, _stream(q))
+    _check(rc, "qattn_fp8_quant_attention_forward_smooth" if smooth_k else "qattn_fp8_quant_attention_forward_strided")
+    if not (return_lse or return_path or return_quant):
         return out
-    return (out,) + ((lse[..., :Sq],) if return_lse else ()) + ((path,) if return_path else ())
+    quant = {"k8": kf, "scale_q": sq, "scale_k": sk, "scale_v": sv, "k_mean": k_mean}
+    return (out,) + ((lse[..., :Sq],) if return_lse else ()) + ((path,) if return_path else ()) + ((quant,) if return_quant else ())
 
 
 def measure_attention_clock(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, is_causal: bool = False, precision: str = "auto",

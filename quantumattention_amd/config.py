@@ -31,6 +31,14 @@ class attention:
     #   "accurate" the precise pass everywhere (about bf16-P accuracy, ~1.5x the matrix work)
     precision = os.getenv("QUANTUM_ATTN_PRECISION", "auto")
 
+    # key smoothing (SageAttention's "smooth-K"; include/qattn_smooth.h): the dense fp8 entries on 16-bit q / k / v subtract the
+    # mean of K over the sequence, per (batch, kv head, channel), in fp32 before quantising it.  The softmax rows do not change
+    # (q.(k_j - m) = q.k_j - q.m, the same shift for every key of a row), the fp8 error of K does: keys with a large per-channel offset
+    # shared by all tokens (image / video DiTs) lose ~10x in output RMSE without it.  Costs one more read of K.  Off by default: every
+    # call then produces the bits it always did.  fp8_attn_varlen_func / fp8_block_sparse_attn_func and pre-quantised q / k ignore it.
+    # Passed to the fused op as an argument, like precision: a compiled graph bakes it in at trace time and does not follow a later change.
+    smooth_k = os.getenv("QUANTUM_ATTN_SMOOTH_K") == "1"
+
     # the P.V product of `fp8_attention_forward` on pre-quantised query / key (the reference's op contract: value arrives in 16 bit):
     #   "fp8"    (default) value is quantised to fp8 per head and both GEMMs run on FP8 MFMA (north_star)
     #   "16bit"  the reference kernel's own numerics: 16-bit P on the un-quantised value, bf16 / fp16 MFMA (head_dim 64 / 128 / 256;

@@ -7,6 +7,7 @@
 
 #include "qattn_attn.h"
 #include "qattn_pv16.h"
+#include "../../include/qattn_smooth.h"
 
 using namespace qattn;
 
@@ -312,7 +313,7 @@ static int quant_attention_impl(const void* q, const void* k, const void* v, int
                                 const float* ssq_q, const float* ssq_k, int B, int Hq, int Hkv, int Sq, int Skv,
                                 int D, int fp8_fmt, int scale_mode, int numerics, int is_causal, float sm_scale,
                                 int precision, float* lse, int lse_layout, unsigned char* row_path, void* workspace, size_t workspace_bytes,
-                                void* stream, unsigned long long* stamps, const long long* strides = nullptr) {
+                                void* stream, unsigned long long* stamps, const long long* strides = nullptr, float* k_mean = nullptr) {
     if (!q || !k || !v || !out || !q8 || !k8 || !v8 || !scale_q || !scale_k || !scale_v) return QATTN_ERR_INVALID_ARG;
     if (lse_layout != QATTN_LSE_NATURAL && lse_layout != QATTN_LSE_REFERENCE) return QATTN_ERR_INVALID_ARG;
     if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0 || Skv <= 0) return QATTN_ERR_INVALID_ARG;
@@ -323,6 +324,10 @@ static int quant_attention_impl(const void* q, const void* k, const void* v, int
     if (in_fmt != QATTN_FMT_BF16 && in_fmt != QATTN_FMT_FP16) return QATTN_ERR_UNSUPPORTED_FMT;
     if (fp8_fmt != QATTN_FMT_E4M3 && fp8_fmt != QATTN_FMT_E5M2) return QATTN_ERR_UNSUPPORTED_FMT;
     if ((amax_q || amax_k || amax_v || ssq_q || ssq_k) && scale_mode != QATTN_SCALE_HEAD) return QATTN_ERR_INVALID_ARG;   // per-head figures
+    // key smoothing (include/qattn_smooth.h): k_mean != nullptr; the per-block channel sums of the mean pass live behind the plain workspace
+    const bool smooth = k_mean != nullptr;
+    if (smooth && (amax_k || ssq_k || (reinterpret_cast<uintptr_t>(k_mean) & 15u) != 0)) return QATTN_ERR_INVALID_ARG;   // (they describe the unsmoothed K)
+    if (smooth) ssq_q = nullptr;   // (no sum for K to go with it: both come from the pre-pass)
     if ((ssq_q == nullptr) != (ssq_k == nullptr)) return QATTN_ERR_INVALID_ARG;
     if (strides) {
         // strided views of the 16-bit inputs (qattn_fp8_quant_attention_forward_strided): D innermost and dense, every row 16-byte aligned,
@@ -336,7 +341,8 @@ static int quant_attention_impl(const void* q, const void* k, const void* v, int
         }
         if ((B > 1 && strides[9] == 0) || (Hq > 1 && strides[10] == 0)) return QATTN_ERR_INVALID_ARG;   // (`out` cannot be a broadcast view)
     }
-    if (!workspace || workspace_bytes < qattn_fp8_quant_attention_workspace_bytes(B, Hq, Hkv, Sq)) return QATTN_ERR_WORKSPACE;
+    if (!workspace || workspace_bytes < (smooth ? qattn_fp8_quant_attention_smooth_workspace_bytes(B, Hq, Hkv, Sq, Skv, D)
+                                                : qattn_fp8_quant_attention_workspace_bytes(B, Hq, Hkv, Sq))) return QATTN_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const bool fuse_q = q_fusion_ok(D, in_fmt, scale_mode, is_causal);
     // the measurement entry exists for one instantiation only: refuse before the pre-pass has written anything
@@ -365,9 +371,20 @@ static int quant_attention_impl(const void* q, const void* k, const void* v, int
     const bool zero_in_prepass = attn_ws != nullptr;
     const size_t zero_bytes = attn_v2_covers(D, is_causal, scale_mode) ? sched_bytes()
                               : precision == QATTN_PRECISION_AUTO ? attn_ws_sched_bytes(B, Hq, Sq) + attn_ws_flag_bytes(B, Hq, Sq) : 0;
-    int rc = launch_quant_qkv(q, k, v, in_fmt, q8, k8, v8, scale_q, scale_k, scale_v, B, Hq, Hkv, Sq, Skv, D, fp8_fmt, scale_mode,
+    int rc = QATTN_OK;
+    if (smooth) {
+        // K first, in three launches of its own (mean, abs-max, quantise), then q and V in the plain pre-pass: measured against the other
+        // order in profiles/smooth_k/
+        const size_t nq = (size_t)B * Hq, nk = (size_t)B * Hkv;
+        float* mean_part = reinterpret_cast<float*>((unsigned char*)workspace + (qattn_fp8_quant_attention_workspace_bytes(B, Hq, Hkv, Sq) + 15) / 16 * 16);
+        rc = launch_smooth_k(k, in_fmt, k8, scale_k, k_mean, B, Hkv, Skv, D, fp8_fmt, scale_mode, numerics, ws + kMomentSplits * nq,
+                             moments ? reinterpret_cast<float*>(ws + kMomentSplits * (nq + 2 * nk)) + nq * kMomentSplits : nullptr,
+                             amax_splits(Sq, Skv, D), mean_part, st, strides ? strides + 3 : nullptr);
+        if (rc != QATTN_OK) return rc;
+    }
+    rc = launch_quant_qkv(q, k, v, in_fmt, q8, k8, v8, scale_q, scale_k, scale_v, B, Hq, Hkv, Sq, Skv, D, fp8_fmt, scale_mode,
                               numerics, ws, fuse_q, moments, v_block, st, ext_amax, zero_in_prepass && zero_bytes ? (unsigned*)attn_ws : nullptr,
-                              zero_in_prepass ? (int)(zero_bytes / sizeof(unsigned)) : 0, strides);
+                              zero_in_prepass ? (int)(zero_bytes / sizeof(unsigned)) : 0, strides, smooth);
     if (rc != QATTN_OK) return rc;
     if (row_path) {   // every row starts as "one-term fp8-V sweep"; the other passes overwrite what they store
         const long n = (long)B * Hq * Sq;
@@ -384,7 +401,32 @@ static int quant_attention_impl(const void* q, const void* k, const void* v, int
                fuse_q ? q : nullptr, fuse_q ? (q_ext ? reinterpret_cast<const unsigned*>(amax_q) : mom.amax_q) : nullptr, fuse_q ? scale_q : nullptr, numerics,
                q_ext ? 1 : mom.nsplit, q_ext ? 1 : kMomentSplits, v, stamps, zero_in_prepass, row_path, strides, strides ? strides + 6 : nullptr, strides ? strides + 9 : nullptr};
     DeviceState* ds = t_profile ? device_state(!stream_is_capturing(st)) : nullptr;
-    return attention_impl(a, st, ds);
+    rc = attention_impl(a, st, ds);
+    if (rc != QATTN_OK || !smooth || !lse) return rc;
+    // the launch wrote the LSE of the smoothed scores; the true scores of row i lie sm_scale * q_i.m higher
+    const float sm = sm_scale > 0.0f ? sm_scale : 1.0f / sqrtf((float)D);
+    return launch_smooth_lse(q, in_fmt, k_mean, lse, (long)qattn_lse_row_stride(Sq, lse_layout), B, Hq, Hkv, Sq, D,
+                             sm * (lse_layout == QATTN_LSE_REFERENCE ? -sqrtf((float)D) : 1.0f), st, strides);
+}
+
+extern "C" size_t qattn_fp8_quant_attention_smooth_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Skv, int D) {
+    if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0 || Skv <= 0 || (D != 64 && D != 128 && D != 256)) return 0;
+    return (qattn_fp8_quant_attention_workspace_bytes(B, Hq, Hkv, Sq) + 15) / 16 * 16 + smooth_k_workspace_bytes(B, Hkv, D);
+}
+
+// The fused entry with key smoothing (include/qattn_smooth.h): K is quantised as fp32(k) - its channel mean over the sequence; `out` is
+// mathematically that of qattn_fp8_quant_attention_forward_strided, the LSE is corrected to that of the true scores.
+extern "C" int qattn_fp8_quant_attention_forward_smooth(const void* q, const void* k, const void* v, const long long* strides, int in_fmt, void* out,
+                                                        void* q8, void* k8, void* v8, float* scale_q, float* scale_k, float* scale_v,
+                                                        const float* amax_q, const float* amax_k, const float* amax_v,
+                                                        const float* ssq_q, const float* ssq_k, int B, int Hq, int Hkv, int Sq, int Skv,
+                                                        int D, int fp8_fmt, int scale_mode, int numerics, int is_causal, float sm_scale,
+                                                        int precision, float* lse, int lse_layout, unsigned char* row_path, void* workspace,
+                                                        size_t workspace_bytes, void* stream, float* k_mean) {
+    if (!k_mean) return QATTN_ERR_INVALID_ARG;
+    return quant_attention_impl(q, k, v, in_fmt, out, q8, k8, v8, scale_q, scale_k, scale_v, amax_q, amax_k, amax_v, ssq_q, ssq_k, B, Hq, Hkv,
+                                Sq, Skv, D, fp8_fmt, scale_mode, numerics, is_causal, sm_scale, precision, lse, lse_layout, row_path, workspace,
+                                workspace_bytes, stream, nullptr, strides, k_mean);
 }
 
 extern "C" int qattn_fp8_quant_attention_forward_ex(const void* q, const void* k, const void* v, int in_fmt, void* out, void* q8,

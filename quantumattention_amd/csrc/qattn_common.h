@@ -346,6 +346,19 @@ int launch_quant_qkv(const void* q, const void* k, const void* v, int in_fmt, vo
                      int numerics, unsigned* ws, bool skip_q_payload, bool want_moments, bool v_block, hipStream_t st,
                      const float* const* ext_amax = nullptr, unsigned* zero_words = nullptr, int zero_n = 0,   // zero_words: a few scratch
                      // words of the NEXT kernel in the stream (the attention launch's hand-out counters) that the quantise pass clears on the way
-                     const long long* strides = nullptr);   // element strides {batch, head, row} of q, k, v (9 values; nullptr: dense [B,H,S,D])
+                     const long long* strides = nullptr,   // element strides {batch, head, row} of q, k, v (9 values; nullptr: dense [B,H,S,D])
+                     bool skip_k = false);   // K takes no part in either launch (key smoothing: launch_smooth_k below quantises it)
+
+// Key smoothing (include/qattn_smooth.h; qattn_smooth_k.hip).  launch_smooth_k: channel mean of K -> k_mean [B*Hkv][D], then K's abs-max
+// pass (head-wise scales: `nsplit` words per head in amax_part_k, and sums of squares in part_k unless nullptr -- the slots K has in
+// launch_quant_qkv's workspace) and quantise pass on fp32(k) - mean.  mean_part: smooth_k_workspace_bytes() of scratch.
+// launch_smooth_lse: lse[b,h,i] += mul * q[b,h,i,:].k_mean[kv head,:].
+constexpr int kMeanSplits = 64;   // >= the mean pass's blocks per head
+size_t smooth_k_workspace_bytes(int B, int Hkv, int D);
+int launch_smooth_k(const void* k, int in_fmt, void* k8, float* scale_k, float* k_mean, int B, int Hkv, int Skv, int D, int out_fmt,
+                    int scale_mode, int numerics, unsigned* amax_part_k, float* part_k, int nsplit, float* mean_part, hipStream_t st,
+                    const long long* kstrides);
+int launch_smooth_lse(const void* q, int in_fmt, const float* k_mean, float* lse, long lse_stride, int B, int Hq, int Hkv, int Sq, int D,
+                      float mul, hipStream_t st, const long long* qstrides);
 
 }  // namespace qattn

@@ -460,7 +460,7 @@ extern "C" int qattn_quant_qkv_fp8(const void* q, const void* k, const void* v, 
 int qattn::launch_quant_qkv(const void* q, const void* k, const void* v, int in_fmt, void* q8, void* k8, void* v8, float* scale_q,
                             float* scale_k, float* scale_v, int B, int Hq, int Hkv, int Sq, int Skv, int D, int out_fmt,
                             int scale_mode, int numerics, unsigned* ws, bool skip_q_payload, bool want_moments, bool v_block, hipStream_t st,
-                            const float* const* ext_amax, unsigned* zero_words, int zero_n, const long long* strides) {
+                            const float* const* ext_amax, unsigned* zero_words, int zero_n, const long long* strides, bool skip_k) {
     const int tok = scale_mode == QATTN_SCALE_TOKEN;
     const unsigned* ext[3] = {nullptr, nullptr, nullptr};
     if (ext_amax)
@@ -484,9 +484,13 @@ int qattn::launch_quant_qkv(const void* q, const void* k, const void* v, int in_
                          Hkv, sv3(2, Hkv, Skv, 0), sv3(2, Hkv, Skv, 1), sv3(2, Hkv, Skv, 2)};
     // the tensors the abs-max pass still has to read: head-wise ones without a caller-supplied abs-max (q, k: not with token-wise
     // scales; V always has one scale per head, or none of its own when block-scaled)
+    // skip_k (key smoothing): K is quantised by launches of its own (qattn_smooth_k.hip).  Its job moves to slot 0, below the slots the
+    // quantise pass walks (2 = v, 1 = q), and takes no part in the abs-max pass; the kernels are the same.
+    if (skip_k) { const QuantJob kj = jobs.j[1]; jobs.j[1] = jobs.j[0]; jobs.j[0] = kj; }
+    const int slot[3] = {skip_k ? 1 : 0, skip_k ? 0 : 1, 2};
     int npass = 0;
     for (int t = 0; t < 3; t++)
-        if ((!ext[t] || (moments && t < 2)) && (t == 2 ? !vblock : !tok)) jobs.zmap[npass++] = t;   // (moments: q and k are read for their sums of squares whoever supplies the abs-max)
+        if ((!ext[t] || (moments && t < 2)) && (t == 2 ? !vblock : !tok) && !(skip_k && t == 1)) jobs.zmap[npass++] = slot[t];   // (moments: q and k are read for their sums of squares whoever supplies the abs-max)
     for (int t = npass; t < 3; t++) jobs.zmap[t] = 0;
     // (Tried and dropped: one tensor at a time -- amax then quantise, hoping the re-read hits the 256 MiB Infinity Cache --
     // was 13 % slower than the two fused launches; a one-pass register-resident variant with a cross-workgroup amax
@@ -512,7 +516,7 @@ int qattn::launch_quant_qkv(const void* q, const void* k, const void* v, int in_
         }
     }
     // the quantise pass walks jobs ztop, ztop-1, ...: with skip_q_payload only v and k (blockIdx.z = 0, 1)
-    dim3 grid((((skip_q_payload ? Skv : Smax) + 63) / 64 + kQuantTilesPerBlock - 1) / kQuantTilesPerBlock, skip_q_payload ? B * Hkv : Gmax, skip_q_payload ? 2 : 3);
+    dim3 grid((((skip_q_payload ? Skv : Smax) + 63) / 64 + kQuantTilesPerBlock - 1) / kQuantTilesPerBlock, skip_q_payload ? B * Hkv : Gmax, (skip_q_payload ? 2 : 3) - (skip_k ? 1 : 0));
     int rc;
     const bool sv = strides != nullptr;
     if (D == 64) rc = launch_quant_multi<64>(jobs, in_fmt, out_fmt, numerics, grid, 2, st, sv);

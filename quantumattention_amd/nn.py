@@ -338,6 +338,10 @@ def _fp8_attention_wrapper(query, key, value, attn_mask=None, dropout_p=0.0, is_
             raise ValueError("amax_q / amax_k / ssq_q / ssq_k are per-head figures: head-wise scaling only")
         if (ssq_q is None) != (ssq_k is None):
             raise ValueError("ssq_q and ssq_k must be both provided or both not provided")
+        # key smoothing (config.attention.smooth_k): the op quantises key - its channel mean; figures of the unsmoothed key are of no use
+        smooth_k = bool(_cfg("smooth_k"))
+        if smooth_k and (amax_k is not None or ssq_k is not None):
+            raise ValueError("amax_k / ssq_k describe the unsmoothed key: not with config.attention.smooth_k")
         amax_v = None
         if (torch.compiler.is_dynamo_compiling() and scaling_method == "head-wise" and not any(given)
                 and _cfg("inline_abs_max_under_compile")):
@@ -347,18 +351,19 @@ def _fp8_attention_wrapper(query, key, value, attn_mask=None, dropout_p=0.0, is_
             # them into the producer's kernel -- and handed to the op, whose abs-max launch then has nothing left to read
             # (qattn_fp8_quant_attention_forward_ex).  abs().amax() of a 16-bit tensor is exact, so the scales and the output are
             # those of the eager call bit for bit (sums of squares: include/qattn.h on the dead-band edge).
-            amax_q, amax_k = _head_abs_max(query), _head_abs_max(key)
+            amax_q, amax_k = _head_abs_max(query), (None if smooth_k else _head_abs_max(key))   # (smooth_k: K's abs-max is that of key - mean)
             # V's abs-max only where V gets one scale per head: on the block-scaled paths (the headline one among them) the op never
             # reads it, and an op input cannot be eliminated as dead code -- the graph would carry a full extra read of V.
             # head_dim, dtype and the key length are static at trace time (mark_static above; a symbolic length counts as long).
             skv = key.shape[-2]
             if not isinstance(skv, int) or checks.fused_step_scales_v_per_head(query.shape[-1], query.dtype, scaling_method, skv):
                 amax_v = _head_abs_max(value)
-            if _cfg("precision") == "auto":
+            if _cfg("precision") == "auto" and not smooth_k:   # (smooth_k: both sums come from the pre-pass, K's being that of key - mean)
                 ssq_q, ssq_k = _head_sum_sq(query), _head_sum_sq(key)
         return ops.fp8_quant_attention_forward(
             query, key, value, is_causal, scaling_method, _cfg("fp8_format"),
-            _cfg("quant_numerics"), _cfg("precision"), amax_q, amax_k, ssq_q, ssq_k, amax_v, _cfg("output_layout"), scale=scale)
+            _cfg("quant_numerics"), _cfg("precision"), amax_q, amax_k, ssq_q, ssq_k, amax_v, _cfg("output_layout"), scale=scale,
+            smooth_k=smooth_k)
     if any(t is not None for t in (amax_q, amax_k, ssq_q, ssq_k)):
         raise ValueError("amax_q / amax_k describe 16-bit query / key; fp8 query / key come with scale_q / scale_k")
     return ops.fp8_attention_forward(
@@ -378,6 +383,9 @@ def _fp8_attention_eager(query, key, value, is_causal, scale, scale_q, scale_k, 
         else:
             raise ValueError(f"Unsupported scaling_method: {scaling_method}")
         query, scale_q = _dynamically_quantize_fp8(query, reduction_dim=reduction_dim)
+        if _cfg("smooth_k"):   # key smoothing restated: fp32 mean over the sequence, fp32 subtraction, then the same quantiser
+            key = key.to(torch.float32)
+            key = key - key.mean(dim=-2, keepdim=True)
         key, scale_k = _dynamically_quantize_fp8(key, reduction_dim=reduction_dim)
     return _eager_fp8_attention(query, key, value, scale_q, scale_k, is_causal, scale)
 
@@ -391,7 +399,9 @@ def fp8_attention(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=Fa
     skipped pass would have collected (without them heads with a wide score spread start one-term: same bound, other bits).
     Preconditions on amax_*: finite, >= the tensor's true abs-max (a smaller value clips; the sign is ignored; a NaN makes the head's
     scale NaN).  With only one of amax_q / amax_k and no ssq_* under precision="auto" nothing is saved (both tensors are still read for
-    their sums of squares) and the result is the plain call's, bit for bit."""
+    their sums of squares) and the result is the plain call's, bit for bit.
+    config.attention.smooth_k (16-bit query / key only): key is quantised as key - its per-channel mean over the sequence (include/qattn_smooth.h);
+    amax_k / ssq_k then raise ValueError.  Pre-quantised query / key (scale_q / scale_k given) ignore the flag: the caller quantised."""
     supported, reason = can_use_attention(
         query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal, scale=scale,
         scaling_method=scaling_method, scale_q=scale_q, scale_k=scale_k)

@@ -128,6 +128,7 @@ def fp8_quant_attention_forward(
     output_layout: str = "contiguous",
     *,
     scale: Optional[float] = None,
+    smooth_k: bool = False,
 ) -> torch.Tensor:
     """Fused entry for 16-bit inputs: the quant pre-pass (nn.py:410-418) writes K and V straight into the MFMA
     fragment layouts, then the attention kernel runs -- what `_fp8_attention_wrapper` (nn.py:394-430) does in the
@@ -136,16 +137,19 @@ def fp8_quant_attention_forward(
     the hand-off the reference gets from Inductor fusing the quantiser into the producer.  ssq_q / ssq_k (fp32 [B,H], both or
     neither): per-head sums of squares, which keep precision="auto" its score-spread estimate when the abs-max pass is skipped.
     amax_v (fp32 [B,Hkv]): the same for value, read only where V has one scale per head (token-wise scales, or more than 16384 keys per
-    head; elsewhere the fused step scales V per 64-key chunk inside the quantise pass and needs no abs-max of it: include/qattn.h PATH TABLE)."""
+    head; elsewhere the fused step scales V per 64-key chunk inside the quantise pass and needs no abs-max of it: include/qattn.h PATH TABLE).
+    smooth_k: key smoothing (include/qattn_smooth.h; config.attention.smooth_k): key is quantised as fp32(key) - its per-channel mean over
+    the sequence; amax_k / ssq_k (figures of the unsmoothed key) are refused with it."""
     return _native.fp8_quant_attention_forward(
         query, key, value, is_causal=is_causal, scaling=scaling_method, fp8_dtype=_native.fp8_dtype_of(fp8_format),
         numerics=numerics, sm_scale=0.0 if scale is None else float(scale), precision=precision, amax_q=amax_q, amax_k=amax_k,
-        amax_v=amax_v, ssq_q=ssq_q, ssq_k=ssq_k, output_layout=output_layout)
+        amax_v=amax_v, ssq_q=ssq_q, ssq_k=ssq_k, output_layout=output_layout, smooth_k=smooth_k)
 
 
 @_register_fake("quantumattention_amd::fp8_quant_attention_forward")
 def _(query, key, value, is_causal=False, scaling_method="head-wise", fp8_format="e4m3", numerics="compiled",
-      precision="auto", amax_q=None, amax_k=None, ssq_q=None, ssq_k=None, amax_v=None, output_layout="contiguous", *, scale=None):
+      precision="auto", amax_q=None, amax_k=None, ssq_q=None, ssq_k=None, amax_v=None, output_layout="contiguous", *, scale=None,
+      smooth_k=False):
     return _out_like(query, value, output_layout)
 
 
