@@ -42,6 +42,31 @@ int qattn_fp8_block_sparse_attention_forward(const void* q, const void* k, const
                                              int D, int fp8_fmt, int numerics, float sm_scale, void* q8, void* k8, float* scale_q,
                                              float* scale_k, void* workspace, size_t workspace_bytes, void* stream);
 
+
+/*
+ * Key smoothing (include/qattn_smooth.h: K is quantised as fp32(k) - its channel mean, `out` is mathematically unchanged, the LSE is
+ * corrected by sm_scale * q.m).  An ABI-8 addition, names found by symbol; the plain entry keeps its signature, launches and bits.
+ * q.m is the same for every key a row attends, whichever keys a block mask lists and whichever sequence a packed row belongs to.
+ *
+ * qattn_fp8_block_sparse_attention_forward_smooth: the arguments of qattn_fp8_block_sparse_attention_forward plus k_mean (as above).
+ * The mean is taken over the WHOLE Skv per (batch, kv head, channel) -- keys of tiles nobody attends count toward it, as toward K's
+ * scale -- so k_mean, scale_k and k8 are, bit for bit, those of qattn_fp8_quant_attention_forward_smooth (QATTN_SCALE_HEAD) on the same K.
+ *   k8   NULL, or an output of qattn_fp8_tensor_bytes(QATTN_LAYOUT_KFRAG, B, Hkv, Skv, D) bytes: the KFRAG image the attention kernel
+ *        reads (the plain entry returns row-major bytes there; the smoothing passes only produce the kernel's own layout).
+ * q's pre-pass, the mask-to-list kernel and the attention kernel are those of the plain entry; K goes through the mean, abs-max and
+ * quantise launches of the dense smoothing entry in place of its share of the pre-pass; lse (when non-NULL) is corrected by
+ * sm_scale * q.k_mean after the attention launch.  A query block without keys still gives zero rows and an LSE of -inf.
+ *
+ * Workspace: at least ..._smooth_workspace_bytes(...), 16-byte aligned; errors as the plain entry, and
+ * QATTN_ERR_INVALID_ARG for a NULL or misaligned k_mean.
+ */
+size_t qattn_fp8_block_sparse_attention_smooth_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Skv, int D);
+int qattn_fp8_block_sparse_attention_forward_smooth(const void* q, const void* k, const void* v, int in_fmt, void* out, float* lse,
+                                                    const void* block_mask, const long long* mask_strides, int B, int Hq, int Hkv, int Sq,
+                                                    int Skv, int D, int fp8_fmt, int numerics, float sm_scale, void* q8, void* k8,
+                                                    float* scale_q, float* scale_k, void* workspace, size_t workspace_bytes, void* stream,
+                                                    float* k_mean);
+
 #ifdef __cplusplus
 }
 #endif

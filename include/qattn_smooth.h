@@ -50,6 +50,10 @@ int qattn_fp8_quant_attention_forward_smooth(const void* q, const void* k, const
                                              int numerics, int is_causal, float sm_scale, int precision, float* lse, int lse_layout,
                                              unsigned char* row_path, void* workspace, size_t workspace_bytes, void* stream, float* k_mean);
 
+/* The packed variable-length and block-sparse entries with key smoothing (qattn_fp8_quant_attention_varlen_forward_smooth,
+ * qattn_fp8_block_sparse_attention_forward_smooth) are declared beside their plain entries: include/qattn_varlen.h,
+ * include/qattn_block_sparse.h. */
+
 #ifdef __cplusplus
 }
 #endif

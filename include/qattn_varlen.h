@@ -45,6 +45,34 @@ int qattn_fp8_quant_attention_varlen_forward(const void* q, const void* k, const
                                              float sm_scale, void* q8, void* k8, float* scale_q, float* scale_k, void* workspace,
                                              size_t workspace_bytes, void* stream);
 
+
+/*
+ * Key smoothing (include/qattn_smooth.h: K is quantised as fp32(k) - its channel mean, `out` is mathematically unchanged, the LSE is
+ * corrected by sm_scale * q.m).  An ABI-8 addition, names found by symbol; the plain entry keeps its signature, launches and bits.
+ * q.m is the same for every key a row attends, whichever keys a block mask lists and whichever sequence a packed row belongs to.
+ *
+ * qattn_fp8_quant_attention_varlen_forward_smooth: the arguments of qattn_fp8_quant_attention_varlen_forward plus k_mean (out, fp32
+ * [B, Hkv, D], required, 16-byte aligned).  Per sequence i with L used keys (seqused_k honoured, extents clamped as in qattn_varlen.h),
+ * bit for bit: k_mean[i], scale_k[i] and the k8 bytes of its KFRAG image are what qattn_fp8_quant_attention_forward_smooth
+ * (QATTN_SCALE_HEAD, the same fp8_fmt and numerics) leaves for that sequence alone -- the mean in the summation order of a dense head of
+ * L rows, evaluated per sequence on the device; padding rows of the last chunk zero bytes.  A sequence with no used key gets k_mean = 0
+ * (not 0/0); keys beyond seqused_k influence no output bit, the mean included.  q8 / scale_q, the attention kernel and `out` per row are
+ * those of the plain entry on the smoothed operands; lse[h, t] (when non-NULL) = what the launch writes + sm_scale * sum_d
+ * fp32(q[t,h,d]) * k_mean[seq(t), kv(h), d], rows at -inf staying -inf.  total_q = 0: nothing is computed or written, k_mean included.
+ * Launches: zeroing node; K's mean (two), abs-max and quantise passes; q's abs-max and quantise passes; attention; the LSE correction
+ * when lse is asked for.  No length is read on the host, nothing is allocated, graph-capture safe (a captured call follows later contents
+ * of the tables).
+ *
+ * Workspace: at least ..._smooth_workspace_bytes(...), 16-byte aligned; errors as the plain entry, and
+ * QATTN_ERR_INVALID_ARG for a NULL or misaligned k_mean.
+ */
+size_t qattn_fp8_quant_attention_varlen_smooth_workspace_bytes(int B, int Hq, int Hkv, int total_q, int total_k, int D);
+int qattn_fp8_quant_attention_varlen_forward_smooth(const void* q, const void* k, const void* v, const long long* strides, int in_fmt, void* out,
+                                                    float* lse, const int* cu_seqlens_q, const int* cu_seqlens_k, const int* seqused_k, int B,
+                                                    int Hq, int Hkv, int total_q, int total_k, int D, int fp8_fmt, int numerics, int is_causal,
+                                                    float sm_scale, void* q8, void* k8, float* scale_q, float* scale_k, void* workspace,
+                                                    size_t workspace_bytes, void* stream, float* k_mean);
+
 #ifdef __cplusplus
 }
 #endif

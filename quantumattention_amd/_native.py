@@ -40,6 +40,8 @@ EXPORTS = (
     "qattn_varlen_tensor_bytes", "qattn_fp8_quant_attention_varlen_workspace_bytes", "qattn_fp8_quant_attention_varlen_forward",
     "qattn_fp8_block_sparse_attention_workspace_bytes", "qattn_fp8_block_sparse_attention_forward",
     "qattn_fp8_quant_attention_smooth_workspace_bytes", "qattn_fp8_quant_attention_forward_smooth",
+    "qattn_fp8_quant_attention_varlen_smooth_workspace_bytes", "qattn_fp8_quant_attention_varlen_forward_smooth",
+    "qattn_fp8_block_sparse_attention_smooth_workspace_bytes", "qattn_fp8_block_sparse_attention_forward_smooth",
 )
 BLOCK_SPARSE_BLOCK = 128   # QATTN_BLOCK_SPARSE_BLOCK (include/qattn_block_sparse.h): rows / keys per mask block
 
@@ -154,6 +156,15 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_quant_attention_smooth_workspace_bytes.argtypes = [i, i, i, i, i, i]
     L.qattn_fp8_quant_attention_forward_smooth.restype = i   # (..._forward_strided's arguments + float* k_mean: include/qattn_smooth.h)
     L.qattn_fp8_quant_attention_forward_smooth.argtypes = L.qattn_fp8_quant_attention_forward_strided.argtypes + [vp]
+    # the varlen and block-sparse entries with key smoothing: their plain entry's arguments + float* k_mean
+    L.qattn_fp8_quant_attention_varlen_smooth_workspace_bytes.restype = sz
+    L.qattn_fp8_quant_attention_varlen_smooth_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    L.qattn_fp8_quant_attention_varlen_forward_smooth.restype = i
+    L.qattn_fp8_quant_attention_varlen_forward_smooth.argtypes = L.qattn_fp8_quant_attention_varlen_forward.argtypes + [vp]
+    L.qattn_fp8_block_sparse_attention_smooth_workspace_bytes.restype = sz
+    L.qattn_fp8_block_sparse_attention_smooth_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    L.qattn_fp8_block_sparse_attention_forward_smooth.restype = i
+    L.qattn_fp8_block_sparse_attention_forward_smooth.argtypes = L.qattn_fp8_block_sparse_attention_forward.argtypes + [vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -610,12 +621,15 @@ def varlen_strided_ok(t: torch.Tensor) -> bool:
 
 def fp8_quant_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,
                                seqused_k: Optional[torch.Tensor] = None, *, is_causal: bool = False, fp8_dtype=torch.float8_e4m3fn,
-                               numerics: str = "compiled", sm_scale: float = 0.0, return_lse: bool = False, return_quant: bool = False):
+                               numerics: str = "compiled", sm_scale: float = 0.0, return_lse: bool = False, return_quant: bool = False,
+                               smooth_k: bool = False):
     """Packed variable-length sequences (qattn_fp8_quant_attention_varlen_forward): q [total_q, Hq, D], k / v [total_k, Hkv, D] bf16 / fp16,
     int32 cu_seqlens_* [B+1], optional int32 seqused_k [B] -> out [total_q, Hq, D] (and lse fp32 [Hq, total_q]).  The caller has validated
     the arguments (varlen.py); views that `varlen_strided_ok` accepts are read in place, others copied.  return_quant (test output): also
     (q8, k8, scale_q, scale_k) -- q8 the row-major per-sequence slabs (uint8, Hq D cu_q[i] bytes in), k8 the KFRAG images (Hkv D (cu_k[i] + 64 i)).
-    Returns out, or a tuple of out, [lse], [q8, k8, scale_q, scale_k]."""
+    smooth_k: key smoothing (qattn_fp8_quant_attention_varlen_forward_smooth, include/qattn_varlen.h): every sequence's K is quantised as
+    fp32(k) - the channel mean of its used keys; return_quant then also returns k_mean fp32 [B, Hkv, D].
+    Returns out, or a tuple of out, [lse], [q8, k8, scale_q, scale_k, [k_mean]]."""
     q, k, v = (t if varlen_strided_ok(t) else t.contiguous() for t in (q, k, v))
     total_q, Hq, D = q.shape
     total_k, Hkv = k.shape[0], k.shape[1]
@@ -635,24 +649,34 @@ def fp8_quant_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
             k8 = torch.empty((max(L.qattn_varlen_tensor_bytes(LAYOUT_KFRAG, B, Hkv, total_k, D), 1),), dtype=torch.uint8, device=dev)
             sq = torch.empty((B, Hq), dtype=torch.float32, device=dev)
             sk = torch.empty((B, Hkv), dtype=torch.float32, device=dev)
-        ws_bytes = L.qattn_fp8_quant_attention_varlen_workspace_bytes(B, Hq, Hkv, total_q, total_k, D)
+        ws_of = L.qattn_fp8_quant_attention_varlen_smooth_workspace_bytes if smooth_k else L.qattn_fp8_quant_attention_varlen_workspace_bytes
+        ws_bytes = ws_of(B, Hq, Hkv, total_q, total_k, D)
         ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
-        rc = L.qattn_fp8_quant_attention_varlen_forward(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), strides, fmt_of(q.dtype), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(),
-            cu_seqlens_k.data_ptr(), _ptr(seqused_k), B, Hq, Hkv, total_q, total_k, D, fmt_of(fp8_dtype), _numerics(numerics), int(is_causal),
-            float(sm_scale), _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_quant_attention_varlen_forward")
+        args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), strides, fmt_of(q.dtype), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(),
+                cu_seqlens_k.data_ptr(), _ptr(seqused_k), B, Hq, Hkv, total_q, total_k, D, fmt_of(fp8_dtype), _numerics(numerics), int(is_causal),
+                float(sm_scale), _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), ws.data_ptr(), ws_bytes, _stream(q))
+        k_mean = None
+        if smooth_k:
+            k_mean = torch.zeros((B, Hkv, D), dtype=torch.float32, device=dev) if total_q == 0 else torch.empty((B, Hkv, D), dtype=torch.float32, device=dev)
+            rc = L.qattn_fp8_quant_attention_varlen_forward_smooth(*args, k_mean.data_ptr())
+        else:
+            rc = L.qattn_fp8_quant_attention_varlen_forward(*args)
+    _check(rc, "qattn_fp8_quant_attention_varlen_forward_smooth" if smooth_k else "qattn_fp8_quant_attention_varlen_forward")
     if not (return_lse or return_quant):
         return out
-    return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) if return_quant else ())
+    return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) + ((k_mean,) if smooth_k else ()) if return_quant else ())
 
 
 def fp8_block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask: torch.Tensor, *, fp8_dtype=torch.float8_e4m3fn,
-                               numerics: str = "compiled", sm_scale: float = 0.0, return_lse: bool = False, return_quant: bool = False):
+                               numerics: str = "compiled", sm_scale: float = 0.0, return_lse: bool = False, return_quant: bool = False,
+                               smooth_k: bool = False):
     """Block-sparse attention (qattn_fp8_block_sparse_attention_forward): q [B,Hq,Sq,D], k / v [B,Hkv,Skv,D] bf16 / fp16; block_mask bool,
     broadcastable to [B, Hq, ceil(Sq/128), ceil(Skv/128)] and read through its strides (an expanded view costs no copy) -> out [B,Hq,Sq,D]
     (and lse fp32 [B,Hq,Sq]).  return_quant (test output): also (q8, k8, scale_q, scale_k), row-major fp8 and fp32 [B,H].
-    Returns out, or a tuple of out, [lse], [q8, k8, scale_q, scale_k]."""
+    smooth_k: key smoothing (qattn_fp8_block_sparse_attention_forward_smooth, include/qattn_block_sparse.h): K is quantised as fp32(k) - its channel
+    mean over the whole Skv; return_quant then returns k8 as the KFRAG image the kernel reads (flat uint8, the dense smoothing entry's k8)
+    and also k_mean fp32 [B, Hkv, D].
+    Returns out, or a tuple of out, [lse], [q8, k8, scale_q, scale_k, [k_mean]]."""
     B, Hq, Hkv, Sq, Skv, D = _check_qkv(q, k, v)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     nb = BLOCK_SPARSE_BLOCK
@@ -667,15 +691,24 @@ def fp8_block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
         q8 = k8 = sq = sk = None
         if return_quant:
             q8 = torch.empty((B, Hq, Sq, D), dtype=fp8_dtype, device=dev)
-            k8 = torch.empty((B, Hkv, Skv, D), dtype=fp8_dtype, device=dev)
+            if smooth_k:
+                k8 = torch.empty((L.qattn_fp8_tensor_bytes(LAYOUT_KFRAG, B, Hkv, Skv, D),), dtype=torch.uint8, device=dev)
+            else:
+                k8 = torch.empty((B, Hkv, Skv, D), dtype=fp8_dtype, device=dev)
             sq = torch.empty((B, Hq), dtype=torch.float32, device=dev)
             sk = torch.empty((B, Hkv), dtype=torch.float32, device=dev)
-        ws_bytes = L.qattn_fp8_block_sparse_attention_workspace_bytes(B, Hq, Hkv, Sq, Skv, D)
+        ws_of = L.qattn_fp8_block_sparse_attention_smooth_workspace_bytes if smooth_k else L.qattn_fp8_block_sparse_attention_workspace_bytes
+        ws_bytes = ws_of(B, Hq, Hkv, Sq, Skv, D)
         ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
-        rc = L.qattn_fp8_block_sparse_attention_forward(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), fmt_of(q.dtype), out.data_ptr(), _ptr(lse), m.data_ptr(), strides, B, Hq, Hkv, Sq, Skv, D,
-            fmt_of(fp8_dtype), _numerics(numerics), float(sm_scale), _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_block_sparse_attention_forward")
+        args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), fmt_of(q.dtype), out.data_ptr(), _ptr(lse), m.data_ptr(), strides, B, Hq, Hkv, Sq, Skv, D,
+                fmt_of(fp8_dtype), _numerics(numerics), float(sm_scale), _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk), ws.data_ptr(), ws_bytes, _stream(q))
+        k_mean = None
+        if smooth_k:
+            k_mean = torch.empty((B, Hkv, D), dtype=torch.float32, device=dev)
+            rc = L.qattn_fp8_block_sparse_attention_forward_smooth(*args, k_mean.data_ptr())
+        else:
+            rc = L.qattn_fp8_block_sparse_attention_forward(*args)
+    _check(rc, "qattn_fp8_block_sparse_attention_forward_smooth" if smooth_k else "qattn_fp8_block_sparse_attention_forward")
     if not (return_lse or return_quant):
         return out
-    return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) if return_quant else ())
+    return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) + ((k_mean,) if smooth_k else ()) if return_quant else ())

@@ -8,7 +8,8 @@ through its strides (a [1, 1, nQB, nKB] mask expanded over batch and heads is no
 Numerics (include/qattn_block_sparse.h): q and k are quantised head-wise over the WHOLE tensors -- the bytes and scales of
 `dynamically_quantize_fp8(x, reduction_dim=[2, 3])` under config.attention.fp8_format / quant_numerics, so keys of masked blocks still
 count toward k's scale -- and P.V runs on the reference kernel's own numerics, 16-bit P on the original 16-bit V (as
-`fp8_attn_varlen_func`; config.attention.precision and pv_precision do not apply).  Key blocks are visited in ascending order: rows
+`fp8_attn_varlen_func`; config.attention.precision and pv_precision do not apply; config.attention.smooth_k smooths K over the whole
+key sequence).  Key blocks are visited in ascending order: rows
 128 i .. 128 i + 127 equal, bit for bit, `fp8_attention_forward_rowmajor(q8, k8[J_i], v[J_i], ..., pv_16bit=True)` on the keys of the
 blocks J_i that query block i lists, gathered in ascending order.  A query block that lists no key block gives zero rows and an LSE of -inf.
 """
@@ -69,15 +70,21 @@ def block_sparse_input_reason(q, k, v, block_mask, scale=None) -> Optional[str]:
     return None
 
 
-def _block_sparse_eager(q, k, v, block_mask, scale, return_lse):
+def _block_sparse_eager(q, k, v, block_mask, scale, return_lse, smooth_k=False):
     """config.attention.force_eager_fallback: the torch definition -- the eager quantiser over the whole q and k (head-wise), de-quantise,
     expand the block mask to elements, fp32 attention with the masked scores at -inf; rows that see no key come out as zero (not NaN)
-    with an LSE of -inf."""
+    with an LSE of -inf.  smooth_k restated: the fp32 mean of k over the WHOLE key sequence (masked blocks included), one fp32
+    subtraction, the same eager quantiser on the result, and the LSE corrected by scale * q.m (the caller's 16-bit q)."""
     fp8_dtype = nn._fp8_dtype()
     B, Hq, Sq, D = q.shape
     Skv = k.shape[2]
     sm = 1.0 / math.sqrt(D) if scale is None else float(scale)
     q8, sq = nn._dynamically_quantize_fp8(q, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+    mean = None
+    if smooth_k:
+        k = k.to(torch.float32)
+        mean = k.mean(dim=-2, keepdim=True)   # [B, Hkv, 1, D]
+        k = k - mean
     k8, sk = nn._dynamically_quantize_fp8(k, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
     dq = q8.float() * sq[..., None, None]
     dk = nn._expand_kv_heads(k8.float() * sk[..., None, None], Hq)
@@ -89,6 +96,8 @@ def _block_sparse_eager(q, k, v, block_mask, scale, return_lse):
     lse = torch.logsumexp(s, dim=-1)
     p = torch.exp(s - lse.clamp_min(torch.finfo(torch.float32).min)[..., None])   # (a row without keys: exp(-inf) = 0)
     out = (p @ dv).to(q.dtype)
+    if smooth_k:   # (-inf rows stay -inf)
+        lse = lse + sm * (q.to(torch.float32) * nn._expand_kv_heads(mean, Hq)).sum(-1)
     return (out, lse) if return_lse else out
 
 
@@ -97,7 +106,12 @@ def fp8_block_sparse_attn_func(q, k, v, block_mask, *, scale=None, return_lse=Fa
     q [B, Hq, Sq, D], k / v [B, Hkv, Skv, D] bf16 / fp16 (one dtype), D in {64, 128, 256}, Hq a multiple of Hkv; block_mask bool on the same
     device, broadcastable to [B, Hq, ceil(Sq/128), ceil(Skv/128)].  scale: softmax scale (None: 1/sqrt(D)).
     Returns out [B, Hq, Sq, D] in the input dtype, or (out, lse) with return_lse (fp32 [B, Hq, Sq], natural log-sum-exp).  A query block
-    with no key block gives zero rows and an LSE of -inf.  Unsupported input raises ValueError(reason)."""
+    with no key block gives zero rows and an LSE of -inf.  Unsupported input raises ValueError(reason).
+    config.attention.smooth_k: key smoothing (include/qattn_smooth.h) -- K is quantised as fp32(k) - its channel mean over the whole key
+    sequence (keys of masked tiles count, as toward K's scale); `out` is mathematically unchanged, the LSE is that of the true scores.  Read
+    here and passed to the op as an argument, so a compiled graph bakes it in at trace time; `config.patch({"attention.smooth_k": ...})`
+    around a call overrides it for that call."""
+    smooth_k = bool(checks.config_value("attention.smooth_k"))
     if not checks.config_value("attention.skip_supported_check"):
         reason = block_sparse_input_reason(q, k, v, block_mask, scale)
         if reason is None:
@@ -106,10 +120,10 @@ def fp8_block_sparse_attn_func(q, k, v, block_mask, *, scale=None, return_lse=Fa
         if reason:
             raise ValueError(reason)
     if checks.config_value("attention.force_eager_fallback") and not torch.compiler.is_dynamo_compiling():
-        return _block_sparse_eager(q, k, v, block_mask, scale, return_lse)
+        return _block_sparse_eager(q, k, v, block_mask, scale, return_lse, smooth_k)
     B, Hq, Sq = q.shape[0], q.shape[1], q.shape[2]
     mask = block_mask.expand(B, Hq, _cdiv(Sq, BLOCK_M), _cdiv(k.shape[2], BLOCK_N))   # (a view: broadcast dimensions keep stride 0)
     out, lse = nn._ops().fp8_block_sparse_attention_forward(
-        q, k, v, mask, checks.config_value("attention.fp8_format"), checks.config_value("attention.quant_numerics"), bool(return_lse),
+        q, k, v, mask, checks.config_value("attention.fp8_format"), checks.config_value("attention.quant_numerics"), bool(return_lse), smooth_k,
         scale=scale)
     return (out, lse) if return_lse else out

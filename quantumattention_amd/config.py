@@ -35,7 +35,8 @@ class attention:
     # mean of K over the sequence, per (batch, kv head, channel), in fp32 before quantising it.  The softmax rows do not change
     # (q.(k_j - m) = q.k_j - q.m, the same shift for every key of a row), the fp8 error of K does: keys with a large per-channel offset
     # shared by all tokens (image / video DiTs) lose ~10x in output RMSE without it.  Costs one more read of K.  Off by default: every
-    # call then produces the bits it always did.  fp8_attn_varlen_func / fp8_block_sparse_attn_func and pre-quantised q / k ignore it.
+    # call then produces the bits it always did.  fp8_attn_varlen_func (mean per sequence over its used keys) and fp8_block_sparse_attn_func
+    # (mean over the whole key sequence) follow it too; pre-quantised q / k ignore it.
     # Passed to the fused op as an argument, like precision: a compiled graph bakes it in at trace time and does not follow a later change.
     smooth_k = os.getenv("QUANTUM_ATTN_SMOOTH_K") == "1"
 

@@ -111,10 +111,18 @@ extern "C" size_t qattn_fp8_block_sparse_attention_workspace_bytes(int B, int Hq
            up256(bs_list_bytes(B, Hq, Sq, Skv));
 }
 
-extern "C" int qattn_fp8_block_sparse_attention_forward(const void* q, const void* k, const void* v, int in_fmt, void* out, float* lse,
-                                                        const void* block_mask, const long long* mask_strides, int B, int Hq, int Hkv, int Sq,
-                                                        int Skv, int D, int fp8_fmt, int numerics, float sm_scale, void* q8, void* k8,
-                                                        float* scale_q, float* scale_k, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" size_t qattn_fp8_block_sparse_attention_smooth_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Skv, int D) {
+    const size_t plain = qattn_fp8_block_sparse_attention_workspace_bytes(B, Hq, Hkv, Sq, Skv, D);
+    // [the plain entry's workspace | per-block channel sums of the mean pass]
+    return plain ? up256(plain) + smooth_k_workspace_bytes(B, Hkv, D) : 0;
+}
+
+// k_mean != nullptr: key smoothing (include/qattn_smooth.h) -- K goes through launch_smooth_k instead of its share of the pre-pass, and k8
+// (when asked for) is the KFRAG image the attention kernel reads
+static int block_sparse_forward_impl(const void* q, const void* k, const void* v, int in_fmt, void* out, float* lse, const void* block_mask,
+                                     const long long* mask_strides, int B, int Hq, int Hkv, int Sq, int Skv, int D, int fp8_fmt, int numerics,
+                                     float sm_scale, void* q8, void* k8, float* scale_q, float* scale_k, void* workspace, size_t workspace_bytes,
+                                     void* stream, float* k_mean) {
     if (!q || !k || !v || !out || !block_mask) return QATTN_ERR_INVALID_ARG;
     if (!bs_dims_ok(B, Hq, Hkv, Sq, Skv)) return QATTN_ERR_INVALID_ARG;
     if ((D != 64 && D != 128 && D != 256) || Hq % Hkv != 0) return QATTN_ERR_UNSUPPORTED_DIM;
@@ -131,7 +139,11 @@ extern "C" int qattn_fp8_block_sparse_attention_forward(const void* q, const voi
     if (((size_t)q | (size_t)k | (size_t)v | (size_t)out) % 16 != 0) return QATTN_ERR_INVALID_ARG;
     if ((long long)B * Hq * nwg > 0x7fffffffLL) return QATTN_ERR_INVALID_ARG;   // (one workgroup per list row: a 32-bit grid)
     if (bs_lds_bytes(D, nkb) > kBsMaxLds) return QATTN_ERR_UNSUPPORTED_DIM;        // (the list lives behind the ring in LDS)
-    if (!workspace || workspace_bytes < qattn_fp8_block_sparse_attention_workspace_bytes(B, Hq, Hkv, Sq, Skv, D)) return QATTN_ERR_WORKSPACE;
+    const bool smooth = k_mean != nullptr;
+    if (smooth && (reinterpret_cast<uintptr_t>(k_mean) & 15u) != 0) return QATTN_ERR_INVALID_ARG;
+    const size_t plain_bytes = qattn_fp8_block_sparse_attention_workspace_bytes(B, Hq, Hkv, Sq, Skv, D);
+    if (!workspace || workspace_bytes < (smooth ? qattn_fp8_block_sparse_attention_smooth_workspace_bytes(B, Hq, Hkv, Sq, Skv, D) : plain_bytes))
+        return QATTN_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     unsigned char* w = (unsigned char*)workspace;
     unsigned char* q8w = w;   w += up256(qattn_fp8_tensor_bytes(QATTN_LAYOUT_ROWMAJOR, B, Hq, Sq, D));
@@ -146,9 +158,15 @@ extern "C" int qattn_fp8_block_sparse_attention_forward(const void* q, const voi
     float* sk = scale_k ? scale_k : skw;
     int rc = qattn_quant_fp8(q, in_fmt, q8p, sq, B, Hq, Sq, D, fp8_fmt, QATTN_SCALE_HEAD, numerics, QATTN_LAYOUT_ROWMAJOR, qws, qws_bytes, stream);
     if (rc != QATTN_OK) return rc;
-    rc = qattn_quant_fp8(k, in_fmt, kfrag, sk, B, Hkv, Skv, D, fp8_fmt, QATTN_SCALE_HEAD, numerics, QATTN_LAYOUT_KFRAG, qws, qws_bytes, stream);
+    if (smooth) {   // mean over the whole Skv, then K's abs-max words (where the pre-pass would leave them) and quantise pass on k - mean
+        if (k8) kfrag = (unsigned char*)k8;
+        rc = launch_smooth_k(k, in_fmt, kfrag, sk, k_mean, B, Hkv, Skv, D, fp8_fmt, QATTN_SCALE_HEAD, numerics, (unsigned*)qws, nullptr,
+                             amax_splits(Skv, Skv, D), reinterpret_cast<float*>((unsigned char*)workspace + up256(plain_bytes)), st, nullptr);
+    } else {
+        rc = qattn_quant_fp8(k, in_fmt, kfrag, sk, B, Hkv, Skv, D, fp8_fmt, QATTN_SCALE_HEAD, numerics, QATTN_LAYOUT_KFRAG, qws, qws_bytes, stream);
+    }
     if (rc != QATTN_OK) return rc;
-    if (k8) {   // (the row-major k8 on request: the same bytes, in the other order)
+    if (k8 && !smooth) {   // (the row-major k8 on request: the same bytes, in the other order)
         rc = qattn_quant_fp8(k, in_fmt, k8, sk, B, Hkv, Skv, D, fp8_fmt, QATTN_SCALE_HEAD, numerics, QATTN_LAYOUT_ROWMAJOR, qws, qws_bytes, stream);
         if (rc != QATTN_OK) return rc;
     }
@@ -179,5 +197,27 @@ extern "C" int qattn_fp8_block_sparse_attention_forward(const void* q, const voi
     else if (D == 128) rc = launch_bs_d<128>(p, lists, list_stride, nkb, fp8_fmt, in_fmt, st);
     else rc = launch_bs_d<256>(p, lists, list_stride, nkb, fp8_fmt, in_fmt, st);
     if (rc != QATTN_OK) return rc;
-    return hipGetLastError() == hipSuccess ? QATTN_OK : QATTN_ERR_LAUNCH;
+    if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
+    if (!smooth || !lse) return QATTN_OK;
+    // the launch wrote the LSE of the smoothed scores; the true scores of row i lie sm_scale * q_i.m higher (-inf rows stay -inf)
+    return launch_smooth_lse(q, in_fmt, k_mean, lse, (long)Sq, B, Hq, Hkv, Sq, D, sm, st, nullptr);
+}
+
+extern "C" int qattn_fp8_block_sparse_attention_forward(const void* q, const void* k, const void* v, int in_fmt, void* out, float* lse,
+                                                        const void* block_mask, const long long* mask_strides, int B, int Hq, int Hkv, int Sq,
+                                                        int Skv, int D, int fp8_fmt, int numerics, float sm_scale, void* q8, void* k8,
+                                                        float* scale_q, float* scale_k, void* workspace, size_t workspace_bytes, void* stream) {
+    return block_sparse_forward_impl(q, k, v, in_fmt, out, lse, block_mask, mask_strides, B, Hq, Hkv, Sq, Skv, D, fp8_fmt, numerics, sm_scale, q8, k8,
+                                     scale_q, scale_k, workspace, workspace_bytes, stream, nullptr);
+}
+
+// The block-sparse entry with key smoothing (include/qattn_block_sparse.h; the idea: include/qattn_smooth.h): K is quantised as fp32(k) - its channel mean over the WHOLE Skv.
+extern "C" int qattn_fp8_block_sparse_attention_forward_smooth(const void* q, const void* k, const void* v, int in_fmt, void* out, float* lse,
+                                                               const void* block_mask, const long long* mask_strides, int B, int Hq, int Hkv,
+                                                               int Sq, int Skv, int D, int fp8_fmt, int numerics, float sm_scale, void* q8, void* k8,
+                                                               float* scale_q, float* scale_k, void* workspace, size_t workspace_bytes, void* stream,
+                                                               float* k_mean) {
+    if (!k_mean) return QATTN_ERR_INVALID_ARG;
+    return block_sparse_forward_impl(q, k, v, in_fmt, out, lse, block_mask, mask_strides, B, Hq, Hkv, Sq, Skv, D, fp8_fmt, numerics, sm_scale, q8, k8,
+                                     scale_q, scale_k, workspace, workspace_bytes, stream, k_mean);
 }

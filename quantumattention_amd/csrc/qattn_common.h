@@ -327,7 +327,7 @@ struct QuantMoments { const float* part_q; const float* part_k; const unsigned* 
 #endif
 constexpr int kAmaxInFlight = QATTN_AMAX_INFLIGHT;   // 16-byte loads a thread of the abs-max pass keeps in flight (tuning knobs:
 constexpr int kAmaxRounds = QATTN_AMAX_ROUNDS;       //   tools/bin variants) and bursts of them per block
-inline int amax_splits(int Sq, int Skv, int D) {
+__host__ __device__ inline int amax_splits(int Sq, int Skv, int D) {   // (on the device: qattn_smooth_dev.h mean_splits, per packed sequence)
     const long vecs = (long)(Sq > Skv ? Sq : Skv) * D / 8;
     const long per = 256L * kAmaxInFlight * kAmaxRounds;
     const long s = (vecs + per - 1) / per;   // kAmaxInFlight x 16 B per thread and burst
@@ -360,5 +360,13 @@ int launch_smooth_k(const void* k, int in_fmt, void* k8, float* scale_k, float* 
                     const long long* kstrides);
 int launch_smooth_lse(const void* q, int in_fmt, const float* k_mean, float* lse, long lse_stride, int B, int Hq, int Hkv, int Sq, int D,
                       float mul, hipStream_t st, const long long* qstrides);
+// The same for packed variable-length sequences (qattn_varlen_smooth.hip): per-sequence mean over the used keys -> k_mean [B][Hkv][D],
+// max |ks| into the zeroed words amax_k [B][Hkv], scale_k [B][Hkv] and the KFRAG images k8; ts / hs: element strides of token and head.
+// mean_part: varlen_smooth_k_workspace_bytes() of scratch.  launch_varlen_smooth_lse: lse[h,t] += mul * q[t,h,:].k_mean[seq(t), kv head,:].
+size_t varlen_smooth_k_workspace_bytes(int B, int Hkv, int D);
+int launch_varlen_smooth_k(const void* k, long ts, long hs, int in_fmt, const int* cu_k, const int* used, int B, int Hkv, int total_k, int D,
+                           int out_fmt, int numerics, void* k8, float* scale_k, float* k_mean, unsigned* amax_k, float* mean_part, hipStream_t st);
+int launch_varlen_smooth_lse(const void* q, long ts, long hs, int in_fmt, const int* cu_q, const float* k_mean, float* lse, int B, int Hq, int Hkv,
+                             int total_q, int D, float mul, hipStream_t st);
 
 }  // namespace qattn

@@ -15,39 +15,12 @@
 // table) as its tile j - f(i) -- or to no tile, and exits.  B + ceil(total / R) workgroups per head cover every tile and waste at most B.
 // Built with strided addressing (QATTN_STRIDED16 = 1: V and `out` through byte strides).
 #include "qattn_pv16.h"
+#include "qattn_varlen_tile.h"
 #include "../../include/qattn_varlen.h"
 
 namespace qattn {
 
 static_assert(kStrided16, "the varlen unit addresses V and the output through strides");
-
-constexpr int kVarlenAmaxRows = 256;   // rows per tile of the abs-max pass
-constexpr int kVarlenQuantRows = 64;   // rows per tile of the quantise pass (= one KFRAG chunk)
-
-__device__ __forceinline__ int clampi(int x, int lo, int hi) { return x < lo ? lo : x > hi ? hi : x; }
-
-// one tile of a packed tensor: sequence i, its clamped first token and length, and the tile index within it (valid: 0 <= tile, tile R < len)
-struct VarlenTile {
-    int i, start, len, tile;
-};
-template <int R>
-__device__ __forceinline__ VarlenTile varlen_tile(const int* cu, const int* used, int B, int total, int j) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {   // (workgroup-uniform) the largest i with i + floor(start_i / R) <= j
-        const int mid = (lo + hi + 1) >> 1;
-        const int s = clampi(__builtin_amdgcn_readfirstlane(cu[mid]), 0, total);
-        if (mid + s / R <= j) lo = mid;
-        else hi = mid - 1;
-    }
-    VarlenTile t;
-    t.i = lo;
-    t.start = clampi(__builtin_amdgcn_readfirstlane(cu[lo]), 0, total);
-    const int end = clampi(__builtin_amdgcn_readfirstlane(cu[lo + 1]), t.start, total);
-    t.len = end - t.start;
-    if (used) t.len = clampi(__builtin_amdgcn_readfirstlane(used[lo]), 0, t.len);
-    t.tile = j - (lo + t.start / R);
-    return t;
-}
 
 // q (z = 0) and k (z = 1) of one call
 struct VarlenQuant {
@@ -235,22 +208,25 @@ template <int D, int QK_FMT, int V16_FMT>
 static int launch_varlen_attn_c(const VarlenAttn& a, int causal, hipStream_t st) {
     return causal ? launch_varlen_attn<D, QK_FMT, V16_FMT, true>(a, st) : launch_varlen_attn<D, QK_FMT, V16_FMT, false>(a, st);
 }
+// skip_k (key smoothing): K takes no part in the abs-max and quantise launches -- their grids shrink to q's slice (z = 0) -- and is
+// quantised by the launches of qattn_varlen_smooth.hip instead, as launch_quant_qkv's skip_k
 template <int D, int IN_FMT, int OUT_FMT>
-static int launch_varlen_d(const VarlenQuant& qa, const VarlenAttn& a, int numerics, int causal, hipStream_t st) {
-    const int tmax = qa.total[0] > qa.total[1] ? qa.total[0] : qa.total[1];
-    const int hmax = qa.H[0] > qa.H[1] ? qa.H[0] : qa.H[1];
-    hipLaunchKernelGGL((varlen_amax_kernel<D, IN_FMT>), dim3((unsigned)(qa.B + ceil_div(tmax, kVarlenAmaxRows)), hmax, 2), dim3(256), 0, st, qa);
-    hipLaunchKernelGGL((varlen_quant_kernel<D, IN_FMT, OUT_FMT>), dim3((unsigned)(qa.B + ceil_div(tmax, kVarlenQuantRows)), hmax, 2), dim3(256), 0, st,
+static int launch_varlen_d(const VarlenQuant& qa, const VarlenAttn& a, int numerics, int causal, hipStream_t st, bool skip_k) {
+    const int tmax = skip_k || qa.total[0] > qa.total[1] ? qa.total[0] : qa.total[1];
+    const int hmax = skip_k || qa.H[0] > qa.H[1] ? qa.H[0] : qa.H[1];
+    const unsigned nz = skip_k ? 1 : 2;
+    hipLaunchKernelGGL((varlen_amax_kernel<D, IN_FMT>), dim3((unsigned)(qa.B + ceil_div(tmax, kVarlenAmaxRows)), hmax, nz), dim3(256), 0, st, qa);
+    hipLaunchKernelGGL((varlen_quant_kernel<D, IN_FMT, OUT_FMT>), dim3((unsigned)(qa.B + ceil_div(tmax, kVarlenQuantRows)), hmax, nz), dim3(256), 0, st,
                        qa, numerics);
     return launch_varlen_attn_c<D, OUT_FMT, IN_FMT>(a, causal, st);
 }
 template <int D>
-static int launch_varlen(const VarlenQuant& qa, const VarlenAttn& a, int in_fmt, int fp8_fmt, int numerics, int causal, hipStream_t st) {
+static int launch_varlen(const VarlenQuant& qa, const VarlenAttn& a, int in_fmt, int fp8_fmt, int numerics, int causal, hipStream_t st, bool skip_k) {
     if (in_fmt == QATTN_FMT_BF16)
-        return fp8_fmt == QATTN_FMT_E4M3 ? launch_varlen_d<D, QATTN_FMT_BF16, QATTN_FMT_E4M3>(qa, a, numerics, causal, st)
-                                         : launch_varlen_d<D, QATTN_FMT_BF16, QATTN_FMT_E5M2>(qa, a, numerics, causal, st);
-    return fp8_fmt == QATTN_FMT_E4M3 ? launch_varlen_d<D, QATTN_FMT_FP16, QATTN_FMT_E4M3>(qa, a, numerics, causal, st)
-                                     : launch_varlen_d<D, QATTN_FMT_FP16, QATTN_FMT_E5M2>(qa, a, numerics, causal, st);
+        return fp8_fmt == QATTN_FMT_E4M3 ? launch_varlen_d<D, QATTN_FMT_BF16, QATTN_FMT_E4M3>(qa, a, numerics, causal, st, skip_k)
+                                         : launch_varlen_d<D, QATTN_FMT_BF16, QATTN_FMT_E5M2>(qa, a, numerics, causal, st, skip_k);
+    return fp8_fmt == QATTN_FMT_E4M3 ? launch_varlen_d<D, QATTN_FMT_FP16, QATTN_FMT_E4M3>(qa, a, numerics, causal, st, skip_k)
+                                     : launch_varlen_d<D, QATTN_FMT_FP16, QATTN_FMT_E5M2>(qa, a, numerics, causal, st, skip_k);
 }
 
 }  // namespace qattn
@@ -276,11 +252,17 @@ extern "C" size_t qattn_fp8_quant_attention_varlen_workspace_bytes(int B, int Hq
            2 * up256(sizeof(float) * (size_t)B * (Hq + Hkv));
 }
 
-extern "C" int qattn_fp8_quant_attention_varlen_forward(const void* q, const void* k, const void* v, const long long* strides, int in_fmt, void* out,
-                                                        float* lse, const int* cu_seqlens_q, const int* cu_seqlens_k, const int* seqused_k, int B,
-                                                        int Hq, int Hkv, int total_q, int total_k, int D, int fp8_fmt, int numerics, int is_causal,
-                                                        float sm_scale, void* q8, void* k8, float* scale_q, float* scale_k, void* workspace,
-                                                        size_t workspace_bytes, void* stream) {
+extern "C" size_t qattn_fp8_quant_attention_varlen_smooth_workspace_bytes(int B, int Hq, int Hkv, int total_q, int total_k, int D) {
+    const size_t plain = qattn_fp8_quant_attention_varlen_workspace_bytes(B, Hq, Hkv, total_q, total_k, D);
+    // [the plain entry's workspace | per-block channel sums of the mean pass]
+    return plain ? up256(plain) + varlen_smooth_k_workspace_bytes(B, Hkv, D) : 0;
+}
+
+// k_mean != nullptr: key smoothing (include/qattn_smooth.h)
+static int varlen_forward_impl(const void* q, const void* k, const void* v, const long long* strides, int in_fmt, void* out, float* lse,
+                               const int* cu_seqlens_q, const int* cu_seqlens_k, const int* seqused_k, int B, int Hq, int Hkv, int total_q,
+                               int total_k, int D, int fp8_fmt, int numerics, int is_causal, float sm_scale, void* q8, void* k8, float* scale_q,
+                               float* scale_k, void* workspace, size_t workspace_bytes, void* stream, float* k_mean) {
     if (!q || !k || !v || !out || !cu_seqlens_q || !cu_seqlens_k) return QATTN_ERR_INVALID_ARG;
     if (!varlen_dims_ok(B, Hq, Hkv, total_q, total_k)) return QATTN_ERR_INVALID_ARG;
     if ((D != 64 && D != 128 && D != 256) || Hq % Hkv != 0) return QATTN_ERR_UNSUPPORTED_DIM;
@@ -297,7 +279,10 @@ extern "C" int qattn_fp8_quant_attention_varlen_forward(const void* q, const voi
     // grids: Hq (B + ceil(total_q / 256)) attention workgroups, B + ceil(total / 64) quantise tiles per head (32-bit dimensions)
     if ((long long)Hq * (B + ceil_div(total_q, kQPerWG)) > 0x7fffffffLL || (long long)B + ceil_div(total_q > total_k ? total_q : total_k, 64) > 0x7fffffffLL)
         return QATTN_ERR_INVALID_ARG;
-    const size_t need = qattn_fp8_quant_attention_varlen_workspace_bytes(B, Hq, Hkv, total_q, total_k, D);
+    const bool smooth = k_mean != nullptr;
+    if (smooth && (reinterpret_cast<uintptr_t>(k_mean) & 15u) != 0) return QATTN_ERR_INVALID_ARG;
+    const size_t plain_bytes = qattn_fp8_quant_attention_varlen_workspace_bytes(B, Hq, Hkv, total_q, total_k, D);
+    const size_t need = smooth ? qattn_fp8_quant_attention_varlen_smooth_workspace_bytes(B, Hq, Hkv, total_q, total_k, D) : plain_bytes;
     if (!workspace || workspace_bytes < need) return QATTN_ERR_WORKSPACE;
     if (total_q == 0) return QATTN_OK;   // no query row: nothing to compute or write
     hipStream_t st = (hipStream_t)stream;
@@ -327,9 +312,38 @@ extern "C" int qattn_fp8_quant_attention_varlen_forward(const void* q, const voi
     a.sm_log2e = sm * 1.4426950408889634f;
     if (zero_words(amax, (long)B * (Hq + Hkv), st) != hipSuccess) return QATTN_ERR_LAUNCH;
     int rc;
-    if (D == 64) rc = launch_varlen<64>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st);
-    else if (D == 128) rc = launch_varlen<128>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st);
-    else rc = launch_varlen<256>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st);
+    if (smooth) {   // K first, in launches of its own (mean, abs-max, quantise on k - mean), then q through the plain two
+        rc = launch_varlen_smooth_k(k, (long)st6[2], (long)st6[3], in_fmt, cu_seqlens_k, seqused_k, B, Hkv, total_k, D, fp8_fmt, numerics, qa.x8[1],
+                                    qa.scale[1], k_mean, qa.amax[1], reinterpret_cast<float*>((unsigned char*)workspace + up256(plain_bytes)), st);
+        if (rc != QATTN_OK) return rc;
+    }
+    if (D == 64) rc = launch_varlen<64>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st, smooth);
+    else if (D == 128) rc = launch_varlen<128>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st, smooth);
+    else rc = launch_varlen<256>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st, smooth);
     if (rc != QATTN_OK) return rc;
-    return hipGetLastError() == hipSuccess ? QATTN_OK : QATTN_ERR_LAUNCH;
+    if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
+    if (!smooth || !lse) return QATTN_OK;
+    // the launch wrote the LSE of the smoothed scores; the true scores of a row lie sm_scale * q.m higher
+    return launch_varlen_smooth_lse(q, (long)st6[0], (long)st6[1], in_fmt, cu_seqlens_q, k_mean, lse, B, Hq, Hkv, total_q, D, sm, st);
+}
+
+extern "C" int qattn_fp8_quant_attention_varlen_forward(const void* q, const void* k, const void* v, const long long* strides, int in_fmt, void* out,
+                                                        float* lse, const int* cu_seqlens_q, const int* cu_seqlens_k, const int* seqused_k, int B,
+                                                        int Hq, int Hkv, int total_q, int total_k, int D, int fp8_fmt, int numerics, int is_causal,
+                                                        float sm_scale, void* q8, void* k8, float* scale_q, float* scale_k, void* workspace,
+                                                        size_t workspace_bytes, void* stream) {
+    return varlen_forward_impl(q, k, v, strides, in_fmt, out, lse, cu_seqlens_q, cu_seqlens_k, seqused_k, B, Hq, Hkv, total_q, total_k, D, fp8_fmt,
+                               numerics, is_causal, sm_scale, q8, k8, scale_q, scale_k, workspace, workspace_bytes, stream, nullptr);
+}
+
+// The varlen entry with key smoothing (include/qattn_varlen.h; the idea: include/qattn_smooth.h): every sequence's K is quantised as fp32(k) - the channel mean of its used keys.
+extern "C" int qattn_fp8_quant_attention_varlen_forward_smooth(const void* q, const void* k, const void* v, const long long* strides, int in_fmt,
+                                                               void* out, float* lse, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                                                               const int* seqused_k, int B, int Hq, int Hkv, int total_q, int total_k, int D,
+                                                               int fp8_fmt, int numerics, int is_causal, float sm_scale, void* q8, void* k8,
+                                                               float* scale_q, float* scale_k, void* workspace, size_t workspace_bytes, void* stream,
+                                                               float* k_mean) {
+    if (!k_mean) return QATTN_ERR_INVALID_ARG;
+    return varlen_forward_impl(q, k, v, strides, in_fmt, out, lse, cu_seqlens_q, cu_seqlens_k, seqused_k, B, Hq, Hkv, total_q, total_k, D, fp8_fmt,
+                               numerics, is_causal, sm_scale, q8, k8, scale_q, scale_k, workspace, workspace_bytes, stream, k_mean);
 }

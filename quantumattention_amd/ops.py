@@ -183,18 +183,20 @@ def fp8_varlen_attention_forward(
     fp8_format: str = "e4m3",
     numerics: str = "compiled",
     return_lse: bool = False,
+    smooth_k: bool = False,
     *,
     scale: Optional[float] = None,
 ) -> tuple[torch.Tensor, torch.Tensor]:
     """Packed variable-length sequences (include/qattn_varlen.h): query [total_q, Hq, D], key / value [total_k, Hkv, D] bf16 / fp16, int32
     cu_seqlens_* [B+1], optional int32 seqused_k [B]; per-(sequence, head) fp8 scales, 16-bit P on the 16-bit value.  Returns (out
     [total_q, Hq, D], lse fp32 [Hq, total_q] -- or an empty [0] tensor without return_lse).  max_seqlen_*: signature compatibility only
-    (the kernels read every length on the device).  Arguments are validated by varlen.fp8_attn_varlen_func."""
+    (the kernels read every length on the device).  smooth_k: key smoothing per sequence over its used keys (include/qattn_smooth.h;
+    config.attention.smooth_k).  Arguments are validated by varlen.fp8_attn_varlen_func."""
     del max_seqlen_q, max_seqlen_k
     res = _native.fp8_quant_attention_varlen(
         query, key, value, cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous(), None if seqused_k is None else seqused_k.contiguous(),
         is_causal=is_causal, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics, sm_scale=0.0 if scale is None else float(scale),
-        return_lse=return_lse)
+        return_lse=return_lse, smooth_k=smooth_k)
     if return_lse:
         return res
     return res, torch.empty((0,), dtype=torch.float32, device=query.device)
@@ -202,7 +204,7 @@ def fp8_varlen_attention_forward(
 
 @_register_fake("quantumattention_amd::fp8_varlen_attention_forward")
 def _(query, key, value, cu_seqlens_q, cu_seqlens_k, seqused_k=None, max_seqlen_q=0, max_seqlen_k=0, is_causal=False, fp8_format="e4m3",
-      numerics="compiled", return_lse=False, *, scale=None):
+      numerics="compiled", return_lse=False, smooth_k=False, *, scale=None):
     out = query.new_empty((query.shape[0], query.shape[1], value.shape[2]), dtype=value.dtype)
     lse = query.new_empty((query.shape[1], query.shape[0]) if return_lse else (0,), dtype=torch.float32)
     return out, lse
@@ -217,22 +219,24 @@ def fp8_block_sparse_attention_forward(
     fp8_format: str = "e4m3",
     numerics: str = "compiled",
     return_lse: bool = False,
+    smooth_k: bool = False,
     *,
     scale: Optional[float] = None,
 ) -> tuple[torch.Tensor, torch.Tensor]:
     """Block-sparse attention (include/qattn_block_sparse.h): query [B, Hq, Sq, D], key / value [B, Hkv, Skv, D] bf16 / fp16, block_mask
     bool [B, Hq, ceil(Sq/128), ceil(Skv/128)] (an expanded view is read through its strides); head-wise fp8 scales over the whole tensors,
     16-bit P on the 16-bit value.  Returns (out [B, Hq, Sq, D], lse fp32 [B, Hq, Sq] -- or an empty [0] tensor without return_lse).
+    smooth_k: key smoothing over the whole key sequence (include/qattn_smooth.h; config.attention.smooth_k).
     Arguments are validated by block_sparse.fp8_block_sparse_attn_func."""
     res = _native.fp8_block_sparse_attention(query, key, value, block_mask, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics,
-                                             sm_scale=0.0 if scale is None else float(scale), return_lse=return_lse)
+                                             sm_scale=0.0 if scale is None else float(scale), return_lse=return_lse, smooth_k=smooth_k)
     if return_lse:
         return res
     return res, torch.empty((0,), dtype=torch.float32, device=query.device)
 
 
 @_register_fake("quantumattention_amd::fp8_block_sparse_attention_forward")
-def _(query, key, value, block_mask, fp8_format="e4m3", numerics="compiled", return_lse=False, *, scale=None):
+def _(query, key, value, block_mask, fp8_format="e4m3", numerics="compiled", return_lse=False, smooth_k=False, *, scale=None):
     B, Hq, Sq = query.shape[0], query.shape[1], query.shape[2]
     out = query.new_empty((B, Hq, Sq, value.shape[3]), dtype=value.dtype)
     lse = query.new_empty((B, Hq, Sq) if return_lse else (0,), dtype=torch.float32)

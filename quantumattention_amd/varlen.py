@@ -8,7 +8,7 @@ without a copy (Wan-style cross-attention).
 Numerics (include/qattn_varlen.h): q and k are quantised head-wise PER (sequence, head) -- exactly `dynamically_quantize_fp8` of each
 sequence on its own, under config.attention.fp8_format / quant_numerics, over the used keys only -- and P.V runs on the reference
 kernel's own numerics, 16-bit P on the original 16-bit value (every row is QATTN_PATH_V16).  config.attention.precision and
-pv_precision do not apply.  Row r of sequence i equals, bit for bit, `fp8_attention_forward_rowmajor(..., pv_16bit=True)` on that
+pv_precision do not apply; config.attention.smooth_k does: key smoothing per sequence over its used keys.  Row r of sequence i equals, bit for bit, `fp8_attention_forward_rowmajor(..., pv_16bit=True)` on that
 sequence alone.  `causal` masks top-left per sequence (key j <= query r), as the dense entry and torch SDPA's is_causal; flash-attn >= 2.1
 aligns the diagonal bottom-right when L_q != L_k -- the two agree for self-attention (cu_seqlens_q == cu_seqlens_k).
 """
@@ -75,9 +75,11 @@ def varlen_input_reason(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_s
     return None
 
 
-def _varlen_eager(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, causal, return_lse):
+def _varlen_eager(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, causal, return_lse, smooth_k=False):
     """config.attention.force_eager_fallback: the per-sequence loop of the eager fp8 definition (eager quantiser per sequence and head,
-    de-quantise, aten SDPA: nn._fp8_attention_eager), with the log-sum-exp of the same de-quantised scores."""
+    de-quantise, aten SDPA: nn._fp8_attention_eager), with the log-sum-exp of the same de-quantised scores.
+    smooth_k restated: the fp32 mean over the sequence's USED keys, one fp32 subtraction, the same eager quantiser on the result, and the
+    LSE corrected by scale * q.m (the caller's 16-bit q)."""
     fp8_dtype = nn._fp8_dtype()
     total_q, Hq, D = q.shape
     scale = 1.0 / math.sqrt(D) if softmax_scale is None else float(softmax_scale)
@@ -93,6 +95,11 @@ def _varlen_eager(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale,
         qi = q[cq[i]:cq[i + 1]].transpose(0, 1)[None]
         ki, vi = (t[ck[i]:ck[i] + lk].transpose(0, 1)[None] for t in (k, v))
         q8, sq = nn._dynamically_quantize_fp8(qi, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+        mean = None
+        if smooth_k:
+            ki = ki.to(torch.float32)
+            mean = ki.mean(dim=-2, keepdim=True)   # [1, Hkv, 1, D]
+            ki = ki - mean
         k8, sk = nn._dynamically_quantize_fp8(ki, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
         o = nn._eager_fp8_attention(q8, k8, vi, sq, sk, causal, softmax_scale)
         out[cq[i]:cq[i + 1]] = o[0].transpose(0, 1)
@@ -102,7 +109,10 @@ def _varlen_eager(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale,
             s = (dq @ dk.transpose(-1, -2)) * scale
             if causal:
                 s = s.masked_fill(torch.ones(lq, lk, dtype=torch.bool, device=q.device).triu(1), -math.inf)
-            lse[:, cq[i]:cq[i + 1]] = torch.logsumexp(s[0], dim=-1)
+            l = torch.logsumexp(s[0], dim=-1)
+            if smooth_k:
+                l = l + scale * (qi[0].to(torch.float32) * nn._expand_kv_heads(mean, Hq)[0]).sum(-1)
+            lse[:, cq[i]:cq[i + 1]] = l
     return (out, lse) if return_lse else out
 
 
@@ -113,7 +123,11 @@ def fp8_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
     head_dim innermost are read in place.  cu_seqlens_q / cu_seqlens_k: int32 [B+1] on the device; max_seqlen_*: host ints, accepted for
     signature compatibility.  seqused_k: optional int32 [B], keys used per sequence (keys beyond it influence no output bit).
     Returns out [total_q, Hq, D] in the input dtype, or (out, lse) with return_lse (fp32 [Hq, total_q], natural log-sum-exp).  A sequence
-    with no query has no rows; one with queries and no key gives zero rows and an LSE of -inf.  Unsupported input raises ValueError(reason)."""
+    with no query has no rows; one with queries and no key gives zero rows and an LSE of -inf.  Unsupported input raises ValueError(reason).
+    config.attention.smooth_k: key smoothing (include/qattn_smooth.h) -- every sequence's K is quantised as fp32(k) - the channel mean of
+    its used keys; `out` is mathematically unchanged, the LSE is that of the true scores.  Read here and passed to the op as an argument,
+    so a compiled graph bakes it in at trace time; `config.patch({"attention.smooth_k": ...})` around a call overrides it for that call."""
+    smooth_k = bool(checks.config_value("attention.smooth_k"))
     if not checks.config_value("attention.skip_supported_check"):
         reason = varlen_input_reason(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, seqused_k)
         if reason is None:
@@ -122,8 +136,9 @@ def fp8_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
         if reason:
             raise ValueError(reason)
     if checks.config_value("attention.force_eager_fallback") and not torch.compiler.is_dynamo_compiling():
-        return _varlen_eager(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, causal, return_lse)
+        return _varlen_eager(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, causal, return_lse, smooth_k)
     out, lse = nn._ops().fp8_varlen_attention_forward(
         q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal),
-        checks.config_value("attention.fp8_format"), checks.config_value("attention.quant_numerics"), bool(return_lse), scale=softmax_scale)
+        checks.config_value("attention.fp8_format"), checks.config_value("attention.quant_numerics"), bool(return_lse), smooth_k,
+        scale=softmax_scale)
     return (out, lse) if return_lse else out
