@@ -20,6 +20,9 @@ from .quantum_attn_interface import (
 # packed variable-length sequences (flash-attn's varlen call shape): a package attribute beyond the reference's seven exported names
 from .varlen import fp8_attn_varlen_func  # noqa: E402
 
+# sliding-window (local) attention, packed and dense call shapes: package attributes too, not in __all__
+from .varlen import fp8_attn_varlen_window_func, fp8_window_attn_func  # noqa: E402
+
 # block-sparse attention over 128 x 128 tiles of a boolean block mask: package attributes too, not in __all__
 from .block_sparse import BLOCK_M, BLOCK_N, fp8_block_sparse_attn_func  # noqa: E402
 

@@ -42,6 +42,7 @@ EXPORTS = (
     "qattn_fp8_quant_attention_smooth_workspace_bytes", "qattn_fp8_quant_attention_forward_smooth",
     "qattn_fp8_quant_attention_varlen_smooth_workspace_bytes", "qattn_fp8_quant_attention_varlen_forward_smooth",
     "qattn_fp8_block_sparse_attention_smooth_workspace_bytes", "qattn_fp8_block_sparse_attention_forward_smooth",
+    "qattn_fp8_quant_attention_varlen_window_workspace_bytes", "qattn_fp8_quant_attention_varlen_window_forward",
 )
 BLOCK_SPARSE_BLOCK = 128   # QATTN_BLOCK_SPARSE_BLOCK (include/qattn_block_sparse.h): rows / keys per mask block
 
@@ -165,6 +166,12 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_block_sparse_attention_smooth_workspace_bytes.argtypes = [i, i, i, i, i, i]
     L.qattn_fp8_block_sparse_attention_forward_smooth.restype = i
     L.qattn_fp8_block_sparse_attention_forward_smooth.argtypes = L.qattn_fp8_block_sparse_attention_forward.argtypes + [vp]
+    # the sliding-window entry (include/qattn_window.h): the varlen entry's arguments with (window_left, window_right) for is_causal, + float* k_mean
+    L.qattn_fp8_quant_attention_varlen_window_workspace_bytes.restype = sz
+    L.qattn_fp8_quant_attention_varlen_window_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    L.qattn_fp8_quant_attention_varlen_window_forward.restype = i
+    L.qattn_fp8_quant_attention_varlen_window_forward.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, f,
+                                                                  vp, vp, vp, vp, vp, sz, vp, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -662,6 +669,51 @@ def fp8_quant_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
         else:
             rc = L.qattn_fp8_quant_attention_varlen_forward(*args)
     _check(rc, "qattn_fp8_quant_attention_varlen_forward_smooth" if smooth_k else "qattn_fp8_quant_attention_varlen_forward")
+    if not (return_lse or return_quant):
+        return out
+    return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) + ((k_mean,) if smooth_k else ()) if return_quant else ())
+
+
+def fp8_quant_attention_varlen_window(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,
+                                      seqused_k: Optional[torch.Tensor] = None, *, window_left: int = -1, window_right: int = -1,
+                                      fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled", sm_scale: float = 0.0, return_lse: bool = False,
+                                      return_quant: bool = False, smooth_k: bool = False):
+    """Sliding-window attention on packed sequences (qattn_fp8_quant_attention_varlen_window_forward, include/qattn_window.h): the arguments
+    and results of `fp8_quant_attention_varlen` with (window_left, window_right) -- host ints >= -1, -1 = unbounded -- in place of is_causal.
+    Row r of a sequence attends keys r + delta - window_left .. r + delta + window_right, delta = L_k(used) - L_q.
+    Returns out, or a tuple of out, [lse], [q8, k8, scale_q, scale_k, [k_mean]]."""
+    _require(int(window_left) >= -1 and int(window_right) >= -1, "window_left and window_right must be >= -1")
+    q, k, v = (t if varlen_strided_ok(t) else t.contiguous() for t in (q, k, v))
+    total_q, Hq, D = q.shape
+    total_k, Hkv = k.shape[0], k.shape[1]
+    B = cu_seqlens_q.shape[0] - 1
+    strides = None
+    if not (q.is_contiguous() and k.is_contiguous() and v.is_contiguous()):
+        dense = lambda t: (t.shape[1] * D, D)     # (a dimension of size 1 has no stride of its own)
+        strides = (ctypes.c_longlong * 6)(*[t.stride(i) if t.shape[i] > 1 else dense(t)[i] for t in (q, k, v) for i in (0, 1)])
+    L = lib()
+    dev = q.device
+    i32max = 2 ** 31 - 1
+    with torch.cuda.device(dev):
+        out = torch.empty((total_q, Hq, D), dtype=q.dtype, device=dev)
+        lse = torch.empty((Hq, total_q), dtype=torch.float32, device=dev) if return_lse else None
+        q8 = k8 = sq = sk = None
+        if return_quant:
+            q8 = torch.empty((max(L.qattn_varlen_tensor_bytes(LAYOUT_ROWMAJOR, B, Hq, total_q, D), 1),), dtype=torch.uint8, device=dev)
+            k8 = torch.empty((max(L.qattn_varlen_tensor_bytes(LAYOUT_KFRAG, B, Hkv, total_k, D), 1),), dtype=torch.uint8, device=dev)
+            sq = torch.empty((B, Hq), dtype=torch.float32, device=dev)
+            sk = torch.empty((B, Hkv), dtype=torch.float32, device=dev)
+        ws_bytes = L.qattn_fp8_quant_attention_varlen_window_workspace_bytes(B, Hq, Hkv, total_q, total_k, D)
+        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+        k_mean = None
+        if smooth_k:
+            k_mean = torch.zeros((B, Hkv, D), dtype=torch.float32, device=dev) if total_q == 0 else torch.empty((B, Hkv, D), dtype=torch.float32, device=dev)
+        rc = L.qattn_fp8_quant_attention_varlen_window_forward(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), strides, fmt_of(q.dtype), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(),
+            cu_seqlens_k.data_ptr(), _ptr(seqused_k), B, Hq, Hkv, total_q, total_k, D, fmt_of(fp8_dtype), _numerics(numerics),
+            min(int(window_left), i32max), min(int(window_right), i32max), float(sm_scale), _ptr(q8), _ptr(k8), _ptr(sq), _ptr(sk),
+            ws.data_ptr(), ws_bytes, _stream(q), _ptr(k_mean))
+    _check(rc, "qattn_fp8_quant_attention_varlen_window_forward")
     if not (return_lse or return_quant):
         return out
     return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) + ((k_mean,) if smooth_k else ()) if return_quant else ())

@@ -520,9 +520,10 @@ __device__ inline void map_block(const AttnParams& p, int bid, int nqb, bool cau
 // RAGGED = false: the caller knows that the chunk lies inside the key range (every chunk but a head's last one); the test
 // then needs nothing of AttnParams -- inside the hand-scheduled loop p.Skv was re-read from the kernel-argument segment every
 // iteration (scalar registers are short there) and its s_waitcnt lgkmcnt(0) drained the operand reads in flight.
-template <bool CAUSAL, bool TOKEN, bool RAGGED = true>
+// WINDOW (sliding-window attention, qattn_pv16.h): key j of row r is alive iff w_lo <= j - r <= w_hi; q0 is the wave's first row (32 rows).
+template <bool CAUSAL, bool TOKEN, bool RAGGED = true, bool WINDOW = false>
 __device__ __forceinline__ void prep_scores(v16f& s0, v16f& s1, const AttnParams& p, int k0, int q0, int qrow, int hh,
-                                            const float* skt) {
+                                            const float* skt, int w_lo = 0, int w_hi = 0) {
     if (TOKEN) {
 #pragma unroll
         for (int tt = 0; tt < 2; tt++)
@@ -536,12 +537,13 @@ __device__ __forceinline__ void prep_scores(v16f& s0, v16f& s1, const AttnParams
                 sx[4 * j + 0] *= w.x; sx[4 * j + 1] *= w.y; sx[4 * j + 2] *= w.z; sx[4 * j + 3] *= w.w;
             }
     }
-    const bool need_mask = (RAGGED && k0 + 64 > p.Skv) || (CAUSAL && k0 + 63 > q0);  // wave-uniform
+    const bool need_mask = (RAGGED && k0 + 64 > p.Skv) || (CAUSAL && k0 + 63 > q0) ||
+                           (WINDOW && (k0 - (q0 + 31) < w_lo || k0 + 63 - q0 > w_hi));  // wave-uniform
     if (__builtin_expect(need_mask, 0)) {
 #pragma unroll
         for (int r = 0; r < 32; r++) {
             const int key = k0 + 32 * (r >> 4) + (r & 3) + 8 * ((r & 15) >> 2) + 4 * hh;
-            const bool dead = key >= p.Skv || (CAUSAL && key > qrow);
+            const bool dead = key >= p.Skv || (CAUSAL && key > qrow) || (WINDOW && (key - qrow < w_lo || key - qrow > w_hi));
             v16f& sx = (r >> 4) ? s1 : s0;
             sx[r & 15] = dead ? -INFINITY : sx[r & 15];
         }

@@ -111,14 +111,22 @@ __device__ __forceinline__ Vec pv16_operand(v2i32 lo, v2i32 hi) {
 // one chunk only: it is the list's last entry).  Only listed chunks are DMA'd; a wave computes a position only if its own 128-row half
 // lists the block (wave-uniform: waves 0-3 / 4-7).  A wave's arithmetic is then that of the dense pass on its own listed keys gathered
 // in ascending order; the only extra operations are products with P = 0 on V chunks the wave lists (exact no-ops on finite V).
+// WINDOW (sliding-window attention, qattn_varlen_window.hip; RESOLVED, no causal flag, head-wise scales only): query row r attends the
+// keys j with win_lo <= j - r <= win_hi (and 0 <= j < Skv).  The workgroup sweeps only the chunks of [klo, khi], the keys that any of its
+// valid rows attends (sweep position u is chunk klo / 64 + u; the caller returns before the pass when that interval is empty), and a
+// wave computes only the positions its own 32 rows need -- an interval of positions, where the causal sweep has a prefix.  V rows outside
+// [klo, khi] are never read: the first and the last chunk re-read row klo / khi in their place (P is 0 there), as the ragged tail does.
+// Rows may meet chunks that are fully masked for them before their first key, or have no key at all: m_run stays at its finite start
+// value for them, so every exponential is exp2(-inf) = 0 exactly, and a row without a key ends as zeros with an LSE of -inf.
 template <int D, int NW, int QK_FMT, int V16_FMT, bool CAUSAL, bool TOKEN, bool Q16, int NS = kPv16Slots, bool PP = false, bool RESOLVED = false,
-          bool SPARSE = false, typename DrawIssue, typename DrawFinish>
+          bool SPARSE = false, bool WINDOW = false, typename DrawIssue, typename DrawFinish>
 __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned char* smem, int tid, int bid, DrawIssue&& draw_issue_hook,
                                                 DrawFinish&& draw_finish_hook,   // hooks around the row stores: the D = 128 kernel requests its next block there
-                                                int resolved_qb = 0, const int* sparse_list = nullptr) {
+                                                int resolved_qb = 0, const int* sparse_list = nullptr, int win_lo = 0, int win_hi = 0) {
     static_assert((D == 64 || D == 128 || D == 256) && NW == 8, "the DMA split is written for 8 waves");
     static_assert(!Q16 || D == 128, "the fused in-kernel form belongs to the D = 128 kernel");
     static_assert(!SPARSE || (RESOLVED && !CAUSAL && !TOKEN && !Q16), "the block-sparse sweep: resolved blocks, no causal mask, head-wise scales");
+    static_assert(!WINDOW || (RESOLVED && !CAUSAL && !TOKEN && !Q16 && !SPARSE), "the sliding-window sweep: resolved blocks, head-wise scales, no other mask");
     typedef Pv16Type<V16_FMT> T;
     typedef typename T::vec vec16;
     constexpr int CH = 64 * D;          // fp8 K chunk
@@ -173,13 +181,26 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
         __syncthreads();
         if (n_ent > 0) sp_chunks = 2 * n_ent - (2 * (__builtin_amdgcn_readfirstlane(slist[n_ent - 1]) >> 2) + 1 >= p.nchunks ? 1 : 0);
     }
+    // WINDOW: the keys [w_klo, w_khi] the workgroup's valid rows attend (not empty: the caller's test), its first chunk, and the
+    // wave's own interval of sweep positions [wu_lo, wu_hi] (empty for a wave without a valid row or without a key)
+    int w_klo = 0, w_khi = 0, w_c0 = 0, w_n = 0, wu_lo = 0, wu_hi = -1;
+    if constexpr (WINDOW) {
+        w_klo = max(q0_wg + win_lo, 0);
+        w_khi = min(min(q0_wg + QWG, p.Sq) - 1 + win_hi, p.Skv - 1);
+        w_c0 = w_klo / 64;
+        w_n = w_khi / 64 - w_c0 + 1;
+        const int klo_w = max(q0 + win_lo, 0), khi_w = min(min(q0 + kQPerWave, p.Sq) - 1 + win_hi, p.Skv - 1);
+        if (q0 < p.Sq && klo_w <= khi_w) { wu_lo = klo_w / 64 - w_c0; wu_hi = khi_w / 64 - w_c0; }
+    }
     // sweep position u -> chunk index; SPARSE: whether this wave's half lists the block of position u (0 <= u < n_wg)
     auto chunk_of = [&](int u) -> int {
         if constexpr (SPARSE) return 2 * (__builtin_amdgcn_readfirstlane(slist[max(u, 0) >> 1]) >> 2) + (u & 1);
+        else if constexpr (WINDOW) return w_c0 + u;
         else return u;
     };
     auto sp_listed = [&](int u) -> bool { return (__builtin_amdgcn_readfirstlane(slist[u >> 1]) >> (wave >> 2)) & 1; };
-    const int n_wg = SPARSE ? sp_chunks : CAUSAL ? min(p.nchunks, (min(q0_wg + QWG, p.Sq) - 1) / 64 + 1) : p.nchunks;
+    auto w_listed = [&](int u) -> bool { return u >= wu_lo && u <= wu_hi; };
+    const int n_wg = SPARSE ? sp_chunks : WINDOW ? w_n : CAUSAL ? min(p.nchunks, (min(q0_wg + QWG, p.Sq) - 1) / 64 + 1) : p.nchunks;
     const int n_w = CAUSAL ? min(n_wg, (q0 + kQPerWave - 1) / 64 + 1) : p.nchunks;
 
     // ---- one ring stage by LDS-DMA: K chunk t (KP pieces of 1 KiB over the waves) and V rows 64 t .. 64 t + 63 (VPW pieces of RPP rows per wave)
@@ -211,7 +232,12 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
         } else {
             const int j = i - KPW, pc = wave * VPW + j;
             const unsigned char* vsrc = vsrc0[j >= 0 && j < VPW ? j : 0] + (long)t * (64 * vrs);
-            if (t * 64 + 64 > p.Skv) {   // (workgroup-uniform) the head's last, ragged chunk: keys beyond Skv re-read the last row
+            if constexpr (WINDOW) {
+                if (t * 64 < w_klo || t * 64 + 64 > w_khi + 1) {   // (workgroup-uniform) the sweep's first / last chunk: no row outside [klo, khi] is read
+                    const int r = RPP * pc + vr;
+                    vsrc = vg + (long)min(max(t * 64 + r, w_klo), w_khi) * vrs + ((vc ^ swz(r)) << 4);
+                }
+            } else if (t * 64 + 64 > p.Skv) {   // (workgroup-uniform) the head's last, ragged chunk: keys beyond Skv re-read the last row
                 const int r = RPP * pc + vr;
                 vsrc = vg + (long)min(t * 64 + r, p.Skv - 1) * vrs + ((vc ^ swz(r)) << 4);
             }
@@ -332,7 +358,8 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
                     }
                 }
         }
-        prep_scores<CAUSAL, false>(s0, s1, p, t * 64, q0, qrow, hh, nullptr);
+        if constexpr (WINDOW) prep_scores<false, false, true, true>(s0, s1, p, t * 64, q0, qrow, hh, nullptr, win_lo, win_hi);
+        else prep_scores<CAUSAL, false>(s0, s1, p, t * 64, q0, qrow, hh, nullptr);
         float mx = fmaxf(fmaxf(s0[0], s0[1]), s0[2]);
 #pragma unroll
         for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, s0[r]), s0[r + 1]);
@@ -343,6 +370,8 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
             auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
             mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
         }
+        // (WINDOW: a row whose chunk is fully masked has mx = -inf: it never asks for a rescale, and when another row does, its own
+        // m_new = max(m_run, -inf) = m_run, alpha = 1; m_run is finite from the start, so no (-inf) - (-inf) arises)
         if (__any((mx - m_run) * c > kPv16RescaleThr)) {
             const float m_new = fmaxf(m_run, mx);
             const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
@@ -452,7 +481,7 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             if (issued < n_wg) { dma_stage(chunk_of(issued), issued % NS); issued++; }
-            if (SPARSE ? sp_listed(t) : t < n_w) {   // wave-uniform (causal: waves whose rows end earlier keep the barrier cadence)
+            if (SPARSE ? sp_listed(t) : WINDOW ? w_listed(t) : t < n_w) {   // wave-uniform (causal: waves whose rows end earlier keep the barrier cadence)
                 qk(t, slot);
                 softmax(chunk_of(t), no_hook);
                 pv(slot);
@@ -516,9 +545,13 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
         // SPARSE: a wave runs the trip if it lists position u (QK^T(u)) or u - 1 (PV(u - 1): the slot of u - 1 is refilled at trip u + 1, so a
         // listed position's PV never waits for the wave's next listed one).  Without a PV due, the product takes P = 0 (pb is zeroed after
         // every trip without a softmax) on V(u), a chunk the wave lists -- as the dense first trip takes it on chunk 0.
+        // WINDOW: the same rule on the wave's interval of positions.
         auto products = [&](int u) {
             if constexpr (SPARSE) {
                 const bool prev = u >= 1 && sp_listed(u - 1), cur = u < n_wg && sp_listed(u);
+                if (prev || cur) pv_qk(prev ? (u - 1) % NS : u % NS, u % NS);
+            } else if constexpr (WINDOW) {
+                const bool prev = w_listed(u - 1), cur = w_listed(u);   // (wu_lo >= 0, wu_hi < n_wg)
                 if (prev || cur) pv_qk(prev ? (u - 1) % NS : u % NS, u % NS);
             } else {
                 if (u <= n_w) pv_qk(u >= 1 ? (u - 1) % NS : 0, u % NS);
@@ -541,7 +574,7 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
             asm volatile("" ::: "memory");
             if (u >= 2 && issued < n_wg) { dma_stage(chunk_of(issued), issued % NS); issued++; }   // (stage u - 2's slot: free since the last barrier but one)
             if (do_softmax) softmax(t, no_hook);
-            else if constexpr (SPARSE) {
+            else if constexpr (SPARSE || WINDOW) {
                 const v4i z = {0, 0, 0, 0};
 #pragma unroll
                 for (int i = 0; i < 4; i++) __builtin_memcpy(&pb[i >> 1][i & 1], &z, 16);
@@ -568,7 +601,7 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
                 PV16_T(0);
                 mid();
                 PV16_T(2);
-                softmax_and_dma(u, SPARSE ? u < n_wg && sp_listed(u) : u < n_w, chunk_of(u));
+                softmax_and_dma(u, SPARSE ? u < n_wg && sp_listed(u) : WINDOW ? w_listed(u) : u < n_w, chunk_of(u));
                 PV16_T(1);
                 tail(u);
                 PV16_T(3);
@@ -576,7 +609,7 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
         } else {
 #pragma nounroll
             for (int u = 0; u <= n_wg; u++) {
-                softmax_and_dma(u, SPARSE ? u >= 1 && sp_listed(u - 1) : u >= 1 && u - 1 < n_w, chunk_of(u - 1));
+                softmax_and_dma(u, SPARSE ? u >= 1 && sp_listed(u - 1) : WINDOW ? w_listed(u - 1) : u >= 1 && u - 1 < n_w, chunk_of(u - 1));
                 PV16_T(1);
                 mid();
                 PV16_T(2);
@@ -596,20 +629,25 @@ __device__ __forceinline__ void pv16_block_pass(const AttnParams& p, unsigned ch
     const float l_lo = bcast_low16(lsum[0]), l_hi = bcast_low16(lsum[1]);
     const float l_tot = (lane & 16) ? l_hi : l_lo;
     const unsigned ticket = draw_issue_hook();
-    // (SPARSE: a half that lists no key block ends with o = 0 and l_tot = 0: zero rows, LSE -inf)
-    store_o_rows<MB>(p.out, p.out_fmt, o, SPARSE ? (l_tot > 0.0f ? 1.0f / l_tot : 0.0f) : 1.0f / l_tot, out_row_offset(p, bh, qrow, MB * 64), hh, qvalid);
+    // (SPARSE: a half that lists no key block ends with o = 0 and l_tot = 0: zero rows, LSE -inf; WINDOW: a row without a key likewise)
+    store_o_rows<MB>(p.out, p.out_fmt, o, SPARSE || WINDOW ? (l_tot > 0.0f ? 1.0f / l_tot : 0.0f) : 1.0f / l_tot, out_row_offset(p, bh, qrow, MB * 64), hh, qvalid);
     draw_finish_hook(ticket);
 #ifndef QATTN_PV16_STAMP
     if (p.lse && hh == 0 && qvalid)
-        p.lse[bh * p.lse_stride + qrow] = SPARSE && !(l_tot > 0.0f) ? -INFINITY : (0.6931471805599453f * (m_run * c) + __logf(l_tot)) * p.lse_mul;
+        p.lse[bh * p.lse_stride + qrow] = (SPARSE || WINDOW) && !(l_tot > 0.0f) ? -INFINITY : (0.6931471805599453f * (m_run * c) + __logf(l_tot)) * p.lse_mul;
 #endif
     if (p.path && hh == 0 && qvalid) p.path[bh * p.Sq + qrow] = (unsigned char)QATTN_PATH_V16;
 }
 // the same for query block qb of head `head` = b Hq + h
-template <int D, int NW, int QK_FMT, int V16_FMT, bool CAUSAL, bool TOKEN, bool Q16, int NS = kPv16Slots, bool PP = false, typename DrawIssue, typename DrawFinish>
+// (WINDOW: the sliding-window sweep, rows attending win_lo <= key - row <= win_hi)
+template <int D, int NW, int QK_FMT, int V16_FMT, bool CAUSAL, bool TOKEN, bool Q16, int NS = kPv16Slots, bool PP = false, bool WINDOW = false,
+          typename DrawIssue, typename DrawFinish>
 __device__ __forceinline__ void pv16_block_pass_at(const AttnParams& p, unsigned char* smem, int tid, int head, int qb, DrawIssue&& draw_issue_hook,
-                                                   DrawFinish&& draw_finish_hook) {
-    pv16_block_pass<D, NW, QK_FMT, V16_FMT, CAUSAL, TOKEN, Q16, NS, PP, true>(p, smem, tid, head, draw_issue_hook, draw_finish_hook, qb);
+                                                   DrawFinish&& draw_finish_hook, int win_lo = 0, int win_hi = 0) {
+    if constexpr (WINDOW)
+        pv16_block_pass<D, NW, QK_FMT, V16_FMT, CAUSAL, TOKEN, Q16, NS, PP, true, false, true>(p, smem, tid, head, draw_issue_hook, draw_finish_hook, qb,
+                                                                                              nullptr, win_lo, win_hi);
+    else pv16_block_pass<D, NW, QK_FMT, V16_FMT, CAUSAL, TOKEN, Q16, NS, PP, true>(p, smem, tid, head, draw_issue_hook, draw_finish_hook, qb);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 // Built with strided addressing (QATTN_STRIDED16 = 1: V and `out` through byte strides).
 #include "qattn_pv16.h"
 #include "qattn_varlen_tile.h"
+#include "qattn_varlen_attn.h"
 #include "../../include/qattn_varlen.h"
 
 namespace qattn {
@@ -126,21 +127,6 @@ __global__ __launch_bounds__(256) void varlen_quant_kernel(const VarlenQuant a, 
     for (int i = tid; i < 64 * D / 16; i += 256) og[i] = *reinterpret_cast<const uint4*>(img + i * 16 + ((i >> 5) << 4));
 }
 
-// the attention launch's arguments: everything but the per-sequence parts of AttnParams
-struct VarlenAttn {
-    const unsigned char* q8;   // row-major slabs
-    const unsigned char* k8;   // KFRAG images
-    const unsigned char* v;    // caller's 16-bit V
-    long v_ts, v_hs;           // its byte strides of token and head
-    void* out;                 // dense [total_q, Hq, D]
-    float* lse;                // [Hq, total_q] or nullptr
-    const float* sq;           // [B, Hq]
-    const float* sk;           // [B, Hkv]
-    const int *cu_q, *cu_k, *used;
-    int B, Hq, Hkv, total_q, total_k, nblk, out_fmt, xcd_remap;
-    float sm_log2e;
-};
-
 // PP: the two-group loop, as launch_one picks it for a whole-tensor launch (D = 128); else the one-group loop with three stages
 template <int D, int QK_FMT, int V16_FMT, bool CAUSAL, bool PP>
 __global__ __launch_bounds__(kThreads, 2) void attn_pv16_varlen_kernel(const VarlenAttn a) {
@@ -211,22 +197,25 @@ static int launch_varlen_attn_c(const VarlenAttn& a, int causal, hipStream_t st)
 // skip_k (key smoothing): K takes no part in the abs-max and quantise launches -- their grids shrink to q's slice (z = 0) -- and is
 // quantised by the launches of qattn_varlen_smooth.hip instead, as launch_quant_qkv's skip_k
 template <int D, int IN_FMT, int OUT_FMT>
-static int launch_varlen_d(const VarlenQuant& qa, const VarlenAttn& a, int numerics, int causal, hipStream_t st, bool skip_k) {
+static int launch_varlen_d(const VarlenQuant& qa, const VarlenAttn& a, int numerics, int causal, hipStream_t st, bool skip_k, const int* window) {
     const int tmax = skip_k || qa.total[0] > qa.total[1] ? qa.total[0] : qa.total[1];
     const int hmax = skip_k || qa.H[0] > qa.H[1] ? qa.H[0] : qa.H[1];
     const unsigned nz = skip_k ? 1 : 2;
     hipLaunchKernelGGL((varlen_amax_kernel<D, IN_FMT>), dim3((unsigned)(qa.B + ceil_div(tmax, kVarlenAmaxRows)), hmax, nz), dim3(256), 0, st, qa);
     hipLaunchKernelGGL((varlen_quant_kernel<D, IN_FMT, OUT_FMT>), dim3((unsigned)(qa.B + ceil_div(tmax, kVarlenQuantRows)), hmax, nz), dim3(256), 0, st,
                        qa, numerics);
+    // window: the sliding-window attention launch (qattn_varlen_window.hip) behind the same pre-pass
+    if (window) return launch_varlen_window_attn(a, D, OUT_FMT, IN_FMT, window[0], window[1], st);
     return launch_varlen_attn_c<D, OUT_FMT, IN_FMT>(a, causal, st);
 }
 template <int D>
-static int launch_varlen(const VarlenQuant& qa, const VarlenAttn& a, int in_fmt, int fp8_fmt, int numerics, int causal, hipStream_t st, bool skip_k) {
+static int launch_varlen(const VarlenQuant& qa, const VarlenAttn& a, int in_fmt, int fp8_fmt, int numerics, int causal, hipStream_t st, bool skip_k,
+                         const int* window) {
     if (in_fmt == QATTN_FMT_BF16)
-        return fp8_fmt == QATTN_FMT_E4M3 ? launch_varlen_d<D, QATTN_FMT_BF16, QATTN_FMT_E4M3>(qa, a, numerics, causal, st, skip_k)
-                                         : launch_varlen_d<D, QATTN_FMT_BF16, QATTN_FMT_E5M2>(qa, a, numerics, causal, st, skip_k);
-    return fp8_fmt == QATTN_FMT_E4M3 ? launch_varlen_d<D, QATTN_FMT_FP16, QATTN_FMT_E4M3>(qa, a, numerics, causal, st, skip_k)
-                                     : launch_varlen_d<D, QATTN_FMT_FP16, QATTN_FMT_E5M2>(qa, a, numerics, causal, st, skip_k);
+        return fp8_fmt == QATTN_FMT_E4M3 ? launch_varlen_d<D, QATTN_FMT_BF16, QATTN_FMT_E4M3>(qa, a, numerics, causal, st, skip_k, window)
+                                         : launch_varlen_d<D, QATTN_FMT_BF16, QATTN_FMT_E5M2>(qa, a, numerics, causal, st, skip_k, window);
+    return fp8_fmt == QATTN_FMT_E4M3 ? launch_varlen_d<D, QATTN_FMT_FP16, QATTN_FMT_E4M3>(qa, a, numerics, causal, st, skip_k, window)
+                                     : launch_varlen_d<D, QATTN_FMT_FP16, QATTN_FMT_E5M2>(qa, a, numerics, causal, st, skip_k, window);
 }
 
 }  // namespace qattn
@@ -258,11 +247,12 @@ extern "C" size_t qattn_fp8_quant_attention_varlen_smooth_workspace_bytes(int B,
     return plain ? up256(plain) + varlen_smooth_k_workspace_bytes(B, Hkv, D) : 0;
 }
 
-// k_mean != nullptr: key smoothing (include/qattn_smooth.h)
-static int varlen_forward_impl(const void* q, const void* k, const void* v, const long long* strides, int in_fmt, void* out, float* lse,
+// k_mean != nullptr: key smoothing (include/qattn_smooth.h); window != nullptr: {left, right} of the sliding-window entry
+// (include/qattn_window.h, validated there), whose attention launch replaces this unit's -- is_causal is then not read
+int qattn::varlen_forward_impl(const void* q, const void* k, const void* v, const long long* strides, int in_fmt, void* out, float* lse,
                                const int* cu_seqlens_q, const int* cu_seqlens_k, const int* seqused_k, int B, int Hq, int Hkv, int total_q,
                                int total_k, int D, int fp8_fmt, int numerics, int is_causal, float sm_scale, void* q8, void* k8, float* scale_q,
-                               float* scale_k, void* workspace, size_t workspace_bytes, void* stream, float* k_mean) {
+                               float* scale_k, void* workspace, size_t workspace_bytes, void* stream, float* k_mean, const int* window) {
     if (!q || !k || !v || !out || !cu_seqlens_q || !cu_seqlens_k) return QATTN_ERR_INVALID_ARG;
     if (!varlen_dims_ok(B, Hq, Hkv, total_q, total_k)) return QATTN_ERR_INVALID_ARG;
     if ((D != 64 && D != 128 && D != 256) || Hq % Hkv != 0) return QATTN_ERR_UNSUPPORTED_DIM;
@@ -317,9 +307,9 @@ static int varlen_forward_impl(const void* q, const void* k, const void* v, cons
                                     qa.scale[1], k_mean, qa.amax[1], reinterpret_cast<float*>((unsigned char*)workspace + up256(plain_bytes)), st);
         if (rc != QATTN_OK) return rc;
     }
-    if (D == 64) rc = launch_varlen<64>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st, smooth);
-    else if (D == 128) rc = launch_varlen<128>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st, smooth);
-    else rc = launch_varlen<256>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st, smooth);
+    if (D == 64) rc = launch_varlen<64>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st, smooth, window);
+    else if (D == 128) rc = launch_varlen<128>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st, smooth, window);
+    else rc = launch_varlen<256>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, st, smooth, window);
     if (rc != QATTN_OK) return rc;
     if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
     if (!smooth || !lse) return QATTN_OK;
@@ -333,7 +323,7 @@ extern "C" int qattn_fp8_quant_attention_varlen_forward(const void* q, const voi
                                                         float sm_scale, void* q8, void* k8, float* scale_q, float* scale_k, void* workspace,
                                                         size_t workspace_bytes, void* stream) {
     return varlen_forward_impl(q, k, v, strides, in_fmt, out, lse, cu_seqlens_q, cu_seqlens_k, seqused_k, B, Hq, Hkv, total_q, total_k, D, fp8_fmt,
-                               numerics, is_causal, sm_scale, q8, k8, scale_q, scale_k, workspace, workspace_bytes, stream, nullptr);
+                               numerics, is_causal, sm_scale, q8, k8, scale_q, scale_k, workspace, workspace_bytes, stream, nullptr, nullptr);
 }
 
 // The varlen entry with key smoothing (include/qattn_varlen.h; the idea: include/qattn_smooth.h): every sequence's K is quantised as fp32(k) - the channel mean of its used keys.
@@ -345,5 +335,5 @@ extern "C" int qattn_fp8_quant_attention_varlen_forward_smooth(const void* q, co
                                                                float* k_mean) {
     if (!k_mean) return QATTN_ERR_INVALID_ARG;
     return varlen_forward_impl(q, k, v, strides, in_fmt, out, lse, cu_seqlens_q, cu_seqlens_k, seqused_k, B, Hq, Hkv, total_q, total_k, D, fp8_fmt,
-                               numerics, is_causal, sm_scale, q8, k8, scale_q, scale_k, workspace, workspace_bytes, stream, k_mean);
+                               numerics, is_causal, sm_scale, q8, k8, scale_q, scale_k, workspace, workspace_bytes, stream, k_mean, nullptr);
 }

@@ -142,3 +142,114 @@ def fp8_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
         checks.config_value("attention.fp8_format"), checks.config_value("attention.quant_numerics"), bool(return_lse), smooth_k,
         scale=softmax_scale)
     return (out, lse) if return_lse else out
+
+
+# ---- sliding-window (local) attention: flash-attn's window_size on the packed call shape (include/qattn_window.h) --------------------
+def window_size_reason(window_size) -> Optional[str]:
+    """The rule a `window_size` breaks, or None: a pair (left, right) of host ints >= -1 (-1: unbounded on that side)."""
+    if not isinstance(window_size, (tuple, list)) or len(window_size) != 2:
+        return f"Expected window_size to be a pair (left, right), but got {window_size!r}"
+    if not all(_is_int(w) for w in window_size):
+        return f"Expected window_size to hold host ints, but got {window_size!r}"
+    if window_size[0] < -1 or window_size[1] < -1:
+        return f"Expected window_size values >= -1 (-1: unbounded on that side), but got {tuple(window_size)!r}"
+    return None
+
+
+def _varlen_window_eager(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, window_size, return_lse, smooth_k=False):
+    """config.attention.force_eager_fallback: `_varlen_eager`'s per-sequence loop with the window mask -- the eager quantiser per sequence
+    and head over ALL its queries and used keys (smooth_k: on fp32(k) - the fp32 mean of the used keys), de-quantise, fp32 attention with
+    the scores outside row r's window [r + delta - left, r + delta + right] (delta = L_k - L_q) at -inf; a row without a key comes out as
+    zeros (not NaN) with an LSE of -inf; the LSE of the other rows is corrected by scale * q.m under smooth_k."""
+    fp8_dtype = nn._fp8_dtype()
+    left, right = int(window_size[0]), int(window_size[1])
+    total_q, Hq, D = q.shape
+    scale = 1.0 / math.sqrt(D) if softmax_scale is None else float(softmax_scale)
+    cq, ck = cu_seqlens_q.tolist(), cu_seqlens_k.tolist()
+    used = None if seqused_k is None else seqused_k.tolist()
+    out = torch.zeros((total_q, Hq, D), dtype=q.dtype, device=q.device)
+    lse = torch.full((Hq, total_q), -math.inf, dtype=torch.float32, device=q.device)
+    for i in range(len(cq) - 1):
+        lq = cq[i + 1] - cq[i]
+        lk = ck[i + 1] - ck[i] if used is None else min(used[i], ck[i + 1] - ck[i])
+        if lq <= 0 or lk <= 0:
+            continue   # (no key: zero rows, LSE -inf)
+        qi = q[cq[i]:cq[i + 1]].transpose(0, 1)[None]
+        ki, vi = (t[ck[i]:ck[i] + lk].transpose(0, 1)[None] for t in (k, v))
+        q8, sq = nn._dynamically_quantize_fp8(qi, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+        mean = None
+        if smooth_k:
+            ki = ki.to(torch.float32)
+            mean = ki.mean(dim=-2, keepdim=True)   # [1, Hkv, 1, D]
+            ki = ki - mean
+        k8, sk = nn._dynamically_quantize_fp8(ki, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+        dq = q8.float() * sq[..., None, None]
+        dk = nn._expand_kv_heads(k8.float() * sk[..., None, None], Hq)
+        dv = nn._expand_kv_heads(vi.float(), Hq)
+        d = torch.arange(lk, device=q.device)[None, :] - torch.arange(lq, device=q.device)[:, None] - (lk - lq)   # j - (r + delta)
+        alive = torch.ones(lq, lk, dtype=torch.bool, device=q.device)
+        if left >= 0:
+            alive &= d >= -left
+        if right >= 0:
+            alive &= d <= right
+        s = ((dq @ dk.transpose(-1, -2)) * scale).masked_fill(~alive, -math.inf)
+        l = torch.logsumexp(s[0], dim=-1)
+        p = torch.exp(s[0] - l.clamp_min(torch.finfo(torch.float32).min)[..., None])   # (a row without keys: exp(-inf) = 0)
+        out[cq[i]:cq[i + 1]] = (p @ dv[0]).to(q.dtype).transpose(0, 1)
+        if smooth_k:   # (-inf rows stay -inf)
+            l = l + scale * (qi[0].to(torch.float32) * nn._expand_kv_heads(mean, Hq)[0]).sum(-1)
+        lse[:, cq[i]:cq[i + 1]] = l
+    return (out, lse) if return_lse else out
+
+
+def fp8_attn_varlen_window_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window_size, dropout_p=0.0, softmax_scale=None,
+                                *, seqused_k=None, return_lse=False):
+    """Sliding-window (local) FP8 attention over packed variable-length sequences: `fp8_attn_varlen_func`'s tensors, tables and results
+    with flash-attn's `window_size=(left, right)` in place of `causal` (include/qattn_window.h).  Per sequence with L_q queries and L_k USED
+    keys, delta = L_k - L_q: query r attends key j iff r + delta - left <= j <= r + delta + right (and 0 <= j < L_k); -1 means unbounded on
+    that side, values larger than any length are legal.  (-1, 0) is the causal mask aligned bottom-right (flash-attn >= 2.1), (-1, -1)
+    masks nothing.  A row whose window holds no key gives a zero row and an LSE of -inf.
+    Numerics are the packed entry's: q and k quantised head-wise per (sequence, head) over all queries and all used keys -- keys outside
+    every window still count toward K's scale -- and 16-bit P on the original 16-bit V.  A 256-row query block visits only the 64-key
+    chunks its rows attend, and V rows outside them are never read.  config.attention.smooth_k, fp8_format and quant_numerics are followed as by
+    `fp8_attn_varlen_func` (the mean over the used keys, the LSE corrected).  Unsupported input raises ValueError(reason)."""
+    smooth_k = bool(checks.config_value("attention.smooth_k"))
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = varlen_input_reason(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, seqused_k)
+        if reason is None:
+            reason = window_size_reason(window_size)
+        if reason is None:
+            ok, reason = nn._pre_check_can_use_hip_attention(device=q.device)
+            reason = None if ok else reason
+        if reason:
+            raise ValueError(reason)
+    if checks.config_value("attention.force_eager_fallback") and not torch.compiler.is_dynamo_compiling():
+        return _varlen_window_eager(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, window_size, return_lse, smooth_k)
+    out, lse = nn._ops().fp8_varlen_window_attention_forward(
+        q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, int(max_seqlen_q), int(max_seqlen_k), int(window_size[0]), int(window_size[1]),
+        checks.config_value("attention.fp8_format"), checks.config_value("attention.quant_numerics"), bool(return_lse), smooth_k,
+        scale=softmax_scale)
+    return (out, lse) if return_lse else out
+
+
+def fp8_window_attn_func(q, k, v, window_size, *, scale=None, return_lse=False):
+    """Sliding-window FP8 attention on dense [B, H, S, D] tensors (the block-sparse entry's call shape): q [B, Hq, Sq, D], k / v
+    [B, Hkv, Skv, D]; every batch entry is one sequence of `fp8_attn_varlen_window_func` (scales per (batch, head), delta = Skv - Sq).
+    The packed [B S, H, D] views and the arange(B+1) S tables are built on the device, without a host synchronisation.  The view is free
+    when B == 1, or when a tensor's batch stride equals S x its token stride (anything backed by [B, S, H, D] memory); any other layout
+    with B > 1 -- a contiguous [B, H, S, D] among them -- costs ONE re-layout copy of that tensor.
+    Returns out as a [B, Hq, Sq, D] view of the packed result, or (out, lse) with return_lse (lse fp32 [B, Hq, Sq], a view)."""
+    if not all(isinstance(t, Tensor) for t in (q, k, v)) or q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("NYI: query, key and value must be 4-D tensors [B, heads, seq_len, head_dim]")
+    if k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0]:
+        raise ValueError(f"Expect query and key/value to have the same batch size but got {q.shape[0]}, {k.shape[0]} and {v.shape[0]}.")
+    if not checks.config_value("attention.skip_supported_check") and window_size_reason(window_size):
+        raise ValueError(window_size_reason(window_size))   # (before the tables are built on the device)
+    B, Hq, Sq, D = q.shape
+    Skv = k.shape[2]
+    # [B, H, S, D] -> [B, S, H, D] -> [B S, H, D]: reshape returns a view exactly where the rule above holds, else one copy
+    qp, kp, vp = (t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], t.shape[1], t.shape[3]) for t in (q, k, v))
+    steps = torch.arange(B + 1, dtype=_INDEX_DTYPE, device=q.device)
+    res = fp8_attn_varlen_window_func(qp, kp, vp, steps * Sq, steps * Skv, Sq, Skv, window_size, softmax_scale=scale, return_lse=return_lse)
+    out = (res[0] if return_lse else res).view(B, Sq, Hq, D).permute(0, 2, 1, 3)
+    return (out, res[1].view(Hq, B, Sq).permute(1, 0, 2)) if return_lse else out
