@@ -203,7 +203,7 @@ int qattn_attention_forward_16(const void* q, const void* k16, const void* v16, 
         int Hkv, int Sq, int Skv, int D, int fmt, int is_causal, float sm_scale, int fast_exp,
         void* stream);
 
-/* strided views of q, k, v: qattn_strided.h; measurement aids (clock stamps, launch timing, probe): qattn_measure.h */
+/* strided views: qattn_strided.h; measurement aids: qattn_measure.h; sizes, alignment, what is written: qattn_buffers.h */
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@
  *   q8 / k8   NULL (then q8 lives in the workspace; k8 is not written) or row-major fp8 [B, Hq, Sq, D] / [B, Hkv, Skv, D] outputs;
  *   scale_q / scale_k   NULL (workspace) or fp32 [B, Hq] / [B, Hkv] outputs.
  *
+ * Sizes, alignment and which bytes of each buffer are written: include/qattn_buffers.h.
  * Launches: the quant pre-pass of q and of k, the mask-to-list kernel, the attention kernel.  The mask is read on the device only: no host
  * synchronisation, no allocation, graph-capture safe (a captured call follows later contents of the mask).  Errors (before any device
  * call): QATTN_ERR_INVALID_ARG (NULL q / k / v / out / block_mask, a non-positive extent, negative mask strides, bases off 16 bytes, bad

@@ -1,0 +1,25 @@
+/*
+ * qattn_buffers.h -- the BUFFER CONTRACT of every entry of qattn.h, qattn_strided.h, qattn_smooth.h, qattn_varlen.h, qattn_window.h and
+ * qattn_block_sparse.h (documentation only: no declaration).  Held by tests/test_gpu_buffer_contract.py on guarded buffers of exactly
+ * these sizes at exactly these alignments.
+ *
+ *   sizes      a buffer of qattn_*_tensor_bytes / qattn_lse_row_stride / *_workspace_bytes bytes (or of the stated shape) suffices; no entry
+ *              reads or writes a byte before a buffer's start or past its end, ragged last tiles included, and no result depends on bytes
+ *              outside the inputs (the pads between the rows / heads of a strided view included) or on what a workspace or an output held.
+ *   alignment  16 bytes (the kernels' widest access: dwordx4 loads / stores, LDS-DMA rows): q / k / v / out and their 8-bit images (q8, k8, v8,
+ *              x8, fragment images), every workspace, k_mean.  4 bytes: fp32 scale_*, amax_*, ssq_*, lse (read and written one float at a
+ *              time, or as float4 runs at whatever offset a head's rows start: token-wise scale_k) and the int32 tables.  1 byte: row_path,
+ *              block_mask.  More alignment is never assumed.
+ *   written    every element of out, lse (REFERENCE layout: the Sq floats of each row, not the pad up to the row stride), row_path, scale_q,
+ *              scale_k, k_mean and of a quantiser's / packer's own outputs (fragment images: the zero padding up to 64 keys included); of a
+ *              strided `out` only the D elements of each row -- the pads between rows and heads keep what they held.  The fused entries
+ *              (qattn.h: qattn_fp8_quant_attention_forward) also write ALL of k8, of q8 where the PATH TABLE says q_quant = prepass (the
+ *              pre-pass's row-major image = qattn_quant_qkv_fp8's) and of v8 / scale_v where v_format = head (per-head VFRAG image and scale).
+ *   scratch    not for a caller to read: q8 of the fused entries where q_quant = kernel (untouched); their v8 / scale_v where v_format =
+ *              block (bytes under per-chunk scales kept in the workspace; scale_v = 1); the packed entries' k8 between the sequences'
+ *              images (qattn_varlen.h: the images of the used keys do not tile the buffer).
+ */
+#ifndef QATTN_BUFFERS_H_
+#define QATTN_BUFFERS_H_
+#include "qattn.h"
+#endif /* QATTN_BUFFERS_H_ */

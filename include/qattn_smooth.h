@@ -29,6 +29,7 @@
  *   amax_k, ssq_k   describe the UNSMOOTHED K: must be NULL, else QATTN_ERR_INVALID_ARG.  amax_q and amax_v work as in ..._forward_ex;
  *             ssq_q is accepted and not used (without K's sum the forecast takes both from the pre-pass: q is read for its own).
  *   workspace at least qattn_fp8_quant_attention_smooth_workspace_bytes(...) bytes, 16-byte aligned.
+ * Sizes, alignment and which bytes of each buffer are written: include/qattn_buffers.h.
  * Costs one more read of K than the plain entry (mean pass, abs-max pass, quantise pass instead of the last two); K rides in launches of
  * its own, q and V in the plain pre-pass.  No host synchronisation, no allocation, graph-capture safe, like every entry.
  */

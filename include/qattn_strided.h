@@ -12,6 +12,7 @@
  *             aligned; else QATTN_ERR_INVALID_ARG.  NULL = dense [B,H,S,D] (= ..._forward_ex).  A stride of 0 broadcasts an INPUT (e.g. one
  *             K / V for every batch).  `out` as a view: e.g. the transpose of a dense [B,Sq,Hq,D] buffer, which the caller reshapes to
  *             [B,Sq,Hq D] for its output projection without a copy (the reference allocates a dense [B,Hq,Sq,D]: tk/attention.py:434-437).
+ * Sizes, alignment and which bytes of each buffer are written: include/qattn_buffers.h.
  *   everything else: as qattn_fp8_quant_attention_forward_ex.
  */
 #ifndef QATTN_STRIDED_H_

@@ -21,6 +21,7 @@
  *             byte Hq D cu_q[i];  k8 KFRAG (include/qattn.h), sequence i's [Hkv, ceil(L_k/64) 64, D] image at byte Hkv D (cu_k[i] + 64 i);
  *             sizes: qattn_varlen_tensor_bytes(QATTN_LAYOUT_ROWMAJOR / _KFRAG, ...);  scale_q fp32 [B, Hq], scale_k fp32 [B, Hkv].
  *
+ * Sizes, alignment and which bytes of each buffer are written: include/qattn_buffers.h.
  * Tables are read on the device only: no host synchronisation, no allocation, graph-capture safe (a captured call follows later
  * contents of the tables).  Every extent is clamped -- start = clamp(cu[i], 0, total), end = clamp(cu[i+1], start, total), used keys
  * <= end - start -- so that no table content makes a kernel touch memory outside its tensors; results for inconsistent tables are

@@ -33,6 +33,7 @@
  * safe (a captured call follows later contents of the tables); every extent is clamped.  Errors (before any device call): those of the
  * packed entry, and QATTN_ERR_INVALID_ARG for window_left < -1 or window_right < -1.
  *
+ * Sizes, alignment and which bytes of each buffer are written: include/qattn_buffers.h.
  * Workspace: at least qattn_fp8_quant_attention_varlen_window_workspace_bytes(...) (enough with and without k_mean), 16-byte aligned.
  */
 #ifndef QATTN_WINDOW_H_
