@@ -293,12 +293,34 @@ __device__ __forceinline__ bool row_is_peaked(const AttnParams& p, float l, floa
 // both 32-wide K blocks of every row here; profiles/r02_mfma_scale_probe.log) and 127 = 2^0 for B = P in byte 1 -- the
 // instruction takes its two scales from vector registers only, op_sel picks the byte, so one register serves both (a
 // separate register holding the constant 127 cost the tightest instantiations a spill).  VS = false: the plain product.
-constexpr int kScaleWordOne = (127 << 8) | 127;   // A x 2^0, B x 2^0
-__device__ __forceinline__ int vscale_word(unsigned e8m0_byte) { return (int)((e8m0_byte & 0xffu) | (127u << 8)); }
+// Byte 2 is B's scale for the LOW term of two-term P (below): 2^-kLoGainLog2.
+constexpr int kLoGainLog2 = 5;
+constexpr float kLoGain = 32.0f;
+constexpr int kScaleWordOne = ((127 - kLoGainLog2) << 16) | (127 << 8) | 127;   // A x 2^0, B x 2^0 (hi) / 2^-5 (lo)
+__device__ __forceinline__ int vscale_word(unsigned e8m0_byte) { return (int)((e8m0_byte & 0xffu) | (unsigned)(kScaleWordOne & 0xffff00)); }
 template <int CBSZ, int BLGP, bool VS>
 __device__ inline v16f mfma_pv(v8i a, v8i b, v16f c, int scale_word) {
     if constexpr (VS) return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, CBSZ, BLGP, 0, scale_word, 1, scale_word);
     else return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, CBSZ, BLGP, 0, 0, 0, 0);
+}
+// Two-term P = hi + lo, hi = e4m3(p'), lo = e4m3((p' - hi) * 2^5) taken back by B's block scale 2^-5 in the PV product.  Unscaled, the low
+// term has the floor of the high one: on a row whose top key carries nearly all of it, the other keys' p' < 2^-10 round to zero in BOTH
+// terms while the fp32 row sum keeps them, and O comes out short by their mass times V's mean (1 % of a constant V: tests/vwitness.py).
+// The gain moves the floor to 2^-15.  |p' - hi| <= 8 (half a step at p' <= 2^8, kRescaleThr), so |lo| <= 256 < 448 -- ONLY for callers
+// whose p' cannot exceed 2^8 (the exact-exponential sweeps, which rescale before a row's maximum passes kRescaleThr): at p' in (256, 448]
+// the residual x 2^5 reaches 512 and the conversion would saturate.  lo_terms: the four
+// residuals of one P dword, two per v_cvt (v_fma_f32 on the dequantised high bytes x 2^5 instead of the v_sub_f32 -- no instruction more).
+__device__ __forceinline__ int lo_terms(const float (&e)[4], int hi, int old) {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const f2 h01 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8((unsigned)hi, kLoGain, false);
+    const f2 h23 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8((unsigned)hi, kLoGain, true);
+    int lo = cvt_pk_fp8<QATTN_FMT_E4M3, false>(__builtin_fmaf(e[0], kLoGain, -h01[0]), __builtin_fmaf(e[1], kLoGain, -h01[1]), old);
+    return cvt_pk_fp8<QATTN_FMT_E4M3, true>(__builtin_fmaf(e[2], kLoGain, -h23[0]), __builtin_fmaf(e[3], kLoGain, -h23[1]), lo);
+}
+// ... and its PV product: V's scale from byte 0 as above, P's from byte 2 (VS = false: the word is kScaleWordOne)
+template <int CBSZ, int BLGP>
+__device__ inline v16f mfma_pv_lo(v8i a, v8i b, v16f c, int scale_word) {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, CBSZ, BLGP, 0, scale_word, 2, scale_word);
 }
 
 template <int CBSZ, int BLGP>
@@ -679,11 +701,7 @@ __device__ __forceinline__ void rescue_rows_at(const AttnParams& p, unsigned cha
             for (int i = 0; i < 4; i++) { e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(sx[4 * j + i], c, mc)); ls += e[i]; }
             int hi = cvt_pk_fp8<QATTN_FMT_E4M3, false>(e[0], e[1], 0);
             hi = cvt_pk_fp8<QATTN_FMT_E4M3, true>(e[2], e[3], hi);
-            typedef float f2 __attribute__((ext_vector_type(2)));
-            const f2 h01 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false), h23 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true);
-            int lo = cvt_pk_fp8<QATTN_FMT_E4M3, false>(e[0] - h01[0], e[1] - h01[1], 0);
-            lo = cvt_pk_fp8<QATTN_FMT_E4M3, true>(e[2] - h23[0], e[3] - h23[1], lo);
-            ph[w] = hi; pl[w] = lo;
+            ph[w] = hi; pl[w] = lo_terms(e, hi, 0);
         }
         l_run += ls;
 #pragma unroll
@@ -696,10 +714,10 @@ __device__ __forceinline__ void rescue_rows_at(const AttnParams& p, unsigned cha
             for (int m = 0; m < VB; m++) {
                 if constexpr (VSCALE) {   // (the D = 128 kernel's call: V may be block-scaled)
                     o[m0 + m] = mfma_pv<V_FMT, QATTN_FMT_E4M3, true>(vf[m], ph, o[m0 + m], vsx);
-                    o[m0 + m] = mfma_pv<V_FMT, QATTN_FMT_E4M3, true>(vf[m], pl, o[m0 + m], vsx);
+                    o[m0 + m] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(vf[m], pl, o[m0 + m], vsx);
                 } else {
                     o[m0 + m] = mfma_f8<V_FMT, QATTN_FMT_E4M3>(vf[m], ph, o[m0 + m]);
-                    o[m0 + m] = mfma_f8<V_FMT, QATTN_FMT_E4M3>(vf[m], pl, o[m0 + m]);
+                    o[m0 + m] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(vf[m], pl, o[m0 + m], kScaleWordOne);
                 }
             }
         }

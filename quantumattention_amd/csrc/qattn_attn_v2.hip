@@ -109,7 +109,7 @@ __device__ __forceinline__ void pv_chunk(const unsigned char* vbuf, const v8i& p
     for (int m = 0; m < D / 32; m++) {
         const v8i va = lds_read_frag(vbuf + (m << 11));
         o[m] = mfma_f8<V_FMT, QATTN_FMT_E4M3>(va, ph, o[m]);
-        if (TWO) o[m] = mfma_f8<V_FMT, QATTN_FMT_E4M3>(va, plo, o[m]);
+        if (TWO) o[m] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(va, plo, o[m], kScaleWordOne);
     }
 }
 
@@ -136,11 +136,8 @@ __device__ __forceinline__ void exp_group(const v16f& sx, int j, float c, float 
     int ph = cvt_pk_fp8<QATTN_FMT_E4M3, false>(e[0], e[1], TWO ? fresh_hi : seed);
     ph = cvt_pk_fp8<QATTN_FMT_E4M3, true>(e[2], e[3], ph);
     if (TWO) {
-        // (v_cvt_pk_f32_fp8: two bytes per instruction -- the pass is bound by vector issue)
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        const f2 h01 = __builtin_amdgcn_cvt_pk_f32_fp8(ph, false), h23 = __builtin_amdgcn_cvt_pk_f32_fp8(ph, true);
-        int plo = cvt_pk_fp8<QATTN_FMT_E4M3, false>(e[0] - h01[0], e[1] - h01[1], fresh_lo);
-        plo = cvt_pk_fp8<QATTN_FMT_E4M3, true>(e[2] - h23[0], e[3] - h23[1], plo);
+        // (lo_terms dequantises two bytes per instruction -- the pass is bound by vector issue)
+        int plo = lo_terms(e, ph, fresh_lo);
         asm volatile("" : "+v"(plo));
         plv[w] = plo;
     }
@@ -210,7 +207,7 @@ __device__ __forceinline__ void full_step(WaveState<D, TWO, BYTE>& st, const uns
 
     // slot 0: O0 += V0.P(t-2)            reads: V2            VALU: max over tile 0
     st.o[0] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(st.vpre[0], pp, st.o[0], st.vsx);
-    if (TWO) st.o[0] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(st.vpre[0], ppl, st.o[0], st.vsx);
+    if (TWO) st.o[0] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(st.vpre[0], ppl, st.o[0], st.vsx);
     v8i fc = LDSF(vprev + (2 << 11));
     // (v_max3_f32 through asm: on MFMA results the compiler otherwise adds a canonicalising v_max_f32 x, x, x per chain.  Three
     // interleaved chains: hipcc pads wait states between an asm statement and a VALU that reads its output unless two other
@@ -224,7 +221,7 @@ __device__ __forceinline__ void full_step(WaveState<D, TWO, BYTE>& st, const uns
     QATTN_SLOT_FENCE();
     // slot 1: O1 += V1.P(t-2)            reads: V3            VALU: max over tile 1, group 0
     st.o[1] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(st.vpre[1], pp, st.o[1], st.vsx);
-    if (TWO) st.o[1] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(st.vpre[1], ppl, st.o[1], st.vsx);
+    if (TWO) st.o[1] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(st.vpre[1], ppl, st.o[1], st.vsx);
     v8i fd = LDSF(vprev + (3 << 11));
     mxa = max3_raw(mxa, sc0[15], sc1[0]);
     mxb = max3_raw(mxb, sc1[1], sc1[2]);
@@ -240,7 +237,7 @@ __device__ __forceinline__ void full_step(WaveState<D, TWO, BYTE>& st, const uns
     QATTN_SLOT_FENCE();
     // slot 2: O2 += V2.P(t-2)            reads: Q k-step 0, K(tile 0, k-step 0)      VALU: group 1
     st.o[2] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(fc, pp, st.o[2], st.vsx);
-    if (TWO) st.o[2] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(fc, ppl, st.o[2], st.vsx);
+    if (TWO) st.o[2] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(fc, ppl, st.o[2], st.vsx);
     v8i qf;
     if (QREG) qf = st.qreg[0]; else qf = LDSF(qbuf);
     v8i ka = LDSF(kbuf + (0 << 11));
@@ -248,14 +245,14 @@ __device__ __forceinline__ void full_step(WaveState<D, TWO, BYTE>& st, const uns
     QATTN_SLOT_FENCE();
     // slot 3: O3 += V3.P(t-2)            reads: K(tile 1, k-step 0)                  VALU: group 2
     st.o[3] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(fd, pp, st.o[3], st.vsx);
-    if (TWO) st.o[3] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(fd, ppl, st.o[3], st.vsx);
+    if (TWO) st.o[3] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(fd, ppl, st.o[3], st.vsx);
     v8i kb = LDSF(kbuf + (2 << 11));
     QATTN_SM_GROUP(false, sc0, 2, mc, 2, pc[1]);
     QATTN_SLOT_FENCE();
     stage();  // K/V staging of a later chunk: after the PV slots are in flight, not between the barrier and the first MFMA
     // slot 4 (BYTE): row sum of the quantised P(t-2) on the matrix pipe: ones(32x64).P^T -> every row = sum over 64 keys
     if (BYTE || SUMM) st.lsum = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(st.ones, pp, st.lsum, QATTN_FMT_E4M3, QATTN_FMT_E4M3, 0, 0, 0, 0);
-    if (SUMM && TWO) st.lsum = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(st.ones, ppl, st.lsum, QATTN_FMT_E4M3, QATTN_FMT_E4M3, 0, 0, 0, 0);
+    if (SUMM && TWO) st.lsum = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(st.ones, ppl, st.lsum, QATTN_FMT_E4M3, QATTN_FMT_E4M3, 0, kScaleWordOne, 2, kScaleWordOne);
     // ... and of its bytes read as e5m2 ~= P'^2 / 2 (WaveState::lsq)
     if (BYTE && NEFF) st.lsq = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(st.ones, pp, st.lsq, QATTN_FMT_E4M3, QATTN_FMT_E5M2, 0, 0, 0, 0);
     v8i qg;                            // Q k-step 1
@@ -556,13 +553,13 @@ __device__ __forceinline__ bool kv_sweep(WaveState<D, TWO, BYTE>& st, const Attn
             st.o[2] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(fc, pp, st.o[2], st.vsx);
             st.o[3] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(fd, pp, st.o[3], st.vsx);
             if (TWO) {
-                st.o[0] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(st.vpre[0], ppl, st.o[0], st.vsx);
-                st.o[1] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(st.vpre[1], ppl, st.o[1], st.vsx);
-                st.o[2] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(fc, ppl, st.o[2], st.vsx);
-                st.o[3] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(fd, ppl, st.o[3], st.vsx);
+                st.o[0] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(st.vpre[0], ppl, st.o[0], st.vsx);
+                st.o[1] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(st.vpre[1], ppl, st.o[1], st.vsx);
+                st.o[2] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(fc, ppl, st.o[2], st.vsx);
+                st.o[3] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(fd, ppl, st.o[3], st.vsx);
             }
             if (BYTE || SUMM) st.lsum = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(st.ones, pp, st.lsum, QATTN_FMT_E4M3, QATTN_FMT_E4M3, 0, 0, 0, 0);
-            if (SUMM && TWO) st.lsum = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(st.ones, ppl, st.lsum, QATTN_FMT_E4M3, QATTN_FMT_E4M3, 0, 0, 0, 0);
+            if (SUMM && TWO) st.lsum = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(st.ones, ppl, st.lsum, QATTN_FMT_E4M3, QATTN_FMT_E4M3, 0, kScaleWordOne, 2, kScaleWordOne);
             if (BYTE && NEFF) st.lsq = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(st.ones, pp, st.lsq, QATTN_FMT_E4M3, QATTN_FMT_E5M2, 0, 0, 0, 0);
         };
         if (t & 1) tail(P1{}); else tail(P0{});
@@ -746,7 +743,10 @@ __device__ __forceinline__ int attend_block(const AttnParams& p, unsigned char* 
 // and lane.  The two-term sweep is bound by vector-instruction issue, and this took 4.8 % off it (profiles/r04/ab_two_term_valu_diet.log) --
 // but it breaks the bound on very peaked rows (q x 3 at S = 4096: 0.022): thousands of keys 15 binades below the row's top key flush to
 // zero in fp8; their V rows average out of the numerator, but their weights ARE 0.5 .. 1 % of the denominator, and a denominator that
-// drops them too rescales the output by that much.  The exact fp32 sum of the un-rounded exponentials stays.
+// drops them too rescales the output by that much.  The exact fp32 sum of the un-rounded exponentials stays.  (That was measured with the
+// low term at the high term's floor.  The numerator had the mirror-image fault on a V that does NOT average out -- those keys' mass
+// times V's mean was missing from it -- and the low term now carries a gain of 2^5, qattn_attn.h lo_terms: the quantised sums would keep
+// those keys too; SUMM has not been measured again and stays off.  Its low-term sum takes B's scale from byte 2 like the PV products.)
 template <int D, int NW, int QK_FMT, int V_FMT, bool CAUSAL, bool TOKEN, bool TWO, bool BYTE, int ABL, bool Q16, bool NEFF = false, bool SUMM = false, int IN16 = QATTN_FMT_BF16>
 __device__ __forceinline__ int block_pass(const AttnParams& p, unsigned char* smem, int tid, int bid, bool check_peaked, volatile unsigned* mail = nullptr) {
     constexpr int CH = 64 * D;      // bytes of one K (or V) chunk

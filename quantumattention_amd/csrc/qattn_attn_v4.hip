@@ -295,12 +295,7 @@ void attn_fwd_kernel_v4(const AttnParams p, const int qb_lo, const int qb_n, con
                 ph = cvt_pk_fp8<QATTN_FMT_E4M3, true>(e[2], e[3], ph);
                 pv[w] = ph;
                 int plo = 0;
-                if (two) {
-                    typedef float f2 __attribute__((ext_vector_type(2)));
-                    const f2 h01 = __builtin_amdgcn_cvt_pk_f32_fp8(ph, false), h23 = __builtin_amdgcn_cvt_pk_f32_fp8(ph, true);
-                    plo = cvt_pk_fp8<QATTN_FMT_E4M3, false>(e[0] - h01[0], e[1] - h01[1], 0);
-                    plo = cvt_pk_fp8<QATTN_FMT_E4M3, true>(e[2] - h23[0], e[3] - h23[1], plo);
-                }
+                if (two) plo = lo_terms(e, ph, 0);
                 pl[w] = plo;
             }
             l_run += ls;
@@ -310,8 +305,8 @@ void attn_fwd_kernel_v4(const AttnParams p, const int qb_lo, const int qb_n, con
         o[0] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(vf0, pv, o[0], vsx);
         o[1] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(vf1, pv, o[1], vsx);
         if (!BYTE && two) {
-            o[0] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(vf0, pl, o[0], vsx);
-            o[1] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(vf1, pl, o[1], vsx);
+            o[0] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(vf0, pl, o[0], vsx);
+            o[1] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(vf1, pl, o[1], vsx);
         }
 #pragma unroll
         for (int m = 2; m < MB; m += 2) {  // the remaining fragments land under the MFMAs already issued
@@ -319,8 +314,8 @@ void attn_fwd_kernel_v4(const AttnParams p, const int qb_lo, const int qb_n, con
             o[m] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(va, pv, o[m], vsx);
             o[m + 1] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(vb, pv, o[m + 1], vsx);
             if (!BYTE && two) {
-                o[m] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(va, pl, o[m], vsx);
-                o[m + 1] = mfma_pv<V_FMT, QATTN_FMT_E4M3, VS>(vb, pl, o[m + 1], vsx);
+                o[m] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(va, pl, o[m], vsx);
+                o[m + 1] = mfma_pv_lo<V_FMT, QATTN_FMT_E4M3>(vb, pl, o[m + 1], vsx);
             }
         }
         if (BYTE) lsum = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ones, pv, lsum, QATTN_FMT_E4M3, QATTN_FMT_E4M3, 0, 0, 0, 0);

@@ -21,7 +21,7 @@ def fp8_round(x):
     return x.to(torch.float8_e4m3fn).float()
 
 
-def sim_head(q, k, v, c, sv, causal, mode, shift=5.0, thr=3.0, bias=0.0, two_term=False, chunk=64):
+def sim_head(q, k, v, c, sv, causal, mode, shift=5.0, thr=3.0, bias=0.0, two_term=False, chunk=64, lo_gain=32.0):
     """q [Sq,D], k,v [Skv,D] float32 (already de-quantised payload values, scales folded into c / sv).
     mode: 'exact' (v_exp + RNE fp8, l from unrounded p) | 'exact_lq' (l from rounded p) | 'byte' (Schraudolph byte)"""
     Sq, D = q.shape
@@ -55,8 +55,8 @@ def sim_head(q, k, v, c, sv, causal, mode, shift=5.0, thr=3.0, bias=0.0, two_ter
             p = torch.exp2(x)
             ph = fp8_round(p)
             pterms = [ph]
-            if two_term:
-                pterms.append(fp8_round(p - ph))
+            if two_term:   # the low term carries a gain of 2^5 that the PV product's block scale takes back (csrc/qattn_attn.h, lo_terms)
+                pterms.append(fp8_round((p - ph) * lo_gain) / lo_gain)
             if mode == "exact":
                 l_run = l_run + p.sum(dim=1)
             else:
