@@ -18,6 +18,15 @@
  *   scratch    not for a caller to read: q8 of the fused entries where q_quant = kernel (untouched); their v8 / scale_v where v_format =
  *              block (bytes under per-chunk scales kept in the workspace; scale_v = 1); the packed entries' k8 between the sequences'
  *              images (qattn_varlen.h: the images of the used keys do not tile the buffer).
+ *
+ * qattn_fp8_quant_attention_varlen_forward_fp8pv (qattn_varlen.h), beyond what the packed entries above state for q8 / k8 / scale_q / scale_k:
+ *   v8         qattn_varlen_tensor_bytes(QATTN_LAYOUT_KFRAG, B, Hkv, total_k, D) bytes (k8's size), 16-byte aligned.  Written: sequence i's VFRAG image,
+ *              Hkv ceil(L_k/64) 64 D bytes from byte Hkv D (cu_k[i] + 64 i) (L_k its used keys; the zero padding up to 64 keys included).
+ *              Scratch between the images: as k8's, the images of the used keys do not tile the buffer.
+ *   scale_v    fp32 [B, Hkv], 4-byte aligned; every element written (a sequence without a used key: the quantiser's eps).
+ *   row_path   uint8 [Hq, total_q], 1-byte aligned; written: the columns cu_q[i] .. cu_q[i+1]-1 of every sequence, the others keep what they held.
+ *   k_mean     fp32 [B, Hkv, D], 16-byte aligned; every element written (as the _smooth entry).
+ *   workspace  ..._fp8pv_workspace_bytes (with k_mean: ..._fp8pv_smooth_workspace_bytes) bytes, 16-byte aligned; no result depends on what it held.
  */
 #ifndef QATTN_BUFFERS_H_
 #define QATTN_BUFFERS_H_

@@ -74,6 +74,56 @@ int qattn_fp8_quant_attention_varlen_forward_smooth(const void* q, const void* k
                                                     float sm_scale, void* q8, void* k8, float* scale_q, float* scale_k, void* workspace,
                                                     size_t workspace_bytes, void* stream, float* k_mean);
 
+
+/*
+ * FP8 P.V on packed sequences (an ABI-8 addition, names found by symbol; the entries above keep their signatures, launches and bits).
+ *
+ * qattn_fp8_quant_attention_varlen_forward_fp8pv: the arguments of qattn_fp8_quant_attention_varlen_forward, with after sm_scale
+ *   precision   QATTN_PRECISION_FAST or _ACCURATE (_AUTO and anything else: QATTN_ERR_INVALID_ARG -- no moments, no rescue pass here);
+ * after k8
+ *   v8          NULL (then it lives in the workspace) or out: per-sequence VFRAG images laid out like k8's KFRAG images -- sequence i's
+ *               [Hkv, ceil(L_k/64) 64, D] image at byte Hkv D (cu_k[i] + 64 i), L_k its USED keys; size qattn_varlen_tensor_bytes(
+ *               QATTN_LAYOUT_KFRAG, B, Hkv, total_k, D): k8's (a 64-key chunk is 64 D bytes in both layouts; the query keeps answering 0
+ *               for QATTN_LAYOUT_VFRAG, as released);
+ * after scale_k
+ *   scale_v     NULL or fp32 [B, Hkv];
+ *   row_path    NULL or uint8 [Hq, total_q] (the LSE's layout): QATTN_PATH_* of every row of a sequence;
+ *   k_mean      NULL = no smoothing; else out, fp32 [B, Hkv, D], 16-byte aligned, as in ..._forward_smooth;
+ * then workspace, workspace_bytes, stream.
+ *
+ * NUMERICS, per sequence i and head h, bit for bit:
+ *   q8 / scale_q, k8 / scale_k, k_mean   those of qattn_fp8_quant_attention_varlen_forward (with k_mean: of ..._forward_smooth, LSE
+ *                correction included) for the same arguments.
+ *   v8 / scale_v the head-wise quant pre-pass (qattn_quant_fp8, QATTN_SCALE_HEAD, QATTN_LAYOUT_VFRAG, `numerics`) of sequence i's USED
+ *                keys alone; the padding rows of its last 64-key chunk are zero bytes.  Keys beyond seqused_k influence no output bit,
+ *                V's scale included (NaN or 1e4 padding there is legal); V MUST BE FINITE on the used keys.
+ *   attention    the sweep of qattn_fp8_block_sparse_attention_forward_fp8pv (include/qattn_block_sparse.h) over the sequence's 64-key
+ *                chunks in ascending order, one 4-wave workgroup per 128-row tile t of the sequence, scale_v[i, kv(h)] applied in the
+ *                epilogue: a non-causal sequence's rows and LSE are those of that entry on the sequence alone under an all-true mask.
+ *                ACCURATE  exact exponentials and two-term (hi + lo) e4m3 P on every row; row_path QATTN_PATH_TWO_TERM.
+ *                FAST      the one-term sweep (QATTN_PATH_ONE_TERM) for the tiles whose rows see n >= 1024 keys, two-term below;
+ *                          n = used L_k, or with is_causal n = min(L_k, 128 (t + 1)).  One-term tiles: byte exponentials, or exact
+ *                          exponentials when lse != NULL (the same bound, other bits).  No rescue: stated for score variance
+ *                          sm_scale^2 D <= 1, as the block-sparse entry's FAST.
+ *   is_causal    key j <= query r of the same sequence, top-left, token-exact: tile t sweeps chunks 0 .. ceil(min(L_k, 128 (t + 1)) / 64)
+ *                - 1 and reads no K or V chunk beyond them.
+ *   A sequence with L_q = 0 has no rows; one with queries and no used key gets zero rows, an LSE of -inf and QATTN_PATH_ONE_TERM.
+ *   total_q = 0: nothing is computed or written.
+ * Launches: zeroing node; [K's mean (two), abs-max and quantise passes with k_mean;] one abs-max and one quantise pass over q, k (unless
+ * smoothed) and v; attention -- one launch for ACCURATE (and for FAST when total_k < 1024), two for FAST (one-term tiles, two-term tiles:
+ * a workgroup of the other launch's tile returns at once); the LSE correction with k_mean and lse.  No length is read on the host, nothing
+ * is allocated, graph-capture safe.  Errors, clamps and argument checks: those of the plain entry, before any device call; workspace at
+ * least ..._fp8pv_workspace_bytes (with k_mean: ..._fp8pv_smooth_workspace_bytes), 16-byte aligned.
+ */
+size_t qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes(int B, int Hq, int Hkv, int total_q, int total_k, int D);
+size_t qattn_fp8_quant_attention_varlen_fp8pv_smooth_workspace_bytes(int B, int Hq, int Hkv, int total_q, int total_k, int D);
+int qattn_fp8_quant_attention_varlen_forward_fp8pv(const void* q, const void* k, const void* v, const long long* strides, int in_fmt, void* out,
+                                                   float* lse, const int* cu_seqlens_q, const int* cu_seqlens_k, const int* seqused_k, int B,
+                                                   int Hq, int Hkv, int total_q, int total_k, int D, int fp8_fmt, int numerics, int is_causal,
+                                                   float sm_scale, int precision, void* q8, void* k8, void* v8, float* scale_q, float* scale_k,
+                                                   float* scale_v, unsigned char* row_path, float* k_mean, void* workspace,
+                                                   size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,9 @@ from .quantum_attn_interface import (
 # packed variable-length sequences (flash-attn's varlen call shape): a package attribute beyond the reference's seven exported names
 from .varlen import fp8_attn_varlen_func  # noqa: E402
 
+# ... with the P.V path as an argument (pv_precision="fp8": both products on the FP8 matrix pipe): a package attribute too, not in __all__
+from .varlen import fp8_attn_varlen_pv_func  # noqa: E402
+
 # sliding-window (local) attention, packed and dense call shapes: package attributes too, not in __all__
 from .varlen import fp8_attn_varlen_window_func, fp8_window_attn_func  # noqa: E402
 

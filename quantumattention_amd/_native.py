@@ -45,6 +45,8 @@ EXPORTS = (
     "qattn_fp8_quant_attention_varlen_window_workspace_bytes", "qattn_fp8_quant_attention_varlen_window_forward",
     "qattn_fp8_block_sparse_attention_fp8pv_workspace_bytes", "qattn_fp8_block_sparse_attention_fp8pv_smooth_workspace_bytes",
     "qattn_fp8_block_sparse_attention_forward_fp8pv",
+    "qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes", "qattn_fp8_quant_attention_varlen_fp8pv_smooth_workspace_bytes",
+    "qattn_fp8_quant_attention_varlen_forward_fp8pv",
 )
 BLOCK_SPARSE_BLOCK = 128   # QATTN_BLOCK_SPARSE_BLOCK (include/qattn_block_sparse.h): rows / keys per mask block
 
@@ -182,6 +184,15 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_block_sparse_attention_fp8pv_smooth_workspace_bytes.argtypes = [i, i, i, i, i, i]
     L.qattn_fp8_block_sparse_attention_forward_fp8pv.restype = i
     L.qattn_fp8_block_sparse_attention_forward_fp8pv.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i,
+                                                                 vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    # the packed entry with FP8 P.V (include/qattn_varlen.h): the plain entry's arguments up to sm_scale, then precision, q8, k8, v8,
+    # scale_q, scale_k, scale_v, row_path, k_mean (NULL: no smoothing), workspace, workspace_bytes, stream
+    L.qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes.restype = sz
+    L.qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    L.qattn_fp8_quant_attention_varlen_fp8pv_smooth_workspace_bytes.restype = sz
+    L.qattn_fp8_quant_attention_varlen_fp8pv_smooth_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    L.qattn_fp8_quant_attention_varlen_forward_fp8pv.restype = i
+    L.qattn_fp8_quant_attention_varlen_forward_fp8pv.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f, i,
                                                                  vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
@@ -683,6 +694,59 @@ def fp8_quant_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     if not (return_lse or return_quant):
         return out
     return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) + ((k_mean,) if smooth_k else ()) if return_quant else ())
+
+
+def fp8_quant_attention_varlen_fp8pv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,
+                                     seqused_k: Optional[torch.Tensor] = None, *, is_causal: bool = False, fp8_dtype=torch.float8_e4m3fn,
+                                     numerics: str = "compiled", sm_scale: float = 0.0, precision: str = "accurate", return_lse: bool = False,
+                                     return_quant: bool = False, return_path: bool = False, smooth_k: bool = False):
+    """Packed variable-length sequences with FP8 P.V (qattn_fp8_quant_attention_varlen_forward_fp8pv, include/qattn_varlen.h): the arguments
+    of `fp8_quant_attention_varlen`; every sequence's v is quantised head-wise over its used keys (finite there), precision "accurate"
+    (two-term e4m3 P everywhere) or "fast" (one-term byte-exponential P for the 128-row tiles whose rows see >= 1024 keys).
+    return_quant (test output): also (q8, k8, v8, scale_q, scale_k, scale_v) -- q8 the row-major per-sequence slabs (uint8, Hq D cu_q[i]
+    bytes in), k8 / v8 the KFRAG / VFRAG images (Hkv D (cu_k[i] + 64 i) bytes in), scales fp32 [B, H] -- and, with smooth_k, k_mean fp32
+    [B, Hkv, D]; return_path: also row_path uint8 [Hq, total_q] (PATH_*; columns of no sequence keep what the buffer held).
+    Returns out, or a tuple of out, [lse], [q8, k8, v8, scale_q, scale_k, scale_v, [k_mean]], [row_path]."""
+    _require(precision in ("fast", "accurate"), f"Unsupported precision for the packed FP8 P.V path: {precision!r} (expected 'fast' or 'accurate')")
+    q, k, v = (t if varlen_strided_ok(t) else t.contiguous() for t in (q, k, v))
+    total_q, Hq, D = q.shape
+    total_k, Hkv = k.shape[0], k.shape[1]
+    B = cu_seqlens_q.shape[0] - 1
+    strides = None
+    if not (q.is_contiguous() and k.is_contiguous() and v.is_contiguous()):
+        dense = lambda t: (t.shape[1] * D, D)     # (a dimension of size 1 has no stride of its own)
+        strides = (ctypes.c_longlong * 6)(*[t.stride(i) if t.shape[i] > 1 else dense(t)[i] for t in (q, k, v) for i in (0, 1)])
+    L = lib()
+    dev = q.device
+    with torch.cuda.device(dev):
+        out = torch.empty((total_q, Hq, D), dtype=q.dtype, device=dev)
+        lse = torch.empty((Hq, total_q), dtype=torch.float32, device=dev) if return_lse else None
+        q8 = k8 = v8 = sq = sk = sv = None
+        if return_quant:
+            q8 = torch.empty((max(L.qattn_varlen_tensor_bytes(LAYOUT_ROWMAJOR, B, Hq, total_q, D), 1),), dtype=torch.uint8, device=dev)
+            k8 = torch.empty((max(L.qattn_varlen_tensor_bytes(LAYOUT_KFRAG, B, Hkv, total_k, D), 1),), dtype=torch.uint8, device=dev)
+            v8 = torch.empty((max(L.qattn_varlen_tensor_bytes(LAYOUT_KFRAG, B, Hkv, total_k, D), 1),), dtype=torch.uint8, device=dev)
+            sq = torch.empty((B, Hq), dtype=torch.float32, device=dev)
+            sk = torch.empty((B, Hkv), dtype=torch.float32, device=dev)
+            sv = torch.empty((B, Hkv), dtype=torch.float32, device=dev)
+        path = torch.empty((Hq, total_q), dtype=torch.uint8, device=dev) if return_path else None
+        k_mean = None
+        if smooth_k:
+            k_mean = torch.zeros((B, Hkv, D), dtype=torch.float32, device=dev) if total_q == 0 else torch.empty((B, Hkv, D), dtype=torch.float32, device=dev)
+        ws_of = (L.qattn_fp8_quant_attention_varlen_fp8pv_smooth_workspace_bytes if smooth_k
+                 else L.qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes)
+        ws_bytes = ws_of(B, Hq, Hkv, total_q, total_k, D)
+        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+        rc = L.qattn_fp8_quant_attention_varlen_forward_fp8pv(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), strides, fmt_of(q.dtype), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(),
+            cu_seqlens_k.data_ptr(), _ptr(seqused_k), B, Hq, Hkv, total_q, total_k, D, fmt_of(fp8_dtype), _numerics(numerics), int(is_causal),
+            float(sm_scale), _precision(precision), _ptr(q8), _ptr(k8), _ptr(v8), _ptr(sq), _ptr(sk), _ptr(sv), _ptr(path), _ptr(k_mean),
+            ws.data_ptr(), ws_bytes, _stream(q))
+    _check(rc, "qattn_fp8_quant_attention_varlen_forward_fp8pv")
+    if not (return_lse or return_quant or return_path):
+        return out
+    return ((out,) + ((lse,) if return_lse else ()) + ((q8, k8, v8, sq, sk, sv) + ((k_mean,) if smooth_k else ()) if return_quant else ())
+            + ((path,) if return_path else ()))
 
 
 def fp8_quant_attention_varlen_window(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,

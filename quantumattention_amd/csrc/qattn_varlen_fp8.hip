@@ -1,0 +1,550 @@
+// qattn_varlen_fp8.hip -- qattn_fp8_quant_attention_varlen_forward_fp8pv (include/qattn_varlen.h): FP8 attention on packed sequences with
+// BOTH products on the FP8 matrix pipe -- Q K^T as the 16-bit-PV packed entry (qattn_varlen.hip), P.V as e4m3 P on a FP8 V that is
+// quantised head-wise per (sequence, kv head) over the sequence's USED keys.
+//
+// Launches after a zeroing node, none of which reads a length on the host:
+//   amax   per (sequence, head) abs-max of q, k and v (used keys only): qattn_varlen.hip's pass (256-row tiles, atomicMax on the fp32
+//          bits) with V as a third z slice
+//   quant  64-row tiles: q into its row-major slab, k into its KFRAG image -- statement for statement qattn_varlen.hip's pass, so the
+//          bytes and scales are the 16-bit-PV entry's -- and v into a VFRAG image beside k's (quant8 / vfrag_offset of the dense pre-pass)
+//          With key smoothing K is left out of both (qattn_varlen_smooth.hip's launches quantise it), as in the 16-bit-PV entry.
+//   attn   attn_vfp8_kernel: attn_bs_fp8_kernel (qattn_block_sparse_fp8.hip) with the packed block map in place of the mask lists --
+//          one 4-wave workgroup per (head, 128-row tile of a sequence) sweeps the 64-key chunks 0 .. n - 1 of that sequence (causal:
+//          up to the tile's diagonal), the chunk number being the loop counter.  ACCURATE: one launch.  FAST: two launches, as there --
+//          the one-term sweep for the tiles whose rows see >= kTwoTermKeys keys, the two-term sweep for the rest; a workgroup whose tile
+//          belongs to the other launch returns before any DMA or barrier.  With total_k < kTwoTermKeys no tile can be one-term: one launch.
+//
+// Block -> (sequence, tile): qattn_varlen_tile.h with R = 128.
+#include "qattn_attn.h"
+#include "qattn_varlen_tile.h"
+#include "../../include/qattn_varlen.h"
+
+namespace qattn {
+
+constexpr int kVfpTile = 128;   // query rows per workgroup
+constexpr int kVfpWaves = 4;
+constexpr int kVfpStages = 2;
+static_assert(kVfpTile == kVfpWaves * kQPerWave && kVfpTile == 2 * 64, "a workgroup is one 128-row tile; its diagonal spans two 64-key chunks");
+
+// q (z = 0), k (z = 1) and v (z = 2) of one call
+struct VfpQuant {
+    const unsigned char* x[3];   // 16-bit inputs
+    long ts[3], hs[3];           // element strides of token and head
+    const int* cu[3];
+    const int* used;             // seqused_k or nullptr (k and v)
+    int total[3], H[3];
+    int B, skip_k;               // skip_k: key smoothing quantises K in launches of its own
+    unsigned* amax[3];           // [B][H] fp32 bits, zeroed before the abs-max pass
+    unsigned char* x8[3];        // q8 row-major slabs / k8 KFRAG images / v8 VFRAG images
+    float* scale[3];             // [B][H]
+};
+
+template <int D, int IN_FMT>
+__global__ __launch_bounds__(256) void vfp_amax_kernel(const VfpQuant a) {
+    constexpr int VPR = D / 8;   // 16-byte vectors per row
+    const int z = blockIdx.z, h = blockIdx.y;
+    if (h >= a.H[z] || (z == 1 && a.skip_k)) return;
+    const VarlenTile t = varlen_tile<kVarlenAmaxRows>(a.cu[z], z ? a.used : nullptr, a.B, a.total[z], (int)blockIdx.x);
+    if (t.tile < 0 || t.tile * kVarlenAmaxRows >= t.len) return;
+    const int row0 = t.tile * kVarlenAmaxRows, rows = min(kVarlenAmaxRows, t.len - row0);
+    const unsigned char* xh = a.x[z] + 2 * ((long)(t.start + row0) * a.ts[z] + (long)h * a.hs[z]);
+    const int nvec = rows * VPR;
+    unsigned m0 = 0, m1 = 0;
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    auto fold = [&](const uint4& v) {
+        unsigned w[4] = {v.x & 0x7fff7fffu, v.y & 0x7fff7fffu, v.z & 0x7fff7fffu, v.w & 0x7fff7fffu};
+        u16x2 pa, pb, pc, pd, p0, p1;
+        __builtin_memcpy(&pa, &w[0], 4); __builtin_memcpy(&pb, &w[1], 4); __builtin_memcpy(&pc, &w[2], 4); __builtin_memcpy(&pd, &w[3], 4);
+        __builtin_memcpy(&p0, &m0, 4); __builtin_memcpy(&p1, &m1, 4);
+        p0 = __builtin_elementwise_max(p0, __builtin_elementwise_max(pa, pb));
+        p1 = __builtin_elementwise_max(p1, __builtin_elementwise_max(pc, pd));
+        __builtin_memcpy(&m0, &p0, 4); __builtin_memcpy(&m1, &p1, 4);
+    };
+    for (int base = threadIdx.x; base < nvec; base += 4 * 256) {
+        uint4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int idx = base + u * 256;
+            v[u] = make_uint4(0, 0, 0, 0);
+            if (idx < nvec) v[u] = load_nt(reinterpret_cast<const uint4*>(xh + 2 * (long)(idx / VPR) * a.ts[z]) + idx % VPR);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) fold(v[u]);
+    }
+    unsigned m = wave_allmax_u32(max(max(m0 & 0xffffu, m0 >> 16), max(m1 & 0xffffu, m1 >> 16)));
+    __shared__ unsigned red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = max(max(red[0], red[1]), max(red[2], red[3]));
+        atomicMax(a.amax[z] + (long)t.i * a.H[z] + h, __float_as_uint(load16f<IN_FMT>((unsigned short)m)));
+    }
+}
+
+template <int D, int IN_FMT, int OUT_FMT>
+__global__ __launch_bounds__(256) void vfp_quant_kernel(const VfpQuant a, int numerics) {
+    constexpr int VPR = D / 8;
+    constexpr int ITERS = 64 * VPR / 256;
+    constexpr int KPAD = 64 * D + (64 * D / 512) * 16;   // the KFRAG image of quant_multi_kernel, padded by 16 B per 512 B
+    __shared__ __attribute__((aligned(16))) unsigned char img[KPAD];
+    const int z = blockIdx.z, h = blockIdx.y, tid = threadIdx.x;
+    if (h >= a.H[z] || (z == 1 && a.skip_k)) return;
+    const int H = a.H[z];
+    const VarlenTile t = varlen_tile<kVarlenQuantRows>(a.cu[z], z ? a.used : nullptr, a.B, a.total[z], (int)blockIdx.x);
+    if (t.tile < 0) return;
+    const float inv_qmax = (float)(1.0 / (double)(OUT_FMT == QATTN_FMT_E4M3 ? 448.0 : 57344.0));
+    const float scale = make_scale(__uint_as_float(a.amax[z][(long)t.i * H + h] & 0x7fffffffu), inv_qmax, numerics, IN_FMT);
+    if (t.tile == 0 && tid == 0) a.scale[z][(long)t.i * H + h] = scale;   // (also for an empty sequence: amax 0 -> eps)
+    if (t.tile * kVarlenQuantRows >= t.len) return;
+    const float rinv = 1.0f / scale;
+    const int row0 = t.tile * kVarlenQuantRows;
+    const unsigned char* xh = a.x[z] + 2 * ((long)t.start * a.ts[z] + (long)h * a.hs[z]);
+    uint4 held[ITERS];
+#pragma unroll
+    for (int it = 0; it < ITERS; it++) {
+        const int vec = it * 256 + tid, row = row0 + vec / VPR;
+        held[it] = make_uint4(0, 0, 0, 0);   // (rows beyond the used length: the zero padding of the dense pack)
+        if (row < t.len) held[it] = load_nt(reinterpret_cast<const uint4*>(xh + 2 * (long)row * a.ts[z]) + vec % VPR);
+    }
+    if (z == 0) {   // q: row-major slab [Hq, L_q, D] at element Hq D start
+        int2* og = reinterpret_cast<int2*>(a.x8[0] + (long)H * D * t.start + ((long)h * t.len + row0) * D);
+#pragma unroll
+        for (int it = 0; it < ITERS; it++) {
+            const int vec = it * 256 + tid, r = vec / VPR;
+            const int2 lohi = quant8<IN_FMT, OUT_FMT>(held[it], scale, rinv);
+            if (row0 + r < t.len) og[(long)r * (D / 8) + vec % VPR] = lohi;
+        }
+        return;
+    }
+    // k / v: KFRAG / VFRAG image of the sequence, [Hkv, ceil(L/64) 64, D] at element Hkv D (start + 64 i)
+    const long Lp = (long)((t.len + 63) / 64) * 64;
+    uint4* og = reinterpret_cast<uint4*>(a.x8[z] + (long)H * D * (t.start + 64L * t.i) + ((long)h * Lp + row0) * D);
+    if (z == 1) {
+#pragma unroll
+        for (int it = 0; it < ITERS; it++) {
+            const int vec = it * 256 + tid, r = vec / VPR, dv = vec % VPR;
+            const int2 lohi = quant8<IN_FMT, OUT_FMT>(held[it], scale, rinv);
+            const int o = kfrag_offset<D>(r, dv * 8);
+            *reinterpret_cast<int2*>(img + o + ((o >> 9) << 4)) = lohi;
+        }
+        __syncthreads();
+        for (int i = tid; i < 64 * D / 16; i += 256) og[i] = *reinterpret_cast<const uint4*>(img + i * 16 + ((i >> 5) << 4));
+        return;
+    }
+    // v: 8 consecutive d of one key land 16 bytes apart in the image (vfrag_offset); byte scatter as pack_tile_kernel (a pre-pass, not hot)
+#pragma unroll
+    for (int it = 0; it < ITERS; it++) {
+        const int vec = it * 256 + tid, r = vec / VPR, dv = vec % VPR;
+        const int2 lohi = quant8<IN_FMT, OUT_FMT>(held[it], scale, rinv);
+        unsigned char b[8];
+        __builtin_memcpy(b, &lohi, 8);
+#pragma unroll
+        for (int j = 0; j < 8; j++) img[vfrag_offset<D>(r, dv * 8 + j)] = b[j];
+    }
+    __syncthreads();
+    for (int i = tid; i < 64 * D / 16; i += 256) og[i] = reinterpret_cast<const uint4*>(img)[i];
+}
+
+// the attention launch's arguments
+struct VfpAttn {
+    const unsigned char* q8;   // row-major slabs
+    const unsigned char* k8;   // KFRAG images
+    const unsigned char* v8;   // VFRAG images, laid out like k8's
+    void* out;                 // dense [total_q, Hq, D]
+    float* lse;                // [Hq, total_q] or nullptr
+    unsigned char* path;       // [Hq, total_q] or nullptr
+    const float* sq;           // [B, Hq]
+    const float* sk;           // [B, Hkv]
+    const float* sv;           // [B, Hkv]
+    const int *cu_q, *cu_k, *used;
+    int B, Hq, Hkv, total_q, total_k, nblk, out_fmt, xcd_remap, two_term_keys;
+    float sm_log2e;
+};
+
+// LIGHT = the byte-exponential kernel (the lean register budget); the exact / two-term variants get one wave per SIMD less
+// (BsfShape of qattn_block_sparse_fp8.hip)
+template <int D, bool LIGHT> struct VfpShape {
+    static constexpr int WPS = D == 256 ? 2 : (D == 64 ? (LIGHT ? 4 : 3) : (LIGHT ? 3 : 2));
+};
+
+// 4 scores -> 4 e4m3 bytes of 2^x (byte_exp4 of qattn_attn_v4.hip)
+__device__ __forceinline__ int vfp_byte_exp4(float s0, float s1, float s2, float s3, float c8, float off8) {
+    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    const us2 qa = __builtin_amdgcn_cvt_pknorm_u16(__builtin_fmaf(s0, c8, off8), __builtin_fmaf(s1, c8, off8));
+    const us2 qb = __builtin_amdgcn_cvt_pknorm_u16(__builtin_fmaf(s2, c8, off8), __builtin_fmaf(s3, c8, off8));
+    unsigned ua, ub;
+    __builtin_memcpy(&ua, &qa, 4);
+    __builtin_memcpy(&ub, &qb, 4);
+    return (int)__builtin_amdgcn_perm(ub, ua, 0x06040200u);
+}
+
+constexpr int kVfpSelAll = 0, kVfpSelMany = 1, kVfpSelFew = 2;   // which tiles a launch attends: all / rows see >= two_term_keys keys / fewer
+
+// BYTE: byte-exponential P + matrix-pipe row sums.  !BYTE: exact v_exp_f32, RNE e4m3, fp32 row sums (LSE output) and -- `two` -- the
+// hi + lo two-term P.  The sweep and the epilogue are attn_bs_fp8_kernel's, operation for operation: a non-causal sequence comes out
+// with the bits of the block-sparse FP8-PV call on that sequence alone under an all-true mask.
+template <int D, int FMT, bool BYTE, bool CAUSAL>
+__global__ __launch_bounds__(kVfpWaves * 64, (VfpShape<D, BYTE>::WPS))
+void attn_vfp8_kernel(const VfpAttn a, const int two, const int sel) {
+    constexpr int NW = kVfpWaves;
+    constexpr int CH = 64 * D, STAGE = 2 * CH, MB = D / 32, KS = D / 64;
+    constexpr int RK = CH / (NW * 1024);   // 1 KiB DMA pieces per wave for the K (and for the V) part of a stage
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ql = lane & 31, hh = lane >> 5;
+
+    const int bid = blockIdx.x;
+    int h, j;
+    if (a.xcd_remap) {   // (speed only) every XCD takes a contiguous range of heads, all sequences of each: their K / V stay in its L2
+        const int idx = bid >> 3, hpx = a.Hq >> 3;
+        h = (bid & 7) * hpx + idx / a.nblk;
+        j = idx % a.nblk;
+    } else {
+        h = bid / a.nblk;
+        j = bid % a.nblk;
+    }
+    if (CAUSAL) j = a.nblk - 1 - j;   // (the last tiles of a sequence see the most keys: roughly longest first)
+    const VarlenTile tq = varlen_tile<kVfpTile>(a.cu_q, nullptr, a.B, a.total_q, j);
+    if (tq.tile < 0 || tq.tile * kVfpTile >= tq.len) return;   // no tile of any sequence
+    const int i = tq.i;
+    const int sk0 = clampi(__builtin_amdgcn_readfirstlane(a.cu_k[i]), 0, a.total_k);
+    int lk = clampi(__builtin_amdgcn_readfirstlane(a.cu_k[i + 1]), sk0, a.total_k) - sk0;
+    if (a.used) lk = clampi(__builtin_amdgcn_readfirstlane(a.used[i]), 0, lk);
+    // keys the tile's rows see (its last row, when causal): the rule of the one-term sweep and the trip count, both workgroup-uniform
+    const int keys = CAUSAL ? min(lk, kVfpTile * (tq.tile + 1)) : lk;
+    if (sel == kVfpSelMany && keys < a.two_term_keys) return;
+    if (sel == kVfpSelFew && keys >= a.two_term_keys) return;
+
+    const int kvh = h / (a.Hq / a.Hkv);
+    const int qrow = tq.tile * kVfpTile + wave * kQPerWave + ql;   // row within the sequence
+    const bool qvalid = qrow < tq.len;
+    const long orow = ((long)(tq.start + (qvalid ? qrow : 0)) * a.Hq + h) * (2L * D);   // bytes: rows are a token stride apart
+    const long lrow = (long)h * a.total_q + tq.start + qrow;                           // lse / path: [Hq, total_q]
+    if (keys == 0) {   // a sequence with queries and no used key: zero rows, LSE -inf, path code QATTN_PATH_ONE_TERM
+        v16f z[MB];
+#pragma unroll
+        for (int m = 0; m < MB; m++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) z[m][r] = 0.0f;
+        store_o_rows<MB>(a.out, a.out_fmt, z, 0.0f, orow, hh, qvalid);
+        if (a.lse && hh == 0 && qvalid) a.lse[lrow] = -INFINITY;
+        if (a.path && hh == 0 && qvalid) a.path[lrow] = (unsigned char)QATTN_PATH_ONE_TERM;
+        return;
+    }
+    const int n_wg = (keys + 63) >> 6;        // chunks 0 .. n_wg - 1 (a causal tile: up to its diagonal)
+    const int nch = (lk + 63) >> 6;           // chunks of the sequence's images
+
+    const long img = (long)a.Hkv * D * (sk0 + 64L * i) + (long)kvh * nch * CH + (wave << 10);
+    const unsigned char* kg_w = a.k8 + img;
+    const unsigned char* vg_w = a.v8 + img;
+    // stage(t) = {K chunk t, V chunk t} -> slot t & 1; every wave copies 2*RK x 1 KiB of it by LDS-DMA
+    const unsigned lane16 = (unsigned)lane << 4;
+    unsigned slot_next = 0;
+    auto dma_chunk = [&](int chunk) {
+        unsigned char* dst = smem + slot_next + (wave << 10);
+        const size_t coff = (size_t)chunk * CH + lane16;
+#pragma unroll
+        for (int r = 0; r < RK; r++) {
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kg_w + (coff + r * (NW * 1024))),
+                                             (__attribute__((address_space(3))) void*)(dst + r * (NW * 1024)), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vg_w + (coff + r * (NW * 1024))),
+                                             (__attribute__((address_space(3))) void*)(dst + CH + r * (NW * 1024)), 16, 0, 0);
+        }
+        slot_next ^= STAGE;
+    };
+    dma_chunk(0);
+
+    // Q^T fragments parked in this lane's own LDS slots
+    unsigned char* qbuf = smem + kVfpStages * STAGE + wave * (KS << 11) + (hh << 10) + (ql << 4);
+    {
+        const unsigned char* qp = a.q8 + (long)a.Hq * D * tq.start + ((long)h * tq.len + (qvalid ? qrow : 0)) * D + hh * 32;
+#pragma unroll
+        for (int s = 0; s < KS; s++) {
+            v4i lo = *reinterpret_cast<const v4i*>(qp + s * 64);
+            v4i hi = *reinterpret_cast<const v4i*>(qp + s * 64 + 16);
+            if (!qvalid) { lo = v4i{0, 0, 0, 0}; hi = v4i{0, 0, 0, 0}; }
+            *reinterpret_cast<v4i*>(qbuf + (s << 11)) = lo;
+            *reinterpret_cast<v4i*>(qbuf + (s << 11) + 512) = hi;
+        }
+    }
+    const float c = a.sm_log2e * a.sq[(long)i * a.Hq + h] * a.sk[(long)i * a.Hkv + kvh];
+
+    v16f o[MB];
+#pragma unroll
+    for (int m = 0; m < MB; m++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) o[m][r] = 0.0f;
+    v4f lsum = {0.0f, 0.0f, 0.0f, 0.0f};
+    v8i ones;  // A of the row-sum MFMA (see WaveState::lsum in qattn_attn_v2.hip)
+    {
+        const int row = lane & 15, kg = lane >> 4;
+        const int one = ((row == 0 && !(kg & 1)) || (row == 1 && (kg & 1))) ? 0x38383838 : 0;
+#pragma unroll
+        for (int w = 0; w < 8; w++) ones[w] = one;
+    }
+    float m_run = -1.0e30f, l_run = 0.0f;
+    float lim = -1.0e30f, off8 = 0.0f;   // m_run + thr / c and the byte formula's additive constant (set by the first chunk's fix-up)
+    constexpr float U16 = 1.0f / 65535.0f;
+    const float c8 = (8.0f * U16) * c;
+    const int frag_lane_off = (hh << 10) + (ql << 4);
+    const int kend = CAUSAL ? min(lk, qrow + 1) : lk;   // this lane's row attends keys 0 .. kend - 1 (token-exact)
+    const int diag = 2 * tq.tile;                       // causal: chunks >= diag hold keys beyond the tile's first row
+
+    for (int t = 0; t < n_wg; t++) {
+        v8i qf[KS];
+#pragma unroll
+        for (int s = 0; s < KS; s++) qf[s] = lds_read_frag(qbuf + (s << 11));
+        wait_vmcnt<0>();                  // this wave's pieces of stage t have landed
+        __builtin_amdgcn_s_barrier();     // ... and everyone's; every wave is also done with stage t-1's slot
+        if (t + 1 < n_wg) dma_chunk(t + 1);
+        const unsigned char* kbuf = smem + (t & 1) * STAGE + frag_lane_off;
+        const unsigned char* vbuf = kbuf + CH;
+        // ---- S^T = K.Q^T
+        v16f s0, s1;
+#pragma unroll
+        for (int r = 0; r < 16; r++) { s0[r] = 0.0f; s1[r] = 0.0f; }
+#pragma unroll
+        for (int s = 0; s < KS; s++) {
+            const v8i ka = lds_read_frag(kbuf + ((0 * KS + s) << 11)), kb = lds_read_frag(kbuf + ((1 * KS + s) << 11));
+            s0 = mfma_f8<FMT, FMT>(ka, qf[s], s0);
+            s1 = mfma_f8<FMT, FMT>(kb, qf[s], s1);
+        }
+        const v8i vf0 = lds_read_frag(vbuf), vf1 = lds_read_frag(vbuf + (1 << 11));
+        // ---- ragged tail of the sequence's keys; causal: the diagonal, by token (workgroup-uniform condition)
+        const int k0 = t * 64;
+        if (__builtin_expect(k0 + 64 > lk || (CAUSAL && t >= diag), 0)) {
+#pragma unroll
+            for (int r = 0; r < 32; r++) {
+                const int key = k0 + 32 * (r >> 4) + (r & 3) + 8 * ((r & 15) >> 2) + 4 * hh;
+                v16f& sx = (r >> 4) ? s1 : s0;
+                sx[r & 15] = key >= kend ? -INFINITY : sx[r & 15];
+            }
+        }
+        // ---- running max; rescale only when a row's max grew past the headroom of the shifted exponent
+        float mx = max32_after_mfma(s0, s1);
+        {
+            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
+            mx = max3_raw(__uint_as_float(sw[0]), __uint_as_float(sw[1]), __uint_as_float(sw[1]));
+        }
+        if (__builtin_expect(__any(mx > lim) != 0, 0)) {   // (mx - m_run) c > thr: P' could overflow e4m3
+            const float m_new = fmaxf(m_run, mx);
+            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
+#pragma unroll
+            for (int m = 0; m < MB; m++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) o[m][r] *= alpha;
+            if (BYTE) {
+                const float alpha16 = __shfl(alpha, (lane & 15) + 16);
+                lsum[0] *= alpha;
+                lsum[1] *= alpha16;
+            } else {
+                l_run *= alpha;
+            }
+            m_run = m_new;
+            lim = m_new + kRescaleThrByte / c;
+            off8 = __builtin_fmaf((-8.0f * U16) * m_new, c, (8.0f * kPShiftByte + 56.0f + kByteBias) * U16);
+        }
+        v8i pv, pl;
+        if (BYTE) {
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                pv[w] = vfp_byte_exp4(s0[4 * w], s0[4 * w + 1], s0[4 * w + 2], s0[4 * w + 3], c8, off8);
+                pv[4 + w] = vfp_byte_exp4(s1[4 * w], s1[4 * w + 1], s1[4 * w + 2], s1[4 * w + 3], c8, off8);
+            }
+        } else {
+            const float mc = kPShift - m_run * c;
+            float ls = 0.0f;
+#pragma unroll
+            for (int w = 0; w < 8; w++) {
+                const v16f& sx = w < 4 ? s0 : s1;
+                const int jj = w & 3;
+                float e[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) { e[u] = __builtin_amdgcn_exp2f(__builtin_fmaf(sx[4 * jj + u], c, mc)); ls += e[u]; }
+                int ph = cvt_pk_fp8<QATTN_FMT_E4M3, false>(e[0], e[1], 0);
+                ph = cvt_pk_fp8<QATTN_FMT_E4M3, true>(e[2], e[3], ph);
+                pv[w] = ph;
+                int plo = 0;
+                if (two) plo = lo_terms(e, ph, 0);
+                pl[w] = plo;
+            }
+            l_run += ls;
+        }
+        // ---- O^T += V^T.P^T, row sums (V's one scale per (sequence, head) is applied in the epilogue; the low term's 2^-5 rides in the scale word)
+        o[0] = mfma_f8<FMT, QATTN_FMT_E4M3>(vf0, pv, o[0]);
+        o[1] = mfma_f8<FMT, QATTN_FMT_E4M3>(vf1, pv, o[1]);
+        if (!BYTE && two) {
+            o[0] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vf0, pl, o[0], kScaleWordOne);
+            o[1] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vf1, pl, o[1], kScaleWordOne);
+        }
+#pragma unroll
+        for (int m = 2; m < MB; m += 2) {
+            const v8i va = lds_read_frag(vbuf + (m << 11)), vb = lds_read_frag(vbuf + ((m + 1) << 11));
+            o[m] = mfma_f8<FMT, QATTN_FMT_E4M3>(va, pv, o[m]);
+            o[m + 1] = mfma_f8<FMT, QATTN_FMT_E4M3>(vb, pv, o[m + 1]);
+            if (!BYTE && two) {
+                o[m] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(va, pl, o[m], kScaleWordOne);
+                o[m + 1] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vb, pl, o[m + 1], kScaleWordOne);
+            }
+        }
+        if (BYTE) lsum = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ones, pv, lsum, QATTN_FMT_E4M3, QATTN_FMT_E4M3, 0, 0, 0, 0);
+    }
+
+    // ---- epilogue
+    float l_tot;
+    if (BYTE) {
+        const float s0l = __shfl(lsum[0], lane & 15), s1l = __shfl(lsum[1], lane & 15);
+        l_tot = (lane & 16) ? s1l : s0l;
+    } else {
+        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
+        l_tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+    }
+    const float inv = a.sv[(long)i * a.Hkv + kvh] / l_tot;
+    store_o_rows<MB>(a.out, a.out_fmt, o, inv, orow, hh, qvalid);
+    if (!BYTE && a.lse && hh == 0 && qvalid)  // ln sum_j exp(score_j) = ln2 * (m*c - shift) + ln(l')
+        a.lse[lrow] = 0.6931471805599453f * (m_run * c - kPShift) + __logf(l_tot);
+    if (a.path && hh == 0 && qvalid) a.path[lrow] = (unsigned char)((!BYTE && two) ? QATTN_PATH_TWO_TERM : QATTN_PATH_ONE_TERM);
+}
+
+// LDS of the attention kernel: the K / V ring and the parked Q^T fragments (D = 256: 96 KiB)
+constexpr int vfp_lds_bytes(int D) { return kVfpStages * 2 * 64 * D + kVfpWaves * kQPerWave * D; }
+static_assert(vfp_lds_bytes(256) <= 160 * 1024, "the ring and the Q slots fit a CU's LDS");
+
+template <int D, int FMT, bool BYTE, bool CAUSAL>
+static int launch_vfp_one(const VfpAttn& a, int two, int sel, hipStream_t st) {
+    constexpr int lds = vfp_lds_bytes(D);
+    auto kern = attn_vfp8_kernel<D, FMT, BYTE, CAUSAL>;
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return QATTN_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(a.Hq * a.nblk)), dim3(kVfpWaves * 64), lds, st, a, two, sel);
+    return QATTN_OK;
+}
+
+template <int D, int FMT, bool CAUSAL>
+static int launch_vfp_attn(const VfpAttn& a, int precision, hipStream_t st) {
+    if (precision == QATTN_PRECISION_ACCURATE || a.total_k < a.two_term_keys)   // (no tile can see two_term_keys keys: every one is two-term)
+        return launch_vfp_one<D, FMT, false, CAUSAL>(a, 1, kVfpSelAll, st);
+    // FAST: the tiles that see many keys on the one-term sweep (an LSE request: exact exponentials), the others two-term
+    int rc = a.lse ? launch_vfp_one<D, FMT, false, CAUSAL>(a, 0, kVfpSelMany, st) : launch_vfp_one<D, FMT, true, CAUSAL>(a, 0, kVfpSelMany, st);
+    if (rc == QATTN_OK) rc = launch_vfp_one<D, FMT, false, CAUSAL>(a, 1, kVfpSelFew, st);
+    return rc;
+}
+
+template <int D, int IN_FMT, int OUT_FMT>
+static int launch_vfp_d(const VfpQuant& qa, const VfpAttn& a, int numerics, int causal, int precision, hipStream_t st) {
+    int tmax = qa.total[0] > qa.total[1] ? qa.total[0] : qa.total[1];
+    int hmax = qa.H[0] > qa.H[1] ? qa.H[0] : qa.H[1];
+    hipLaunchKernelGGL((vfp_amax_kernel<D, IN_FMT>), dim3((unsigned)(qa.B + ceil_div(tmax, kVarlenAmaxRows)), hmax, 3), dim3(256), 0, st, qa);
+    hipLaunchKernelGGL((vfp_quant_kernel<D, IN_FMT, OUT_FMT>), dim3((unsigned)(qa.B + ceil_div(tmax, kVarlenQuantRows)), hmax, 3), dim3(256), 0, st, qa,
+                       numerics);
+    return causal ? launch_vfp_attn<D, OUT_FMT, true>(a, precision, st) : launch_vfp_attn<D, OUT_FMT, false>(a, precision, st);
+}
+template <int D>
+static int launch_vfp(const VfpQuant& qa, const VfpAttn& a, int in_fmt, int fp8_fmt, int numerics, int causal, int precision, hipStream_t st) {
+    if (in_fmt == QATTN_FMT_BF16)
+        return fp8_fmt == QATTN_FMT_E4M3 ? launch_vfp_d<D, QATTN_FMT_BF16, QATTN_FMT_E4M3>(qa, a, numerics, causal, precision, st)
+                                         : launch_vfp_d<D, QATTN_FMT_BF16, QATTN_FMT_E5M2>(qa, a, numerics, causal, precision, st);
+    return fp8_fmt == QATTN_FMT_E4M3 ? launch_vfp_d<D, QATTN_FMT_FP16, QATTN_FMT_E4M3>(qa, a, numerics, causal, precision, st)
+                                     : launch_vfp_d<D, QATTN_FMT_FP16, QATTN_FMT_E5M2>(qa, a, numerics, causal, precision, st);
+}
+
+}  // namespace qattn
+
+using namespace qattn;
+
+namespace {
+size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+// the VFRAG images take the room of the KFRAG images: a 64-key chunk is 64 D bytes in both layouts
+size_t vfp_v8_bytes(int B, int Hkv, int total_k, int D) { return qattn_varlen_tensor_bytes(QATTN_LAYOUT_KFRAG, B, Hkv, total_k, D); }
+bool vfp_dims_ok(int B, int Hq, int Hkv, int total_q, int total_k) { return B >= 1 && Hq > 0 && Hkv > 0 && total_q >= 0 && total_k >= 0; }
+}  // namespace
+
+extern "C" size_t qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes(int B, int Hq, int Hkv, int total_q, int total_k, int D) {
+    if (!vfp_dims_ok(B, Hq, Hkv, total_q, total_k) || (D != 64 && D != 128 && D != 256)) return 0;
+    // [q8 | k8 | v8 | scale_q, scale_k, scale_v | abs-max words of q, k, v]: the buffers only used where the caller passes none of its own
+    return up256(qattn_varlen_tensor_bytes(QATTN_LAYOUT_ROWMAJOR, B, Hq, total_q, D)) + up256(qattn_varlen_tensor_bytes(QATTN_LAYOUT_KFRAG, B, Hkv, total_k, D)) +
+           up256(vfp_v8_bytes(B, Hkv, total_k, D)) + 2 * up256(sizeof(float) * (size_t)B * (Hq + 2 * (size_t)Hkv));
+}
+
+extern "C" size_t qattn_fp8_quant_attention_varlen_fp8pv_smooth_workspace_bytes(int B, int Hq, int Hkv, int total_q, int total_k, int D) {
+    const size_t plain = qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes(B, Hq, Hkv, total_q, total_k, D);
+    // [the plain workspace | per-block channel sums of the mean pass]
+    return plain ? up256(plain) + varlen_smooth_k_workspace_bytes(B, Hkv, D) : 0;
+}
+
+extern "C" int qattn_fp8_quant_attention_varlen_forward_fp8pv(const void* q, const void* k, const void* v, const long long* strides, int in_fmt,
+                                                              void* out, float* lse, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                                                              const int* seqused_k, int B, int Hq, int Hkv, int total_q, int total_k, int D,
+                                                              int fp8_fmt, int numerics, int is_causal, float sm_scale, int precision, void* q8,
+                                                              void* k8, void* v8, float* scale_q, float* scale_k, float* scale_v,
+                                                              unsigned char* row_path, float* k_mean, void* workspace, size_t workspace_bytes,
+                                                              void* stream) {
+    if (!q || !k || !v || !out || !cu_seqlens_q || !cu_seqlens_k) return QATTN_ERR_INVALID_ARG;
+    if (!vfp_dims_ok(B, Hq, Hkv, total_q, total_k)) return QATTN_ERR_INVALID_ARG;
+    if ((D != 64 && D != 128 && D != 256) || Hq % Hkv != 0) return QATTN_ERR_UNSUPPORTED_DIM;
+    if (in_fmt != QATTN_FMT_BF16 && in_fmt != QATTN_FMT_FP16) return QATTN_ERR_UNSUPPORTED_FMT;
+    if (fp8_fmt != QATTN_FMT_E4M3 && fp8_fmt != QATTN_FMT_E5M2) return QATTN_ERR_UNSUPPORTED_FMT;
+    if (numerics != QATTN_NUMERICS_COMPILED && numerics != QATTN_NUMERICS_EAGER) return QATTN_ERR_INVALID_ARG;
+    if (precision != QATTN_PRECISION_FAST && precision != QATTN_PRECISION_ACCURATE) return QATTN_ERR_INVALID_ARG;
+    long long st6[6] = {(long long)Hq * D, D, (long long)Hkv * D, D, (long long)Hkv * D, D};   // dense [total, H, D]
+    if (strides)
+        for (int s = 0; s < 6; s++) {
+            if (strides[s] < 0 || strides[s] % 8 != 0) return QATTN_ERR_INVALID_ARG;
+            st6[s] = strides[s];
+        }
+    if (((size_t)q | (size_t)k | (size_t)v | (size_t)out) % 16 != 0) return QATTN_ERR_INVALID_ARG;
+    // grids: Hq (B + ceil(total_q / 128)) attention workgroups, B + ceil(total / 64) quantise tiles per head (32-bit dimensions)
+    if ((long long)Hq * (B + ceil_div(total_q, kVfpTile)) > 0x7fffffffLL || (long long)B + ceil_div(total_q > total_k ? total_q : total_k, 64) > 0x7fffffffLL)
+        return QATTN_ERR_INVALID_ARG;
+    const bool smooth = k_mean != nullptr;
+    if (smooth && (reinterpret_cast<uintptr_t>(k_mean) & 15u) != 0) return QATTN_ERR_INVALID_ARG;
+    const size_t plain_bytes = qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes(B, Hq, Hkv, total_q, total_k, D);
+    const size_t need = smooth ? qattn_fp8_quant_attention_varlen_fp8pv_smooth_workspace_bytes(B, Hq, Hkv, total_q, total_k, D) : plain_bytes;
+    if (!workspace || workspace_bytes < need) return QATTN_ERR_WORKSPACE;
+    if (total_q == 0) return QATTN_OK;   // no query row: nothing to compute or write
+    hipStream_t st = (hipStream_t)stream;
+    const size_t nq = (size_t)B * Hq, nk = (size_t)B * Hkv;
+    unsigned char* w = (unsigned char*)workspace;
+    unsigned char* q8w = w;   w += up256(qattn_varlen_tensor_bytes(QATTN_LAYOUT_ROWMAJOR, B, Hq, total_q, D));
+    unsigned char* k8w = w;   w += up256(qattn_varlen_tensor_bytes(QATTN_LAYOUT_KFRAG, B, Hkv, total_k, D));
+    unsigned char* v8w = w;   w += up256(vfp_v8_bytes(B, Hkv, total_k, D));
+    float* sw = (float*)w;    w += up256(sizeof(float) * (nq + 2 * nk));
+    unsigned* amax = (unsigned*)w;
+    VfpQuant qa;
+    qa.x[0] = (const unsigned char*)q; qa.x[1] = (const unsigned char*)k; qa.x[2] = (const unsigned char*)v;
+    for (int z = 0; z < 3; z++) { qa.ts[z] = st6[2 * z]; qa.hs[z] = st6[2 * z + 1]; }
+    qa.cu[0] = cu_seqlens_q; qa.cu[1] = cu_seqlens_k; qa.cu[2] = cu_seqlens_k; qa.used = seqused_k;
+    qa.total[0] = total_q; qa.total[1] = total_k; qa.total[2] = total_k;
+    qa.H[0] = Hq; qa.H[1] = Hkv; qa.H[2] = Hkv;
+    qa.B = B; qa.skip_k = smooth ? 1 : 0;
+    qa.amax[0] = amax; qa.amax[1] = amax + nq; qa.amax[2] = amax + nq + nk;
+    qa.x8[0] = q8 ? (unsigned char*)q8 : q8w; qa.x8[1] = k8 ? (unsigned char*)k8 : k8w; qa.x8[2] = v8 ? (unsigned char*)v8 : v8w;
+    qa.scale[0] = scale_q ? scale_q : sw; qa.scale[1] = scale_k ? scale_k : sw + nq; qa.scale[2] = scale_v ? scale_v : sw + nq + nk;
+    VfpAttn a;
+    a.q8 = qa.x8[0]; a.k8 = qa.x8[1]; a.v8 = qa.x8[2];
+    a.out = out; a.lse = lse; a.path = row_path;
+    a.sq = qa.scale[0]; a.sk = qa.scale[1]; a.sv = qa.scale[2];
+    a.cu_q = cu_seqlens_q; a.cu_k = cu_seqlens_k; a.used = seqused_k;
+    a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.total_q = total_q; a.total_k = total_k;
+    a.nblk = B + ceil_div(total_q, kVfpTile);
+    a.out_fmt = in_fmt;
+    a.xcd_remap = (Hq % 8 == 0 && xcd_count() == 8) ? 1 : 0;   // (the XCD-contiguous map assumes 8 XCDs; a speed assumption only)
+    a.two_term_keys = kTwoTermKeys;
+    const float sm = sm_scale > 0.0f ? sm_scale : 1.0f / sqrtf((float)D);
+    a.sm_log2e = sm * 1.4426950408889634f;
+    if (zero_words(amax, (long)(nq + 2 * nk), st) != hipSuccess) return QATTN_ERR_LAUNCH;
+    int rc;
+    if (smooth) {   // K first, in launches of its own (mean, abs-max, quantise on k - mean), then q and v through the plain two
+        rc = launch_varlen_smooth_k(k, (long)st6[2], (long)st6[3], in_fmt, cu_seqlens_k, seqused_k, B, Hkv, total_k, D, fp8_fmt, numerics, qa.x8[1],
+                                    qa.scale[1], k_mean, qa.amax[1], reinterpret_cast<float*>((unsigned char*)workspace + up256(plain_bytes)), st);
+        if (rc != QATTN_OK) return rc;
+    }
+    if (D == 64) rc = launch_vfp<64>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, precision, st);
+    else if (D == 128) rc = launch_vfp<128>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, precision, st);
+    else rc = launch_vfp<256>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, precision, st);
+    if (rc != QATTN_OK) return rc;
+    if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
+    if (!smooth || !lse) return QATTN_OK;
+    // the launch wrote the LSE of the smoothed scores; the true scores of a row lie sm_scale * q.m higher (-inf rows stay -inf)
+    return launch_varlen_smooth_lse(q, (long)st6[0], (long)st6[1], in_fmt, cu_seqlens_q, k_mean, lse, B, Hq, Hkv, total_q, D, sm, st);
+}

@@ -144,6 +144,88 @@ def fp8_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
     return (out, lse) if return_lse else out
 
 
+# ---- FP8 P.V on the packed call shape (include/qattn_varlen.h: qattn_fp8_quant_attention_varlen_forward_fp8pv) ---------------------------
+def _varlen_eager_fp8pv(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, causal, return_lse, smooth_k=False):
+    """config.attention.force_eager_fallback with pv_precision="fp8": `_varlen_eager`'s per-sequence loop with V restated -- the eager
+    quantiser per sequence and head on q, on the USED keys (smooth_k: on fp32(k) - their fp32 mean) and on the V of the used keys, all
+    three de-quantised, then fp32 attention (top-left causal mask) and the log-sum-exp of the same scores, corrected by scale * q.m under
+    smooth_k.  P stays fp32: both precisions of the kernel are within the fp8-V bound of this definition."""
+    fp8_dtype = nn._fp8_dtype()
+    total_q, Hq, D = q.shape
+    scale = 1.0 / math.sqrt(D) if softmax_scale is None else float(softmax_scale)
+    cq, ck = cu_seqlens_q.tolist(), cu_seqlens_k.tolist()
+    used = None if seqused_k is None else seqused_k.tolist()
+    out = torch.zeros((total_q, Hq, D), dtype=q.dtype, device=q.device)
+    lse = torch.full((Hq, total_q), -math.inf, dtype=torch.float32, device=q.device)
+    for i in range(len(cq) - 1):
+        lq = cq[i + 1] - cq[i]
+        lk = ck[i + 1] - ck[i] if used is None else min(used[i], ck[i + 1] - ck[i])
+        if lq <= 0 or lk <= 0:
+            continue   # (no key: zero rows, LSE -inf)
+        qi = q[cq[i]:cq[i + 1]].transpose(0, 1)[None]
+        ki, vi = (t[ck[i]:ck[i] + lk].transpose(0, 1)[None] for t in (k, v))
+        q8, sq = nn._dynamically_quantize_fp8(qi, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+        mean = None
+        if smooth_k:
+            ki = ki.to(torch.float32)
+            mean = ki.mean(dim=-2, keepdim=True)   # [1, Hkv, 1, D]
+            ki = ki - mean
+        k8, sk = nn._dynamically_quantize_fp8(ki, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+        v8, sv = nn._dynamically_quantize_fp8(vi, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+        dq = q8.float() * sq[..., None, None]
+        dk = nn._expand_kv_heads(k8.float() * sk[..., None, None], Hq)
+        dv = nn._expand_kv_heads(v8.float() * sv[..., None, None], Hq)
+        s = (dq @ dk.transpose(-1, -2)) * scale
+        if causal:
+            s = s.masked_fill(torch.ones(lq, lk, dtype=torch.bool, device=q.device).triu(1), -math.inf)
+        l = torch.logsumexp(s[0], dim=-1)
+        out[cq[i]:cq[i + 1]] = (torch.exp(s[0] - l[..., None]) @ dv[0]).to(q.dtype).transpose(0, 1)
+        if smooth_k:
+            l = l + scale * (qi[0].to(torch.float32) * nn._expand_kv_heads(mean, Hq)[0]).sum(-1)
+        lse[:, cq[i]:cq[i + 1]] = l
+    return (out, lse) if return_lse else out
+
+
+def fp8_attn_varlen_pv_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None, causal=False,
+                            *, seqused_k=None, return_lse=False, pv_precision="16bit", precision="accurate"):
+    """fp8_attn_varlen_func with the P.V path as an explicit argument (same tensors, tables, results and config flags; a sibling function:
+    fp8_attn_varlen_func keeps the signature it was released with).
+    pv_precision "16bit" (default): exactly fp8_attn_varlen_func, bit for bit; `precision` must then be "accurate".
+    pv_precision "fp8": both products on the FP8 matrix pipe.  Every sequence's V is quantised head-wise over its USED keys alone (the
+    bytes and scale of the quant pre-pass on v_i[:used]; V must be finite there, and keys beyond seqused_k still influence no output
+    bit), P is e4m3: precision "accurate" = exact exponentials and two-term (hi + lo) P on every row; "fast" = the one-term
+    byte-exponential sweep for the 128-row tiles whose rows see n >= 1024 keys (n = used L_k, or min(L_k, 128 (t + 1)) for tile t when
+    causal), two-term below, and exact exponentials on the one-term tiles when the LSE is asked for.  "fast" has no rescue pass and is
+    stated for score variance softmax_scale^2 D <= 1.  Any other value of either argument -- "auto" included -- raises ValueError.
+    config.attention.pv_precision / precision do not apply; fp8_format, quant_numerics, smooth_k, skip_supported_check and
+    force_eager_fallback are followed as by fp8_attn_varlen_func."""
+    if pv_precision not in ("16bit", "fp8"):
+        raise ValueError(f"Unsupported pv_precision: {pv_precision!r} (expected '16bit' or 'fp8')")
+    if pv_precision == "16bit":
+        if precision != "accurate":
+            raise ValueError(f"Unsupported precision for pv_precision='16bit': {precision!r} (the 16-bit P.V path has one precision, 'accurate')")
+        return fp8_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal,
+                                    seqused_k=seqused_k, return_lse=return_lse)
+    if precision not in ("accurate", "fast"):
+        raise ValueError(f"Unsupported precision for pv_precision='fp8': {precision!r} (expected 'accurate' or 'fast'; 'auto' is not offered "
+                         "by the packed entry)")
+    smooth_k = bool(checks.config_value("attention.smooth_k"))
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = varlen_input_reason(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, seqused_k)
+        if reason is None:
+            ok, reason = nn._pre_check_can_use_hip_attention(device=q.device)
+            reason = None if ok else reason
+        if reason:
+            raise ValueError(reason)
+    if checks.config_value("attention.force_eager_fallback") and not torch.compiler.is_dynamo_compiling():
+        return _varlen_eager_fp8pv(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, causal, return_lse, smooth_k)
+    out, lse = nn._ops().fp8_varlen_attention_forward_fp8pv(
+        q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal),
+        checks.config_value("attention.fp8_format"), checks.config_value("attention.quant_numerics"), bool(return_lse), smooth_k, precision,
+        scale=softmax_scale)
+    return (out, lse) if return_lse else out
+
+
 # ---- sliding-window (local) attention: flash-attn's window_size on the packed call shape (include/qattn_window.h) --------------------
 def window_size_reason(window_size) -> Optional[str]:
     """The rule a `window_size` breaks, or None: a pair (left, right) of host ints >= -1 (-1: unbounded on that side)."""

@@ -8,6 +8,9 @@ Step times are HIP events around blocks of `--iters` back-to-back steps, the can
 `rocprofv3 --kernel-trace --stats` (the attention kernels: attn_pv16_varlen_kernel, attn_pv16_kernel).  --cases picks the workloads:
   equal    4 x 4096, H 32, D 128, non-causal (the README's dense 16-bit-V step shape)
   mixed    32 sequences drawn from 256 .. 4096 tokens (seed 0), H 24, D 128, causal and non-causal
+--pv fp8 --precision fast|accurate: the FP8-PV mode (fp8_attn_varlen_pv_func(..., pv_precision="fp8"), attention kernel attn_vfp8_kernel)
+instead, interleaved with the 16-bit-PV packed entry in the same run and -- on equal lengths -- with the dense fused call
+fp8_attn_func on 16-bit inputs under config.attention.precision = "fast".  Only same-run ratios count.
 Prints one JSON line per case; FLOPs follow bench.py (4 Sq Skv D per head, halved for causal), the attention fraction is against bench.py's
 FP8_PEAK_TFLOPS."""
 import argparse
@@ -27,7 +30,7 @@ from quantumattention_amd import _native  # noqa: E402
 FP8_PEAK_TFLOPS = 5000.0   # bench.py
 
 
-def step_ms(fns, iters, rounds=5, warmup=3):
+def step_ms(fns, iters, rounds=5, warmup=3, pick=None):
     """ms per step of each of `fns`: blocks of `iters` steps, the candidates interleaved block by block over `rounds` rounds (clock and
     thermal drift hit all of them alike), median over the rounds"""
     for fn in fns:
@@ -44,11 +47,44 @@ def step_ms(fns, iters, rounds=5, warmup=3):
             e1.record()
             laps[i].append((e0, e1))
     torch.cuda.synchronize()
-    return [sorted(a.elapsed_time(b) / iters for a, b in lap)[rounds // 2] for lap in laps]
+    pick = pick or (lambda xs: sorted(xs)[rounds // 2])
+    return [pick([a.elapsed_time(b) / iters for a, b in lap]) for lap in laps]
 
 
 def flops(lens_q, lens_k, H, D, causal):
     return sum(4.0 * H * a * b * D * (0.5 if causal else 1.0) for a, b in zip(lens_q, lens_k))
+
+
+def run_case_fp8pv(name, lens, H, D, causal, iters, precision, dense=False):
+    """the FP8-PV packed call against the 16-bit-PV packed call (and the dense fused FAST call on equal lengths): medians and minima"""
+    torch.manual_seed(0)
+    total = int(sum(lens))
+    q, k, v = (torch.randn(total, H, D, dtype=torch.bfloat16, device="cuda") for _ in range(3))
+    cu = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32, device="cuda")
+    fns = {"varlen16": lambda: qa.fp8_attn_varlen_func(q, k, v, cu, cu, max(lens), max(lens), causal=causal),
+           "varlen_fp8": lambda: qa.fp8_attn_varlen_pv_func(q, k, v, cu, cu, max(lens), max(lens), causal=causal, pv_precision="fp8",
+                                                            precision=precision)}
+    if dense:
+        B, S = len(lens), lens[0]
+        qd, kd, vd = (t.view(B, S, H, D).transpose(1, 2) for t in (q, k, v))   # (strided views: read in place)
+
+        def dense_fast():
+            with qa.config.patch({"attention.precision": "fast"}):
+                return qa.fp8_attn_func(qd, kd, vd, is_causal=causal)
+
+        fns["dense_fast"] = dense_fast
+    f = flops(lens, lens, H, D, causal)
+    res = {"case": name, "pv": "fp8", "precision": precision, "B": len(lens), "H": H, "D": D, "causal": causal, "total_tokens": total, "flops": f}
+    names = list(fns)
+    med = step_ms([fns[n] for n in names], iters, rounds=7)
+    low = step_ms([fns[n] for n in names], iters, rounds=7, pick=min)
+    for n, a, b in zip(names, med, low):
+        res[n + "_ms"], res[n + "_min_ms"] = a, b
+    res["fp8_over_16bit"] = res["varlen_fp8_ms"] / res["varlen16_ms"]
+    if dense:
+        res["fp8_over_dense_fast"] = res["varlen_fp8_ms"] / res["dense_fast_ms"]
+    res["varlen_fp8_step_TFLOPs"] = f / (res["varlen_fp8_ms"] * 1e-3) / 1e12
+    return res
 
 
 def run_case(name, lens, H, D, causal, iters, dense=False):
@@ -95,9 +131,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="equal,mixed")
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--pv", default="16bit", choices=["16bit", "fp8"])
+    ap.add_argument("--precision", default="fast", choices=["fast", "accurate"])
     args = ap.parse_args()
     assert _native.lib().qattn_check_device() == 0, "needs the MI355X"
     cases = args.cases.split(",")
+    if args.pv == "fp8":
+        if "equal" in cases:
+            print(json.dumps(run_case_fp8pv("equal", [4096] * 4, 32, 128, False, args.iters, args.precision, dense=True)), flush=True)
+        if "mixed" in cases:
+            lens = [int(x) for x in np.random.default_rng(0).integers(256, 4097, size=32)]
+            for causal in (False, True):
+                print(json.dumps(run_case_fp8pv("mixed", lens, 24, 128, causal, args.iters, args.precision)), flush=True)
+        return
     if "equal" in cases:
         print(json.dumps(run_case("equal", [4096] * 4, 32, 128, False, args.iters, dense=True)), flush=True)
     if "mixed" in cases:
