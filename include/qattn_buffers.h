@@ -27,6 +27,13 @@
  *   row_path   uint8 [Hq, total_q], 1-byte aligned; written: the columns cu_q[i] .. cu_q[i+1]-1 of every sequence, the others keep what they held.
  *   k_mean     fp32 [B, Hkv, D], 16-byte aligned; every element written (as the _smooth entry).
  *   workspace  ..._fp8pv_workspace_bytes (with k_mean: ..._fp8pv_smooth_workspace_bytes) bytes, 16-byte aligned; no result depends on what it held.
+ *
+ * qattn_fp8_quant_attention_varlen_window_forward_fp8pv (qattn_window.h): every line of qattn_fp8_quant_attention_varlen_forward_fp8pv above --
+ *   q8 / k8 / v8 / scale_q / scale_k / scale_v / k_mean  the same sizes, alignments and written bytes: the pre-pass is that entry's and covers ALL
+ *              used keys, whatever the window leaves out.
+ *   out / lse / row_path  every row of every sequence is written, rows whose window holds no key included (zeros / -inf / the tile's code).
+ *   workspace  qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes (with k_mean: ..._fp8pv_smooth_workspace_bytes) bytes -- the packed
+ *              FP8-PV entry's own two functions, there is no third --, 16-byte aligned; no result depends on what it held.
  */
 #ifndef QATTN_BUFFERS_H_
 #define QATTN_BUFFERS_H_

@@ -26,6 +26,9 @@ from .varlen import fp8_attn_varlen_pv_func  # noqa: E402
 # sliding-window (local) attention, packed and dense call shapes: package attributes too, not in __all__
 from .varlen import fp8_attn_varlen_window_func, fp8_window_attn_func  # noqa: E402
 
+# ... with the P.V path as an argument (pv_precision="fp8"): package attributes too, not in __all__
+from .varlen import fp8_attn_varlen_window_pv_func, fp8_window_attn_pv_func  # noqa: E402
+
 # block-sparse attention over 128 x 128 tiles of a boolean block mask: package attributes too, not in __all__
 from .block_sparse import BLOCK_M, BLOCK_N, fp8_block_sparse_attn_func, fp8_block_sparse_attn_pv_func  # noqa: E402
 

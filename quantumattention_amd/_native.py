@@ -47,6 +47,7 @@ EXPORTS = (
     "qattn_fp8_block_sparse_attention_forward_fp8pv",
     "qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes", "qattn_fp8_quant_attention_varlen_fp8pv_smooth_workspace_bytes",
     "qattn_fp8_quant_attention_varlen_forward_fp8pv",
+    "qattn_fp8_quant_attention_varlen_window_forward_fp8pv",
 )
 BLOCK_SPARSE_BLOCK = 128   # QATTN_BLOCK_SPARSE_BLOCK (include/qattn_block_sparse.h): rows / keys per mask block
 
@@ -194,6 +195,11 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_quant_attention_varlen_forward_fp8pv.restype = i
     L.qattn_fp8_quant_attention_varlen_forward_fp8pv.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f, i,
                                                                  vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    # the sliding-window entry with FP8 P.V (include/qattn_window.h): the packed FP8-PV entry's arguments with (window_left, window_right)
+    # for is_causal; its workspace is sized by the two packed FP8-PV functions above
+    L.qattn_fp8_quant_attention_varlen_window_forward_fp8pv.restype = i
+    L.qattn_fp8_quant_attention_varlen_window_forward_fp8pv.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, f, i,
+                                                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -696,18 +702,10 @@ def fp8_quant_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) + ((k_mean,) if smooth_k else ()) if return_quant else ())
 
 
-def fp8_quant_attention_varlen_fp8pv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,
-                                     seqused_k: Optional[torch.Tensor] = None, *, is_causal: bool = False, fp8_dtype=torch.float8_e4m3fn,
-                                     numerics: str = "compiled", sm_scale: float = 0.0, precision: str = "accurate", return_lse: bool = False,
-                                     return_quant: bool = False, return_path: bool = False, smooth_k: bool = False):
-    """Packed variable-length sequences with FP8 P.V (qattn_fp8_quant_attention_varlen_forward_fp8pv, include/qattn_varlen.h): the arguments
-    of `fp8_quant_attention_varlen`; every sequence's v is quantised head-wise over its used keys (finite there), precision "accurate"
-    (two-term e4m3 P everywhere) or "fast" (one-term byte-exponential P for the 128-row tiles whose rows see >= 1024 keys).
-    return_quant (test output): also (q8, k8, v8, scale_q, scale_k, scale_v) -- q8 the row-major per-sequence slabs (uint8, Hq D cu_q[i]
-    bytes in), k8 / v8 the KFRAG / VFRAG images (Hkv D (cu_k[i] + 64 i) bytes in), scales fp32 [B, H] -- and, with smooth_k, k_mean fp32
-    [B, Hkv, D]; return_path: also row_path uint8 [Hq, total_q] (PATH_*; columns of no sequence keep what the buffer held).
-    Returns out, or a tuple of out, [lse], [q8, k8, v8, scale_q, scale_k, scale_v, [k_mean]], [row_path]."""
-    _require(precision in ("fast", "accurate"), f"Unsupported precision for the packed FP8 P.V path: {precision!r} (expected 'fast' or 'accurate')")
+def _varlen_fp8pv(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, is_causal, window, fp8_dtype, numerics, sm_scale, precision, return_lse,
+                  return_quant, return_path, smooth_k):
+    """The two packed FP8-PV entries through one body: window None -> qattn_fp8_quant_attention_varlen_forward_fp8pv under is_causal,
+    (left, right) -> qattn_fp8_quant_attention_varlen_window_forward_fp8pv.  Same buffers, same workspace functions, same results."""
     q, k, v = (t if varlen_strided_ok(t) else t.contiguous() for t in (q, k, v))
     total_q, Hq, D = q.shape
     total_k, Hkv = k.shape[0], k.shape[1]
@@ -737,16 +735,35 @@ def fp8_quant_attention_varlen_fp8pv(q: torch.Tensor, k: torch.Tensor, v: torch.
                  else L.qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes)
         ws_bytes = ws_of(B, Hq, Hkv, total_q, total_k, D)
         ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
-        rc = L.qattn_fp8_quant_attention_varlen_forward_fp8pv(
+        entry = L.qattn_fp8_quant_attention_varlen_forward_fp8pv if window is None else L.qattn_fp8_quant_attention_varlen_window_forward_fp8pv
+        i32max = 2 ** 31 - 1
+        mask = (int(is_causal),) if window is None else (min(int(window[0]), i32max), min(int(window[1]), i32max))
+        rc = entry(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), strides, fmt_of(q.dtype), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(),
-            cu_seqlens_k.data_ptr(), _ptr(seqused_k), B, Hq, Hkv, total_q, total_k, D, fmt_of(fp8_dtype), _numerics(numerics), int(is_causal),
+            cu_seqlens_k.data_ptr(), _ptr(seqused_k), B, Hq, Hkv, total_q, total_k, D, fmt_of(fp8_dtype), _numerics(numerics), *mask,
             float(sm_scale), _precision(precision), _ptr(q8), _ptr(k8), _ptr(v8), _ptr(sq), _ptr(sk), _ptr(sv), _ptr(path), _ptr(k_mean),
             ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_quant_attention_varlen_forward_fp8pv")
+    _check(rc, "qattn_fp8_quant_attention_varlen_forward_fp8pv" if window is None else "qattn_fp8_quant_attention_varlen_window_forward_fp8pv")
     if not (return_lse or return_quant or return_path):
         return out
     return ((out,) + ((lse,) if return_lse else ()) + ((q8, k8, v8, sq, sk, sv) + ((k_mean,) if smooth_k else ()) if return_quant else ())
             + ((path,) if return_path else ()))
+
+
+def fp8_quant_attention_varlen_fp8pv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,
+                                     seqused_k: Optional[torch.Tensor] = None, *, is_causal: bool = False, fp8_dtype=torch.float8_e4m3fn,
+                                     numerics: str = "compiled", sm_scale: float = 0.0, precision: str = "accurate", return_lse: bool = False,
+                                     return_quant: bool = False, return_path: bool = False, smooth_k: bool = False):
+    """Packed variable-length sequences with FP8 P.V (qattn_fp8_quant_attention_varlen_forward_fp8pv, include/qattn_varlen.h): the arguments
+    of `fp8_quant_attention_varlen`; every sequence's v is quantised head-wise over its used keys (finite there), precision "accurate"
+    (two-term e4m3 P everywhere) or "fast" (one-term byte-exponential P for the 128-row tiles whose rows see >= 1024 keys).
+    return_quant (test output): also (q8, k8, v8, scale_q, scale_k, scale_v) -- q8 the row-major per-sequence slabs (uint8, Hq D cu_q[i]
+    bytes in), k8 / v8 the KFRAG / VFRAG images (Hkv D (cu_k[i] + 64 i) bytes in), scales fp32 [B, H] -- and, with smooth_k, k_mean fp32
+    [B, Hkv, D]; return_path: also row_path uint8 [Hq, total_q] (PATH_*; columns of no sequence keep what the buffer held).
+    Returns out, or a tuple of out, [lse], [q8, k8, v8, scale_q, scale_k, scale_v, [k_mean]], [row_path]."""
+    _require(precision in ("fast", "accurate"), f"Unsupported precision for the packed FP8 P.V path: {precision!r} (expected 'fast' or 'accurate')")
+    return _varlen_fp8pv(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, is_causal, None, fp8_dtype, numerics, sm_scale, precision, return_lse,
+                         return_quant, return_path, smooth_k)
 
 
 def fp8_quant_attention_varlen_window(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,
@@ -792,6 +809,22 @@ def fp8_quant_attention_varlen_window(q: torch.Tensor, k: torch.Tensor, v: torch
     if not (return_lse or return_quant):
         return out
     return (out,) + ((lse,) if return_lse else ()) + ((q8, k8, sq, sk) + ((k_mean,) if smooth_k else ()) if return_quant else ())
+
+
+def fp8_quant_attention_varlen_window_fp8pv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor,
+                                            cu_seqlens_k: torch.Tensor, seqused_k: Optional[torch.Tensor] = None, *, window_left: int = -1,
+                                            window_right: int = -1, fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled",
+                                            sm_scale: float = 0.0, precision: str = "accurate", return_lse: bool = False,
+                                            return_quant: bool = False, return_path: bool = False, smooth_k: bool = False):
+    """Sliding-window attention on packed sequences with FP8 P.V (qattn_fp8_quant_attention_varlen_window_forward_fp8pv,
+    include/qattn_window.h): the arguments and results of `fp8_quant_attention_varlen_fp8pv` with (window_left, window_right) -- host ints
+    >= -1, -1 = unbounded -- in place of is_causal.  Row r of a sequence attends keys r + delta - window_left .. r + delta + window_right,
+    delta = L_k(used) - L_q; precision "fast" runs the one-term sweep on the 128-row tiles whose rows attend an interval of >= 1024 keys.
+    Returns out, or a tuple of out, [lse], [q8, k8, v8, scale_q, scale_k, scale_v, [k_mean]], [row_path]."""
+    _require(int(window_left) >= -1 and int(window_right) >= -1, "window_left and window_right must be >= -1")
+    _require(precision in ("fast", "accurate"), f"Unsupported precision for the sliding-window FP8 P.V path: {precision!r} (expected 'fast' or 'accurate')")
+    return _varlen_fp8pv(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, False, (window_left, window_right), fp8_dtype, numerics, sm_scale,
+                         precision, return_lse, return_quant, return_path, smooth_k)
 
 
 def fp8_block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask: torch.Tensor, *, fp8_dtype=torch.float8_e4m3fn,

@@ -15,16 +15,13 @@
 //          belongs to the other launch returns before any DMA or barrier.  With total_k < kTwoTermKeys no tile can be one-term: one launch.
 //
 // Block -> (sequence, tile): qattn_varlen_tile.h with R = 128.
-#include "qattn_attn.h"
+// What the sliding-window unit (qattn_varlen_window_fp8.hip) shares with this one is in qattn_varlen_fp8.h; the body of the entry below
+// (varlen_fp8pv_forward_impl) runs that unit's attention launch behind this unit's pre-pass when it is given a window.
+#include "qattn_varlen_fp8.h"
 #include "qattn_varlen_tile.h"
 #include "../../include/qattn_varlen.h"
 
 namespace qattn {
-
-constexpr int kVfpTile = 128;   // query rows per workgroup
-constexpr int kVfpWaves = 4;
-constexpr int kVfpStages = 2;
-static_assert(kVfpTile == kVfpWaves * kQPerWave && kVfpTile == 2 * 64, "a workgroup is one 128-row tile; its diagonal spans two 64-key chunks");
 
 // q (z = 0), k (z = 1) and v (z = 2) of one call
 struct VfpQuant {
@@ -144,41 +141,6 @@ __global__ __launch_bounds__(256) void vfp_quant_kernel(const VfpQuant a, int nu
     __syncthreads();
     for (int i = tid; i < 64 * D / 16; i += 256) og[i] = reinterpret_cast<const uint4*>(img)[i];
 }
-
-// the attention launch's arguments
-struct VfpAttn {
-    const unsigned char* q8;   // row-major slabs
-    const unsigned char* k8;   // KFRAG images
-    const unsigned char* v8;   // VFRAG images, laid out like k8's
-    void* out;                 // dense [total_q, Hq, D]
-    float* lse;                // [Hq, total_q] or nullptr
-    unsigned char* path;       // [Hq, total_q] or nullptr
-    const float* sq;           // [B, Hq]
-    const float* sk;           // [B, Hkv]
-    const float* sv;           // [B, Hkv]
-    const int *cu_q, *cu_k, *used;
-    int B, Hq, Hkv, total_q, total_k, nblk, out_fmt, xcd_remap, two_term_keys;
-    float sm_log2e;
-};
-
-// LIGHT = the byte-exponential kernel (the lean register budget); the exact / two-term variants get one wave per SIMD less
-// (BsfShape of qattn_block_sparse_fp8.hip)
-template <int D, bool LIGHT> struct VfpShape {
-    static constexpr int WPS = D == 256 ? 2 : (D == 64 ? (LIGHT ? 4 : 3) : (LIGHT ? 3 : 2));
-};
-
-// 4 scores -> 4 e4m3 bytes of 2^x (byte_exp4 of qattn_attn_v4.hip)
-__device__ __forceinline__ int vfp_byte_exp4(float s0, float s1, float s2, float s3, float c8, float off8) {
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-    const us2 qa = __builtin_amdgcn_cvt_pknorm_u16(__builtin_fmaf(s0, c8, off8), __builtin_fmaf(s1, c8, off8));
-    const us2 qb = __builtin_amdgcn_cvt_pknorm_u16(__builtin_fmaf(s2, c8, off8), __builtin_fmaf(s3, c8, off8));
-    unsigned ua, ub;
-    __builtin_memcpy(&ua, &qa, 4);
-    __builtin_memcpy(&ub, &qb, 4);
-    return (int)__builtin_amdgcn_perm(ub, ua, 0x06040200u);
-}
-
-constexpr int kVfpSelAll = 0, kVfpSelMany = 1, kVfpSelFew = 2;   // which tiles a launch attends: all / rows see >= two_term_keys keys / fewer
 
 // BYTE: byte-exponential P + matrix-pipe row sums.  !BYTE: exact v_exp_f32, RNE e4m3, fp32 row sums (LSE output) and -- `two` -- the
 // hi + lo two-term P.  The sweep and the epilogue are attn_bs_fp8_kernel's, operation for operation: a non-causal sequence comes out
@@ -407,10 +369,6 @@ void attn_vfp8_kernel(const VfpAttn a, const int two, const int sel) {
     if (a.path && hh == 0 && qvalid) a.path[lrow] = (unsigned char)((!BYTE && two) ? QATTN_PATH_TWO_TERM : QATTN_PATH_ONE_TERM);
 }
 
-// LDS of the attention kernel: the K / V ring and the parked Q^T fragments (D = 256: 96 KiB)
-constexpr int vfp_lds_bytes(int D) { return kVfpStages * 2 * 64 * D + kVfpWaves * kQPerWave * D; }
-static_assert(vfp_lds_bytes(256) <= 160 * 1024, "the ring and the Q slots fit a CU's LDS");
-
 template <int D, int FMT, bool BYTE, bool CAUSAL>
 static int launch_vfp_one(const VfpAttn& a, int two, int sel, hipStream_t st) {
     constexpr int lds = vfp_lds_bytes(D);
@@ -431,21 +389,23 @@ static int launch_vfp_attn(const VfpAttn& a, int precision, hipStream_t st) {
 }
 
 template <int D, int IN_FMT, int OUT_FMT>
-static int launch_vfp_d(const VfpQuant& qa, const VfpAttn& a, int numerics, int causal, int precision, hipStream_t st) {
+static int launch_vfp_d(const VfpQuant& qa, const VfpAttn& a, int numerics, int causal, int precision, const int* window, hipStream_t st) {
     int tmax = qa.total[0] > qa.total[1] ? qa.total[0] : qa.total[1];
     int hmax = qa.H[0] > qa.H[1] ? qa.H[0] : qa.H[1];
     hipLaunchKernelGGL((vfp_amax_kernel<D, IN_FMT>), dim3((unsigned)(qa.B + ceil_div(tmax, kVarlenAmaxRows)), hmax, 3), dim3(256), 0, st, qa);
     hipLaunchKernelGGL((vfp_quant_kernel<D, IN_FMT, OUT_FMT>), dim3((unsigned)(qa.B + ceil_div(tmax, kVarlenQuantRows)), hmax, 3), dim3(256), 0, st, qa,
                        numerics);
+    if (window) return launch_varlen_window_fp8_attn(a, D, OUT_FMT, precision, window[0], window[1], st);   // (qattn_varlen_window_fp8.hip)
     return causal ? launch_vfp_attn<D, OUT_FMT, true>(a, precision, st) : launch_vfp_attn<D, OUT_FMT, false>(a, precision, st);
 }
 template <int D>
-static int launch_vfp(const VfpQuant& qa, const VfpAttn& a, int in_fmt, int fp8_fmt, int numerics, int causal, int precision, hipStream_t st) {
+static int launch_vfp(const VfpQuant& qa, const VfpAttn& a, int in_fmt, int fp8_fmt, int numerics, int causal, int precision, const int* window,
+                      hipStream_t st) {
     if (in_fmt == QATTN_FMT_BF16)
-        return fp8_fmt == QATTN_FMT_E4M3 ? launch_vfp_d<D, QATTN_FMT_BF16, QATTN_FMT_E4M3>(qa, a, numerics, causal, precision, st)
-                                         : launch_vfp_d<D, QATTN_FMT_BF16, QATTN_FMT_E5M2>(qa, a, numerics, causal, precision, st);
-    return fp8_fmt == QATTN_FMT_E4M3 ? launch_vfp_d<D, QATTN_FMT_FP16, QATTN_FMT_E4M3>(qa, a, numerics, causal, precision, st)
-                                     : launch_vfp_d<D, QATTN_FMT_FP16, QATTN_FMT_E5M2>(qa, a, numerics, causal, precision, st);
+        return fp8_fmt == QATTN_FMT_E4M3 ? launch_vfp_d<D, QATTN_FMT_BF16, QATTN_FMT_E4M3>(qa, a, numerics, causal, precision, window, st)
+                                         : launch_vfp_d<D, QATTN_FMT_BF16, QATTN_FMT_E5M2>(qa, a, numerics, causal, precision, window, st);
+    return fp8_fmt == QATTN_FMT_E4M3 ? launch_vfp_d<D, QATTN_FMT_FP16, QATTN_FMT_E4M3>(qa, a, numerics, causal, precision, window, st)
+                                     : launch_vfp_d<D, QATTN_FMT_FP16, QATTN_FMT_E5M2>(qa, a, numerics, causal, precision, window, st);
 }
 
 }  // namespace qattn
@@ -472,13 +432,11 @@ extern "C" size_t qattn_fp8_quant_attention_varlen_fp8pv_smooth_workspace_bytes(
     return plain ? up256(plain) + varlen_smooth_k_workspace_bytes(B, Hkv, D) : 0;
 }
 
-extern "C" int qattn_fp8_quant_attention_varlen_forward_fp8pv(const void* q, const void* k, const void* v, const long long* strides, int in_fmt,
-                                                              void* out, float* lse, const int* cu_seqlens_q, const int* cu_seqlens_k,
-                                                              const int* seqused_k, int B, int Hq, int Hkv, int total_q, int total_k, int D,
-                                                              int fp8_fmt, int numerics, int is_causal, float sm_scale, int precision, void* q8,
-                                                              void* k8, void* v8, float* scale_q, float* scale_k, float* scale_v,
-                                                              unsigned char* row_path, float* k_mean, void* workspace, size_t workspace_bytes,
-                                                              void* stream) {
+int qattn::varlen_fp8pv_forward_impl(const void* q, const void* k, const void* v, const long long* strides, int in_fmt, void* out, float* lse,
+                                     const int* cu_seqlens_q, const int* cu_seqlens_k, const int* seqused_k, int B, int Hq, int Hkv, int total_q,
+                                     int total_k, int D, int fp8_fmt, int numerics, int is_causal, float sm_scale, int precision, void* q8,
+                                     void* k8, void* v8, float* scale_q, float* scale_k, float* scale_v, unsigned char* row_path, float* k_mean,
+                                     void* workspace, size_t workspace_bytes, void* stream, const int* window) {
     if (!q || !k || !v || !out || !cu_seqlens_q || !cu_seqlens_k) return QATTN_ERR_INVALID_ARG;
     if (!vfp_dims_ok(B, Hq, Hkv, total_q, total_k)) return QATTN_ERR_INVALID_ARG;
     if ((D != 64 && D != 128 && D != 256) || Hq % Hkv != 0) return QATTN_ERR_UNSUPPORTED_DIM;
@@ -539,12 +497,24 @@ extern "C" int qattn_fp8_quant_attention_varlen_forward_fp8pv(const void* q, con
                                     qa.scale[1], k_mean, qa.amax[1], reinterpret_cast<float*>((unsigned char*)workspace + up256(plain_bytes)), st);
         if (rc != QATTN_OK) return rc;
     }
-    if (D == 64) rc = launch_vfp<64>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, precision, st);
-    else if (D == 128) rc = launch_vfp<128>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, precision, st);
-    else rc = launch_vfp<256>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, precision, st);
+    if (D == 64) rc = launch_vfp<64>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, precision, window, st);
+    else if (D == 128) rc = launch_vfp<128>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, precision, window, st);
+    else rc = launch_vfp<256>(qa, a, in_fmt, fp8_fmt, numerics, is_causal, precision, window, st);
     if (rc != QATTN_OK) return rc;
     if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
     if (!smooth || !lse) return QATTN_OK;
     // the launch wrote the LSE of the smoothed scores; the true scores of a row lie sm_scale * q.m higher (-inf rows stay -inf)
     return launch_varlen_smooth_lse(q, (long)st6[0], (long)st6[1], in_fmt, cu_seqlens_q, k_mean, lse, B, Hq, Hkv, total_q, D, sm, st);
+}
+
+extern "C" int qattn_fp8_quant_attention_varlen_forward_fp8pv(const void* q, const void* k, const void* v, const long long* strides, int in_fmt,
+                                                              void* out, float* lse, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                                                              const int* seqused_k, int B, int Hq, int Hkv, int total_q, int total_k, int D,
+                                                              int fp8_fmt, int numerics, int is_causal, float sm_scale, int precision, void* q8,
+                                                              void* k8, void* v8, float* scale_q, float* scale_k, float* scale_v,
+                                                              unsigned char* row_path, float* k_mean, void* workspace, size_t workspace_bytes,
+                                                              void* stream) {
+    return varlen_fp8pv_forward_impl(q, k, v, strides, in_fmt, out, lse, cu_seqlens_q, cu_seqlens_k, seqused_k, B, Hq, Hkv, total_q, total_k, D,
+                                     fp8_fmt, numerics, is_causal, sm_scale, precision, q8, k8, v8, scale_q, scale_k, scale_v, row_path, k_mean,
+                                     workspace, workspace_bytes, stream, nullptr);
 }

@@ -292,6 +292,48 @@ def _(query, key, value, cu_seqlens_q, cu_seqlens_k, seqused_k=None, max_seqlen_
     return out, lse
 
 
+@_custom_op("quantumattention_amd::fp8_varlen_window_attention_forward_fp8pv", mutates_args=(), device_types=("cuda",))
+def fp8_varlen_window_attention_forward_fp8pv(
+    query: torch.Tensor,
+    key: torch.Tensor,
+    value: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    cu_seqlens_k: torch.Tensor,
+    seqused_k: Optional[torch.Tensor] = None,
+    max_seqlen_q: int = 0,
+    max_seqlen_k: int = 0,
+    window_left: int = -1,
+    window_right: int = -1,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    return_lse: bool = False,
+    smooth_k: bool = False,
+    precision: str = "accurate",
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """Sliding-window attention on packed sequences with FP8 P.V (include/qattn_window.h, ..._window_forward_fp8pv): the tensors, window and
+    results of fp8_varlen_window_attention_forward; value is quantised head-wise per (sequence, head) over the used keys, P is e4m3 --
+    two-term everywhere (precision "accurate") or one-term byte-exponential for the 128-row tiles whose rows attend an interval of
+    >= 1024 keys ("fast").  Arguments are validated by varlen.fp8_attn_varlen_window_pv_func."""
+    del max_seqlen_q, max_seqlen_k
+    res = _native.fp8_quant_attention_varlen_window_fp8pv(
+        query, key, value, cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous(), None if seqused_k is None else seqused_k.contiguous(),
+        window_left=window_left, window_right=window_right, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics,
+        sm_scale=0.0 if scale is None else float(scale), precision=precision, return_lse=return_lse, smooth_k=smooth_k)
+    if return_lse:
+        return res
+    return res, torch.empty((0,), dtype=torch.float32, device=query.device)
+
+
+@_register_fake("quantumattention_amd::fp8_varlen_window_attention_forward_fp8pv")
+def _(query, key, value, cu_seqlens_q, cu_seqlens_k, seqused_k=None, max_seqlen_q=0, max_seqlen_k=0, window_left=-1, window_right=-1,
+      fp8_format="e4m3", numerics="compiled", return_lse=False, smooth_k=False, precision="accurate", *, scale=None):
+    out = query.new_empty((query.shape[0], query.shape[1], value.shape[2]), dtype=value.dtype)
+    lse = query.new_empty((query.shape[1], query.shape[0]) if return_lse else (0,), dtype=torch.float32)
+    return out, lse
+
+
 @_custom_op("quantumattention_amd::fp8_block_sparse_attention_forward", mutates_args=(), device_types=("cuda",))
 def fp8_block_sparse_attention_forward(
     query: torch.Tensor,

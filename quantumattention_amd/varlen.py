@@ -314,13 +314,10 @@ def fp8_attn_varlen_window_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_
     return (out, lse) if return_lse else out
 
 
-def fp8_window_attn_func(q, k, v, window_size, *, scale=None, return_lse=False):
-    """Sliding-window FP8 attention on dense [B, H, S, D] tensors (the block-sparse entry's call shape): q [B, Hq, Sq, D], k / v
-    [B, Hkv, Skv, D]; every batch entry is one sequence of `fp8_attn_varlen_window_func` (scales per (batch, head), delta = Skv - Sq).
-    The packed [B S, H, D] views and the arange(B+1) S tables are built on the device, without a host synchronisation.  The view is free
-    when B == 1, or when a tensor's batch stride equals S x its token stride (anything backed by [B, S, H, D] memory); any other layout
-    with B > 1 -- a contiguous [B, H, S, D] among them -- costs ONE re-layout copy of that tensor.
-    Returns out as a [B, Hq, Sq, D] view of the packed result, or (out, lse) with return_lse (lse fp32 [B, Hq, Sq], a view)."""
+def _window_attn_dense(packed_call, q, k, v, window_size, return_lse):
+    """The dense [B, H, S, D] call shape around a packed window function: checks, the packed [B S, H, D] views (free where
+    `fp8_window_attn_func` says so, else one copy), the arange(B+1) S tables built on the device, and the views of the packed results.
+    packed_call(qp, kp, vp, cu_q, cu_k, Sq, Skv) returns out or (out, lse)."""
     if not all(isinstance(t, Tensor) for t in (q, k, v)) or q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError("NYI: query, key and value must be 4-D tensors [B, heads, seq_len, head_dim]")
     if k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0]:
@@ -332,6 +329,93 @@ def fp8_window_attn_func(q, k, v, window_size, *, scale=None, return_lse=False):
     # [B, H, S, D] -> [B, S, H, D] -> [B S, H, D]: reshape returns a view exactly where the rule above holds, else one copy
     qp, kp, vp = (t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], t.shape[1], t.shape[3]) for t in (q, k, v))
     steps = torch.arange(B + 1, dtype=_INDEX_DTYPE, device=q.device)
-    res = fp8_attn_varlen_window_func(qp, kp, vp, steps * Sq, steps * Skv, Sq, Skv, window_size, softmax_scale=scale, return_lse=return_lse)
+    res = packed_call(qp, kp, vp, steps * Sq, steps * Skv, Sq, Skv)
     out = (res[0] if return_lse else res).view(B, Sq, Hq, D).permute(0, 2, 1, 3)
     return (out, res[1].view(Hq, B, Sq).permute(1, 0, 2)) if return_lse else out
+
+
+def fp8_window_attn_func(q, k, v, window_size, *, scale=None, return_lse=False):
+    """Sliding-window FP8 attention on dense [B, H, S, D] tensors (the block-sparse entry's call shape): q [B, Hq, Sq, D], k / v
+    [B, Hkv, Skv, D]; every batch entry is one sequence of `fp8_attn_varlen_window_func` (scales per (batch, head), delta = Skv - Sq).
+    The packed [B S, H, D] views and the arange(B+1) S tables are built on the device, without a host synchronisation.  The view is free
+    when B == 1, or when a tensor's batch stride equals S x its token stride (anything backed by [B, S, H, D] memory); any other layout
+    with B > 1 -- a contiguous [B, H, S, D] among them -- costs ONE re-layout copy of that tensor.
+    Returns out as a [B, Hq, Sq, D] view of the packed result, or (out, lse) with return_lse (lse fp32 [B, Hq, Sq], a view)."""
+    return _window_attn_dense(
+        lambda qp, kp, vp, cu_q, cu_k, Sq, Skv: fp8_attn_varlen_window_func(qp, kp, vp, cu_q, cu_k, Sq, Skv, window_size, softmax_scale=scale,
+                                                                            return_lse=return_lse),
+        q, k, v, window_size, return_lse)
+
+
+# ---- FP8 P.V under the sliding window (include/qattn_window.h: qattn_fp8_quant_attention_varlen_window_forward_fp8pv) ---------------------
+def _varlen_window_eager_fp8pv(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, window_size, return_lse, smooth_k=False):
+    """config.attention.force_eager_fallback with pv_precision="fp8": `_varlen_window_eager` with V restated as `_varlen_eager_fp8pv`
+    restates it for `_varlen_eager` -- every sequence's V of the USED keys goes through the eager quantiser per head and back (fp32);
+    everything else (q, k, mask, keyless rows, the LSE and its smooth_k correction) is `_varlen_window_eager`'s, whose fp32 P.V then runs
+    on the de-quantised V.  Keys beyond seqused_k are replaced by zeros and attended by no row."""
+    fp8_dtype = nn._fp8_dtype()
+    cq, ck = cu_seqlens_q.tolist(), cu_seqlens_k.tolist()
+    used = None if seqused_k is None else seqused_k.tolist()
+    dv = torch.zeros(v.shape, dtype=torch.float32, device=v.device)
+    for i in range(len(cq) - 1):
+        lk = ck[i + 1] - ck[i] if used is None else min(used[i], ck[i + 1] - ck[i])
+        if cq[i + 1] - cq[i] <= 0 or lk <= 0:
+            continue
+        vi = v[ck[i]:ck[i] + lk].transpose(0, 1)[None]
+        v8, sv = nn._dynamically_quantize_fp8(vi, reduction_dim=[2, 3], fp8_dtype=fp8_dtype)
+        dv[ck[i]:ck[i] + lk] = (v8.float() * sv[..., None, None])[0].transpose(0, 1)
+    return _varlen_window_eager(q, k, dv, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, window_size, return_lse, smooth_k)
+
+
+def fp8_attn_varlen_window_pv_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window_size, dropout_p=0.0, softmax_scale=None,
+                                   *, seqused_k=None, return_lse=False, pv_precision="16bit", precision="accurate"):
+    """fp8_attn_varlen_window_func with the P.V path as an explicit argument (same tensors, tables, window, results and config flags; a
+    sibling function: fp8_attn_varlen_window_func keeps the signature it was released with).
+    pv_precision "16bit" (default): exactly fp8_attn_varlen_window_func, bit for bit; `precision` must then be "accurate".
+    pv_precision "fp8": both products on the FP8 matrix pipe (include/qattn_window.h, ..._window_forward_fp8pv).  q, k and v are quantised
+    as by fp8_attn_varlen_pv_func: head-wise per (sequence, head) over all queries and all USED keys, windowed or not.  V must be FINITE
+    on the used keys -- unlike the 16-bit window path, which tolerates NaN in V rows that no row attends; keys beyond seqused_k still
+    influence no output bit.  One workgroup per 128-row tile sweeps only the 64-key chunks of [klo, khi], the keys its rows attend.  P is
+    e4m3: precision "accurate" = exact exponentials and two-term (hi + lo) P on every row; "fast" = the one-term byte-exponential sweep
+    for the tiles with n = khi - klo + 1 >= 1024, two-term below, and exact exponentials on the one-term tiles when the LSE is asked
+    for.  "fast" has no rescue pass and is stated for score variance softmax_scale^2 D <= 1.  A row whose window holds no key gives a
+    zero row and an LSE of -inf.  Any other value of either argument -- "auto" included -- raises ValueError.
+    config.attention.pv_precision / precision do not apply; fp8_format, quant_numerics, smooth_k, skip_supported_check and
+    force_eager_fallback are followed as by fp8_attn_varlen_window_func."""
+    if pv_precision not in ("16bit", "fp8"):
+        raise ValueError(f"Unsupported pv_precision: {pv_precision!r} (expected '16bit' or 'fp8')")
+    if pv_precision == "16bit":
+        if precision != "accurate":
+            raise ValueError(f"Unsupported precision for pv_precision='16bit': {precision!r} (the 16-bit P.V path has one precision, 'accurate')")
+        return fp8_attn_varlen_window_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window_size, dropout_p, softmax_scale,
+                                           seqused_k=seqused_k, return_lse=return_lse)
+    if precision not in ("accurate", "fast"):
+        raise ValueError(f"Unsupported precision for pv_precision='fp8': {precision!r} (expected 'accurate' or 'fast'; 'auto' is not offered "
+                         "by the sliding-window entry)")
+    smooth_k = bool(checks.config_value("attention.smooth_k"))
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = varlen_input_reason(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, seqused_k)
+        if reason is None:
+            reason = window_size_reason(window_size)
+        if reason is None:
+            ok, reason = nn._pre_check_can_use_hip_attention(device=q.device)
+            reason = None if ok else reason
+        if reason:
+            raise ValueError(reason)
+    if checks.config_value("attention.force_eager_fallback") and not torch.compiler.is_dynamo_compiling():
+        return _varlen_window_eager_fp8pv(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, softmax_scale, window_size, return_lse, smooth_k)
+    out, lse = nn._ops().fp8_varlen_window_attention_forward_fp8pv(
+        q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, int(max_seqlen_q), int(max_seqlen_k), int(window_size[0]), int(window_size[1]),
+        checks.config_value("attention.fp8_format"), checks.config_value("attention.quant_numerics"), bool(return_lse), smooth_k, precision,
+        scale=softmax_scale)
+    return (out, lse) if return_lse else out
+
+
+def fp8_window_attn_pv_func(q, k, v, window_size, *, scale=None, return_lse=False, pv_precision="16bit", precision="accurate"):
+    """fp8_window_attn_func with the P.V path as an explicit argument: its dense [B, H, S, D] call shape and view logic around
+    `fp8_attn_varlen_window_pv_func` (pv_precision / precision as there; "16bit" is fp8_window_attn_func bit for bit)."""
+    return _window_attn_dense(
+        lambda qp, kp, vp, cu_q, cu_k, Sq, Skv: fp8_attn_varlen_window_pv_func(qp, kp, vp, cu_q, cu_k, Sq, Skv, window_size, softmax_scale=scale,
+                                                                               return_lse=return_lse, pv_precision=pv_precision,
+                                                                               precision=precision),
+        q, k, v, window_size, return_lse)
