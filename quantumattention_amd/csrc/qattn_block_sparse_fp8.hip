@@ -5,22 +5,20 @@
 //   quant  qattn_quant_fp8 of q (row-major), k (KFRAG; with smoothing launch_smooth_k) and v (VFRAG): head-wise over the WHOLE tensors
 //   lists  block_mask_to_list128_kernel, one wave per (b, h, 128-row query block): {n, keys listed, j_0 < j_1 < ... < j_n-1}
 //          (ballot + prefix popcount: no atomics, no scan)
-//   attn   attn_bs_fp8_kernel, one 4-wave workgroup per (b, h, 128-row query block) at every head dimension: the per-wave sequence of
-//          attn_fwd_kernel_v4 (qattn_attn_v4.hip: QK^T -> max / rescale -> exponentials -> PV, two-stage K/V LDS-DMA ring, Q^T fragments
-//          parked in LDS) over the 64-key chunks of the block's OWN list, which sits in LDS behind the ring.  A workgroup is exactly one mask
-//          row, so nothing is swept for a neighbour (the 256-row workgroups of the 16-bit-PV entry sweep the union of two lists).
+//   attn   attn_bs_fp8_kernel, one 4-wave workgroup per (b, h, 128-row query block) at every head dimension: the FP8-PV chunk sweep of
+//          qattn_fp8pv_sweep.h (shared with the packed and the sliding-window kernels) over the 64-key chunks of the block's OWN list,
+//          which sits in LDS behind the ring.  This unit keeps the block map, the list and the ragged-tail mask.  A workgroup is exactly
+//          one mask row, so nothing is swept for a neighbour (the 256-row workgroups of the 16-bit-PV entry sweep the union of two lists).
 //          ACCURATE: one launch, exact exponentials and two-term (hi + lo) e4m3 P.  FAST: two launches -- the byte-exponential one-term
 //          sweep (exact exponentials when an LSE is asked for) for the blocks that list >= kTwoTermKeys keys, the two-term sweep for the
 //          rest; a workgroup whose block belongs to the other launch returns at once.
-#include "qattn_attn.h"
+#include "qattn_fp8pv_sweep.h"
 #include "../../include/qattn_block_sparse.h"
 
 namespace qattn {
 
 constexpr int kBsfBlock = QATTN_BLOCK_SPARSE_BLOCK;
-constexpr int kBsfWaves = 4;                       // waves per workgroup: 4 x 32 rows = one mask block
-constexpr int kBsfStages = 2;
-static_assert(kBsfBlock == kBsfWaves * kQPerWave && kBsfBlock == 2 * 64, "a workgroup is one mask block; a key block is two 64-key chunks");
+static_assert(kBsfBlock == kFpvTile, "a workgroup is one mask block; a key block is two 64-key chunks");
 
 struct BsfMask {
     const unsigned char* m;   // one byte per tile, 0 = off
@@ -52,36 +50,15 @@ __global__ __launch_bounds__(256) void block_mask_to_list128_kernel(const BsfMas
     if (lane == 0) { out[0] = n; out[1] = keys; }
 }
 
-// LIGHT = the byte-exponential kernel (the lean register budget); the exact / two-term variants get one wave per SIMD less
-template <int D, bool LIGHT> struct BsfShape {
-    static constexpr int WPS = D == 256 ? 2 : (D == 64 ? (LIGHT ? 4 : 3) : (LIGHT ? 3 : 2));
-};
-
-// 4 scores -> 4 e4m3 bytes of 2^x (byte_exp4 of qattn_attn_v4.hip)
-__device__ __forceinline__ int bsf_byte_exp4(float s0, float s1, float s2, float s3, float c8, float off8) {
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-    const us2 qa = __builtin_amdgcn_cvt_pknorm_u16(__builtin_fmaf(s0, c8, off8), __builtin_fmaf(s1, c8, off8));
-    const us2 qb = __builtin_amdgcn_cvt_pknorm_u16(__builtin_fmaf(s2, c8, off8), __builtin_fmaf(s3, c8, off8));
-    unsigned ua, ub;
-    __builtin_memcpy(&ua, &qa, 4);
-    __builtin_memcpy(&ub, &qb, 4);
-    return (int)__builtin_amdgcn_perm(ub, ua, 0x06040200u);
-}
-
-constexpr int kBsfSelAll = 0, kBsfSelMany = 1, kBsfSelFew = 2;   // which blocks a launch attends: all / keys >= two_term_keys / fewer
-
-// BYTE: byte-exponential P + matrix-pipe row sums.  !BYTE: exact v_exp_f32, RNE e4m3, fp32 row sums (LSE output) and -- `two` -- the
-// hi + lo two-term P.  p.nqb: 128-row blocks per head; p.v / p.sv: the head-wise FP8 V (VFRAG) and its scales.
+// BYTE / two: FpvSweep (qattn_fp8pv_sweep.h).  sel: the launch (kFpvSel*).  p.nqb: 128-row blocks per head; p.v / p.sv: the head-wise
+// FP8 V (VFRAG) and its scales.
 template <int D, int FMT, bool BYTE>
-__global__ __launch_bounds__(kBsfWaves * 64, (BsfShape<D, BYTE>::WPS))
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
 void attn_bs_fp8_kernel(const AttnParams p, const int* lists, const int list_stride, const int two, const int sel) {
-    constexpr int NW = kBsfWaves;
-    constexpr int CH = 64 * D, STAGE = 2 * CH, MB = D / 32, KS = D / 64;
-    constexpr int RK = CH / (NW * 1024);   // 1 KiB DMA pieces per wave for the K (and for the V) part of a stage
+    constexpr int CH = 64 * D, MB = D / 32, KS = D / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ql = lane & 31, hh = lane >> 5;
+    FpvSweep<D, FMT, BYTE> sw(smem);
+    const int lane = sw.lane, wave = sw.wave, ql = sw.ql, hh = sw.hh;
 
     int head, qb;
     map_block(p, (int)blockIdx.x, p.nqb, false, head, qb);
@@ -93,18 +70,11 @@ void attn_bs_fp8_kernel(const AttnParams p, const int* lists, const int list_str
     const int n = __builtin_amdgcn_readfirstlane(lrow[0]);
     {   // workgroup-uniform: the launch this block belongs to
         const int keys = __builtin_amdgcn_readfirstlane(lrow[1]);
-        if (sel == kBsfSelMany && keys < p.two_term_keys) return;
-        if (sel == kBsfSelFew && keys >= p.two_term_keys) return;
+        if (sel == kFpvSelMany && keys < p.two_term_keys) return;
+        if (sel == kFpvSelFew && keys >= p.two_term_keys) return;
     }
-    if (n == 0) {   // a query block that lists nothing: zero rows, LSE -inf, path code QATTN_PATH_ONE_TERM
-        v16f z[MB];
-#pragma unroll
-        for (int m = 0; m < MB; m++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) z[m][r] = 0.0f;
-        store_o_rows<MB>(p.out, p.out_fmt, z, 0.0f, out_row_offset(p, bh, qrow, MB * 64), hh, qrow < p.Sq);
-        if (p.lse && hh == 0 && qrow < p.Sq) p.lse[bh * p.lse_stride + qrow] = -INFINITY;
-        if (p.path && hh == 0 && qrow < p.Sq) p.path[bh * p.Sq + qrow] = (unsigned char)QATTN_PATH_ONE_TERM;
+    if (n == 0) {   // a query block that lists nothing
+        fpv_store_empty<D>(p.out, p.out_fmt, out_row_offset(p, bh, qrow, MB * 64), p.lse, bh * p.lse_stride + qrow, p.path, bh * p.Sq + qrow, hh, qrow < p.Sq);
         return;
     }
     // 64-key chunks to sweep: two per listed block, one for a last key block of at most 64 keys (ascending: it can only be the last entry)
@@ -112,87 +82,30 @@ void attn_bs_fp8_kernel(const AttnParams p, const int* lists, const int list_str
     const int last = __builtin_amdgcn_readfirstlane(lrow[1 + n]);
     const int n_wg = 2 * n - ((last == nkb - 1 && (p.nchunks & 1)) ? 1 : 0);
 
-    const unsigned char* kg_w = p.k + kv_head * (long)p.nchunks * CH + (wave << 10);
-    const unsigned char* vg_w = p.v + kv_head * (long)p.nchunks * CH + (wave << 10);
-    // stage(t) = {K chunk c_t, V chunk c_t} -> slot t & 1; every wave copies 2*RK x 1 KiB of it by LDS-DMA
-    const unsigned lane16 = (unsigned)lane << 4;
-    unsigned slot_next = 0;
-    auto dma_chunk = [&](int chunk) {
-        unsigned char* dst = smem + slot_next + (wave << 10);
-        const size_t coff = (size_t)chunk * CH + lane16;
-#pragma unroll
-        for (int r = 0; r < RK; r++) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kg_w + (coff + r * (NW * 1024))),
-                                             (__attribute__((address_space(3))) void*)(dst + r * (NW * 1024)), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vg_w + (coff + r * (NW * 1024))),
-                                             (__attribute__((address_space(3))) void*)(dst + CH + r * (NW * 1024)), 16, 0, 0);
-        }
-        slot_next ^= STAGE;
-    };
+    FpvRing<D> ring(smem, wave, lane, p.k + kv_head * (long)p.nchunks * CH + (wave << 10), p.v + kv_head * (long)p.nchunks * CH + (wave << 10));
     // the block's list, behind the ring and the Q slots (requested before the first DMA: the wait for these loads does not wait for it)
-    int* lst = reinterpret_cast<int*>(smem + kBsfStages * STAGE + NW * kQPerWave * D);
-    for (int i = tid; i < n; i += NW * 64) lst[i] = lrow[2 + i];
+    int* lst = reinterpret_cast<int*>(smem + fpv_lds_bytes(D));
+    for (int i = (int)threadIdx.x; i < n; i += kFpvWaves * 64) lst[i] = lrow[2 + i];
     int cur = 2 * __builtin_amdgcn_readfirstlane(lrow[2]);   // chunk of step 0
-    dma_chunk(cur);
-
-    // Q^T fragments parked in this lane's own LDS slots
-    unsigned char* qbuf = smem + kBsfStages * STAGE + wave * (KS << 11) + (hh << 10) + (ql << 4);
+    ring.dma_chunk(cur);
     {
         const bool qvalid = qrow < p.Sq;
-        const unsigned char* qp = p.q + (bh * p.Sq + (qvalid ? qrow : 0)) * D + hh * 32;
-#pragma unroll
-        for (int s = 0; s < KS; s++) {
-            v4i lo = *reinterpret_cast<const v4i*>(qp + s * 64);
-            v4i hi = *reinterpret_cast<const v4i*>(qp + s * 64 + 16);
-            if (!qvalid) { lo = v4i{0, 0, 0, 0}; hi = v4i{0, 0, 0, 0}; }
-            *reinterpret_cast<v4i*>(qbuf + (s << 11)) = lo;
-            *reinterpret_cast<v4i*>(qbuf + (s << 11) + 512) = hi;
-        }
+        sw.park_q(p.q + (bh * p.Sq + (qvalid ? qrow : 0)) * D + hh * 32, qvalid);
     }
     lds_barrier();   // the list is in LDS
-    const float c = p.sm_log2e * p.sq[bh] * p.sk[kv_head];
-
-    v16f o[MB];
-#pragma unroll
-    for (int m = 0; m < MB; m++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) o[m][r] = 0.0f;
-    v4f lsum = {0.0f, 0.0f, 0.0f, 0.0f};
-    v8i ones;  // A of the row-sum MFMA (see WaveState::lsum in qattn_attn_v2.hip)
-    {
-        const int row = lane & 15, kg = lane >> 4;
-        const int one = ((row == 0 && !(kg & 1)) || (row == 1 && (kg & 1))) ? 0x38383838 : 0;
-#pragma unroll
-        for (int w = 0; w < 8; w++) ones[w] = one;
-    }
-    float m_run = -1.0e30f, l_run = 0.0f;
-    float lim = -1.0e30f, off8 = 0.0f;   // m_run + thr / c and the byte formula's additive constant (set by the first chunk's fix-up)
-    constexpr float U16 = 1.0f / 65535.0f;
-    const float c8 = (8.0f * U16) * c;
-    const int frag_lane_off = (hh << 10) + (ql << 4);
+    sw.init_state(p.sm_log2e * p.sq[bh] * p.sk[kv_head], -1.0e30f);
+    const v8i ones = fpv_ones(lane);
 
     for (int t = 0; t < n_wg; t++) {
         v8i qf[KS];
-#pragma unroll
-        for (int s = 0; s < KS; s++) qf[s] = lds_read_frag(qbuf + (s << 11));
+        sw.read_q(qf);
         int nxt = 0;   // chunk of step t + 1 (workgroup-uniform)
         if (t + 1 < n_wg) nxt = __builtin_amdgcn_readfirstlane(2 * lst[(t + 1) >> 1] + ((t + 1) & 1));
-        wait_vmcnt<0>();                  // this wave's pieces of stage t have landed
-        __builtin_amdgcn_s_barrier();     // ... and everyone's; every wave is also done with stage t-1's slot
-        if (t + 1 < n_wg) dma_chunk(nxt);
-        const unsigned char* kbuf = smem + (t & 1) * STAGE + frag_lane_off;
-        const unsigned char* vbuf = kbuf + CH;
-        // ---- S^T = K.Q^T
+        sw.wait_stage();
+        if (t + 1 < n_wg) ring.dma_chunk(nxt);
         v16f s0, s1;
-#pragma unroll
-        for (int r = 0; r < 16; r++) { s0[r] = 0.0f; s1[r] = 0.0f; }
-#pragma unroll
-        for (int s = 0; s < KS; s++) {
-            const v8i ka = lds_read_frag(kbuf + ((0 * KS + s) << 11)), kb = lds_read_frag(kbuf + ((1 * KS + s) << 11));
-            s0 = mfma_f8<FMT, FMT>(ka, qf[s], s0);
-            s1 = mfma_f8<FMT, FMT>(kb, qf[s], s1);
-        }
-        const v8i vf0 = lds_read_frag(vbuf), vf1 = lds_read_frag(vbuf + (1 << 11));
+        v8i vf0, vf1;
+        sw.qk(t, qf, s0, s1, vf0, vf1);
         // ---- ragged tail of the key sequence
         const int k0 = cur * 64;
         cur = nxt;
@@ -204,115 +117,28 @@ void attn_bs_fp8_kernel(const AttnParams p, const int* lists, const int list_str
                 sx[r & 15] = key >= p.Skv ? -INFINITY : sx[r & 15];
             }
         }
-        // ---- running max; rescale only when a row's max grew past the headroom of the shifted exponent
-        float mx = max32_after_mfma(s0, s1);
-        {
-            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = max3_raw(__uint_as_float(sw[0]), __uint_as_float(sw[1]), __uint_as_float(sw[1]));
-        }
-        if (__builtin_expect(__any(mx > lim) != 0, 0)) {   // (mx - m_run) c > thr: P' could overflow e4m3
-            const float m_new = fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-#pragma unroll
-            for (int m = 0; m < MB; m++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) o[m][r] *= alpha;
-            if (BYTE) {
-                const float alpha16 = __shfl(alpha, (lane & 15) + 16);
-                lsum[0] *= alpha;
-                lsum[1] *= alpha16;
-            } else {
-                l_run *= alpha;
-            }
-            m_run = m_new;
-            lim = m_new + kRescaleThrByte / c;
-            off8 = __builtin_fmaf((-8.0f * U16) * m_new, c, (8.0f * kPShiftByte + 56.0f + kByteBias) * U16);
-        }
-        v8i pv, pl;
-        if (BYTE) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                pv[j] = bsf_byte_exp4(s0[4 * j], s0[4 * j + 1], s0[4 * j + 2], s0[4 * j + 3], c8, off8);
-                pv[4 + j] = bsf_byte_exp4(s1[4 * j], s1[4 * j + 1], s1[4 * j + 2], s1[4 * j + 3], c8, off8);
-            }
-        } else {
-            const float mc = kPShift - m_run * c;
-            float ls = 0.0f;
-#pragma unroll
-            for (int w = 0; w < 8; w++) {
-                const v16f& sx = w < 4 ? s0 : s1;
-                const int j = w & 3;
-                float e[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) { e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(sx[4 * j + i], c, mc)); ls += e[i]; }
-                int ph = cvt_pk_fp8<QATTN_FMT_E4M3, false>(e[0], e[1], 0);
-                ph = cvt_pk_fp8<QATTN_FMT_E4M3, true>(e[2], e[3], ph);
-                pv[w] = ph;
-                int plo = 0;
-                if (two) plo = lo_terms(e, ph, 0);
-                pl[w] = plo;
-            }
-            l_run += ls;
-        }
-        // ---- O^T += V^T.P^T, row sums (V's one scale per head is applied in the epilogue; the low term's 2^-5 rides in the scale word)
-        o[0] = mfma_f8<FMT, QATTN_FMT_E4M3>(vf0, pv, o[0]);
-        o[1] = mfma_f8<FMT, QATTN_FMT_E4M3>(vf1, pv, o[1]);
-        if (!BYTE && two) {
-            o[0] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vf0, pl, o[0], kScaleWordOne);
-            o[1] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vf1, pl, o[1], kScaleWordOne);
-        }
-#pragma unroll
-        for (int m = 2; m < MB; m += 2) {
-            const v8i va = lds_read_frag(vbuf + (m << 11)), vb = lds_read_frag(vbuf + ((m + 1) << 11));
-            o[m] = mfma_f8<FMT, QATTN_FMT_E4M3>(va, pv, o[m]);
-            o[m + 1] = mfma_f8<FMT, QATTN_FMT_E4M3>(vb, pv, o[m + 1]);
-            if (!BYTE && two) {
-                o[m] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(va, pl, o[m], kScaleWordOne);
-                o[m + 1] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vb, pl, o[m + 1], kScaleWordOne);
-            }
-        }
-        if (BYTE) lsum = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ones, pv, lsum, QATTN_FMT_E4M3, QATTN_FMT_E4M3, 0, 0, 0, 0);
+        sw.softmax_pv(s0, s1, vf0, vf1, two, [&] { return ones; });
     }
 
-    // ---- epilogue
-    float l_tot;
-    if (BYTE) {
-        const float s0l = __shfl(lsum[0], lane & 15), s1l = __shfl(lsum[1], lane & 15);
-        l_tot = (lane & 16) ? s1l : s0l;
-    } else {
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
-        l_tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-    }
+    // ---- epilogue (V's one scale per head is applied here)
+    const float l_tot = sw.row_sum();
     const float inv = p.sv[kv_head] / l_tot;
-    store_o_rows<MB>(p.out, p.out_fmt, o, inv, out_row_offset(p, bh, qrow, MB * 64), hh, qrow < p.Sq);
-    if (!BYTE && p.lse && hh == 0 && qrow < p.Sq)  // ln sum_j exp(score_j) = ln2 * (m*c - shift) + ln(l')
-        p.lse[bh * p.lse_stride + qrow] = 0.6931471805599453f * (m_run * c - kPShift) + __logf(l_tot);
+    store_o_rows<MB>(p.out, p.out_fmt, sw.o, inv, out_row_offset(p, bh, qrow, MB * 64), hh, qrow < p.Sq);
+    if (!BYTE && p.lse && hh == 0 && qrow < p.Sq) p.lse[bh * p.lse_stride + qrow] = 0.6931471805599453f * (sw.m_run * sw.c - kPShift) + __logf(l_tot);
     if (p.path && hh == 0 && qrow < p.Sq) p.path[bh * p.Sq + qrow] = (unsigned char)((!BYTE && two) ? QATTN_PATH_TWO_TERM : QATTN_PATH_ONE_TERM);
 }
 
 // LDS of the attention kernel: the K / V ring, the parked Q^T fragments, then the block's list
-constexpr int bsf_fixed_lds(int D) { return kBsfStages * 2 * 64 * D + kBsfWaves * kQPerWave * D; }
-inline size_t bsf_lds_bytes(int D, int nkb) { return (size_t)bsf_fixed_lds(D) + ((size_t)4 * nkb + 15) / 16 * 16; }
+inline size_t bsf_lds_bytes(int D, int nkb) { return (size_t)fpv_lds_bytes(D) + ((size_t)4 * nkb + 15) / 16 * 16; }
 constexpr size_t kBsfMaxLds = 160 * 1024;
-
-template <int D, int FMT, bool BYTE>
-static int launch_bsf_one(const AttnParams& p, const int* lists, int list_stride, int nkb, int two, int sel, hipStream_t st) {
-    const size_t lds = bsf_lds_bytes(D, nkb);
-    auto kern = attn_bs_fp8_kernel<D, FMT, BYTE>;
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return QATTN_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(p.B * p.Hq * p.nqb)), dim3(kBsfWaves * 64), lds, st, p, lists, list_stride, two, sel);
-    return QATTN_OK;
-}
 
 template <int D, int FMT>
 static int launch_bsf_fmt(const AttnParams& p, const int* lists, int list_stride, int nkb, int precision, hipStream_t st) {
-    if (precision == QATTN_PRECISION_ACCURATE || p.Skv < p.two_term_keys)   // (no block can list two_term_keys keys: every one is two-term)
-        return launch_bsf_one<D, FMT, false>(p, lists, list_stride, nkb, 1, kBsfSelAll, st);
-    // FAST: the blocks with many keys on the one-term sweep (an LSE request: exact exponentials), the others two-term
-    int rc = p.lse ? launch_bsf_one<D, FMT, false>(p, lists, list_stride, nkb, 0, kBsfSelMany, st)
-                   : launch_bsf_one<D, FMT, true>(p, lists, list_stride, nkb, 0, kBsfSelMany, st);
-    if (rc == QATTN_OK) rc = launch_bsf_one<D, FMT, false>(p, lists, list_stride, nkb, 1, kBsfSelFew, st);
-    return rc;
+    // (Skv: the most keys a block can list)
+    return fpv_precision_ladder(precision, p.Skv, p.two_term_keys, p.lse != nullptr, [&](auto byte, int two, int sel) {
+        return fpv_launch(attn_bs_fp8_kernel<D, FMT, decltype(byte)::value>, (unsigned)(p.B * p.Hq * p.nqb), bsf_lds_bytes(D, nkb), st, p, lists,
+                          list_stride, two, sel);
+    });
 }
 
 template <int D>
@@ -326,7 +152,6 @@ static int launch_bsf_d(const AttnParams& p, const int* lists, int list_stride, 
 using namespace qattn;
 
 namespace {
-size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 bool bsf_dims_ok(int B, int Hq, int Hkv, int Sq, int Skv) { return B > 0 && Hq > 0 && Hkv > 0 && Sq > 0 && Skv > 0; }
 size_t bsf_quant_ws_bytes(int B, int Hq, int Hkv, int Sq, int Skv, int D) {
     const size_t a = qattn_quant_workspace_bytes(B, Hq, Sq, D, QATTN_SCALE_HEAD), b = qattn_quant_workspace_bytes(B, Hkv, Skv, D, QATTN_SCALE_HEAD);

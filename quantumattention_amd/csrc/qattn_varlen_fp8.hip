@@ -8,15 +8,16 @@
 //   quant  64-row tiles: q into its row-major slab, k into its KFRAG image -- statement for statement qattn_varlen.hip's pass, so the
 //          bytes and scales are the 16-bit-PV entry's -- and v into a VFRAG image beside k's (quant8 / vfrag_offset of the dense pre-pass)
 //          With key smoothing K is left out of both (qattn_varlen_smooth.hip's launches quantise it), as in the 16-bit-PV entry.
-//   attn   attn_vfp8_kernel: attn_bs_fp8_kernel (qattn_block_sparse_fp8.hip) with the packed block map in place of the mask lists --
-//          one 4-wave workgroup per (head, 128-row tile of a sequence) sweeps the 64-key chunks 0 .. n - 1 of that sequence (causal:
-//          up to the tile's diagonal), the chunk number being the loop counter.  ACCURATE: one launch.  FAST: two launches, as there --
+//   attn   attn_vfp8_kernel: the FP8-PV chunk sweep of qattn_fp8pv_sweep.h (shared with the block-sparse and the sliding-window kernels)
+//          under the packed block map -- one 4-wave workgroup per (head, 128-row tile of a sequence) sweeps the 64-key chunks 0 .. n - 1
+//          of that sequence (causal: up to the tile's diagonal), the chunk number being the loop counter; this unit keeps the map, the
+//          tail / diagonal mask and the token-stride offsets.  ACCURATE: one launch.  FAST: two launches (fpv_precision_ladder) --
 //          the one-term sweep for the tiles whose rows see >= kTwoTermKeys keys, the two-term sweep for the rest; a workgroup whose tile
 //          belongs to the other launch returns before any DMA or barrier.  With total_k < kTwoTermKeys no tile can be one-term: one launch.
 //
 // Block -> (sequence, tile): qattn_varlen_tile.h with R = 128.
-// What the sliding-window unit (qattn_varlen_window_fp8.hip) shares with this one is in qattn_varlen_fp8.h; the body of the entry below
-// (varlen_fp8pv_forward_impl) runs that unit's attention launch behind this unit's pre-pass when it is given a window.
+// The body of the entry below (varlen_fp8pv_forward_impl, declared in qattn_varlen_fp8.h with the launch's arguments) runs the
+// sliding-window unit's attention launch (qattn_varlen_window_fp8.hip) behind this unit's pre-pass when it is given a window.
 #include "qattn_varlen_fp8.h"
 #include "qattn_varlen_tile.h"
 #include "../../include/qattn_varlen.h"
@@ -142,19 +143,15 @@ __global__ __launch_bounds__(256) void vfp_quant_kernel(const VfpQuant a, int nu
     for (int i = tid; i < 64 * D / 16; i += 256) og[i] = reinterpret_cast<const uint4*>(img)[i];
 }
 
-// BYTE: byte-exponential P + matrix-pipe row sums.  !BYTE: exact v_exp_f32, RNE e4m3, fp32 row sums (LSE output) and -- `two` -- the
-// hi + lo two-term P.  The sweep and the epilogue are attn_bs_fp8_kernel's, operation for operation: a non-causal sequence comes out
-// with the bits of the block-sparse FP8-PV call on that sequence alone under an all-true mask.
+// BYTE / two: FpvSweep (qattn_fp8pv_sweep.h).  sel: the launch (kFpvSel*).  The sweep is the block-sparse kernel's: a non-causal
+// sequence comes out with the bits of the block-sparse FP8-PV call on that sequence alone under an all-true mask.
 template <int D, int FMT, bool BYTE, bool CAUSAL>
-__global__ __launch_bounds__(kVfpWaves * 64, (VfpShape<D, BYTE>::WPS))
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
 void attn_vfp8_kernel(const VfpAttn a, const int two, const int sel) {
-    constexpr int NW = kVfpWaves;
-    constexpr int CH = 64 * D, STAGE = 2 * CH, MB = D / 32, KS = D / 64;
-    constexpr int RK = CH / (NW * 1024);   // 1 KiB DMA pieces per wave for the K (and for the V) part of a stage
+    constexpr int CH = 64 * D, MB = D / 32, KS = D / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ql = lane & 31, hh = lane >> 5;
+    FpvSweep<D, FMT, BYTE> sw(smem);
+    const int lane = sw.lane, wave = sw.wave, ql = sw.ql, hh = sw.hh;
 
     const int bid = blockIdx.x;
     int h, j;
@@ -167,112 +164,46 @@ void attn_vfp8_kernel(const VfpAttn a, const int two, const int sel) {
         j = bid % a.nblk;
     }
     if (CAUSAL) j = a.nblk - 1 - j;   // (the last tiles of a sequence see the most keys: roughly longest first)
-    const VarlenTile tq = varlen_tile<kVfpTile>(a.cu_q, nullptr, a.B, a.total_q, j);
-    if (tq.tile < 0 || tq.tile * kVfpTile >= tq.len) return;   // no tile of any sequence
+    const VarlenTile tq = varlen_tile<kFpvTile>(a.cu_q, nullptr, a.B, a.total_q, j);
+    if (tq.tile < 0 || tq.tile * kFpvTile >= tq.len) return;   // no tile of any sequence
     const int i = tq.i;
     const int sk0 = clampi(__builtin_amdgcn_readfirstlane(a.cu_k[i]), 0, a.total_k);
     int lk = clampi(__builtin_amdgcn_readfirstlane(a.cu_k[i + 1]), sk0, a.total_k) - sk0;
     if (a.used) lk = clampi(__builtin_amdgcn_readfirstlane(a.used[i]), 0, lk);
     // keys the tile's rows see (its last row, when causal): the rule of the one-term sweep and the trip count, both workgroup-uniform
-    const int keys = CAUSAL ? min(lk, kVfpTile * (tq.tile + 1)) : lk;
-    if (sel == kVfpSelMany && keys < a.two_term_keys) return;
-    if (sel == kVfpSelFew && keys >= a.two_term_keys) return;
+    const int keys = CAUSAL ? min(lk, kFpvTile * (tq.tile + 1)) : lk;
+    if (sel == kFpvSelMany && keys < a.two_term_keys) return;
+    if (sel == kFpvSelFew && keys >= a.two_term_keys) return;
 
     const int kvh = h / (a.Hq / a.Hkv);
-    const int qrow = tq.tile * kVfpTile + wave * kQPerWave + ql;   // row within the sequence
+    const int qrow = tq.tile * kFpvTile + wave * kQPerWave + ql;   // row within the sequence
     const bool qvalid = qrow < tq.len;
     const long orow = ((long)(tq.start + (qvalid ? qrow : 0)) * a.Hq + h) * (2L * D);   // bytes: rows are a token stride apart
     const long lrow = (long)h * a.total_q + tq.start + qrow;                           // lse / path: [Hq, total_q]
-    if (keys == 0) {   // a sequence with queries and no used key: zero rows, LSE -inf, path code QATTN_PATH_ONE_TERM
-        v16f z[MB];
-#pragma unroll
-        for (int m = 0; m < MB; m++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) z[m][r] = 0.0f;
-        store_o_rows<MB>(a.out, a.out_fmt, z, 0.0f, orow, hh, qvalid);
-        if (a.lse && hh == 0 && qvalid) a.lse[lrow] = -INFINITY;
-        if (a.path && hh == 0 && qvalid) a.path[lrow] = (unsigned char)QATTN_PATH_ONE_TERM;
+    if (keys == 0) {   // a sequence with queries and no used key
+        fpv_store_empty<D>(a.out, a.out_fmt, orow, a.lse, lrow, a.path, lrow, hh, qvalid);
         return;
     }
     const int n_wg = (keys + 63) >> 6;        // chunks 0 .. n_wg - 1 (a causal tile: up to its diagonal)
     const int nch = (lk + 63) >> 6;           // chunks of the sequence's images
 
     const long img = (long)a.Hkv * D * (sk0 + 64L * i) + (long)kvh * nch * CH + (wave << 10);
-    const unsigned char* kg_w = a.k8 + img;
-    const unsigned char* vg_w = a.v8 + img;
-    // stage(t) = {K chunk t, V chunk t} -> slot t & 1; every wave copies 2*RK x 1 KiB of it by LDS-DMA
-    const unsigned lane16 = (unsigned)lane << 4;
-    unsigned slot_next = 0;
-    auto dma_chunk = [&](int chunk) {
-        unsigned char* dst = smem + slot_next + (wave << 10);
-        const size_t coff = (size_t)chunk * CH + lane16;
-#pragma unroll
-        for (int r = 0; r < RK; r++) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kg_w + (coff + r * (NW * 1024))),
-                                             (__attribute__((address_space(3))) void*)(dst + r * (NW * 1024)), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vg_w + (coff + r * (NW * 1024))),
-                                             (__attribute__((address_space(3))) void*)(dst + CH + r * (NW * 1024)), 16, 0, 0);
-        }
-        slot_next ^= STAGE;
-    };
-    dma_chunk(0);
-
-    // Q^T fragments parked in this lane's own LDS slots
-    unsigned char* qbuf = smem + kVfpStages * STAGE + wave * (KS << 11) + (hh << 10) + (ql << 4);
-    {
-        const unsigned char* qp = a.q8 + (long)a.Hq * D * tq.start + ((long)h * tq.len + (qvalid ? qrow : 0)) * D + hh * 32;
-#pragma unroll
-        for (int s = 0; s < KS; s++) {
-            v4i lo = *reinterpret_cast<const v4i*>(qp + s * 64);
-            v4i hi = *reinterpret_cast<const v4i*>(qp + s * 64 + 16);
-            if (!qvalid) { lo = v4i{0, 0, 0, 0}; hi = v4i{0, 0, 0, 0}; }
-            *reinterpret_cast<v4i*>(qbuf + (s << 11)) = lo;
-            *reinterpret_cast<v4i*>(qbuf + (s << 11) + 512) = hi;
-        }
-    }
-    const float c = a.sm_log2e * a.sq[(long)i * a.Hq + h] * a.sk[(long)i * a.Hkv + kvh];
-
-    v16f o[MB];
-#pragma unroll
-    for (int m = 0; m < MB; m++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) o[m][r] = 0.0f;
-    v4f lsum = {0.0f, 0.0f, 0.0f, 0.0f};
-    v8i ones;  // A of the row-sum MFMA (see WaveState::lsum in qattn_attn_v2.hip)
-    {
-        const int row = lane & 15, kg = lane >> 4;
-        const int one = ((row == 0 && !(kg & 1)) || (row == 1 && (kg & 1))) ? 0x38383838 : 0;
-#pragma unroll
-        for (int w = 0; w < 8; w++) ones[w] = one;
-    }
-    float m_run = -1.0e30f, l_run = 0.0f;
-    float lim = -1.0e30f, off8 = 0.0f;   // m_run + thr / c and the byte formula's additive constant (set by the first chunk's fix-up)
-    constexpr float U16 = 1.0f / 65535.0f;
-    const float c8 = (8.0f * U16) * c;
-    const int frag_lane_off = (hh << 10) + (ql << 4);
+    FpvRing<D> ring(smem, wave, lane, a.k8 + img, a.v8 + img);
+    ring.dma_chunk(0);
+    sw.park_q(a.q8 + (long)a.Hq * D * tq.start + ((long)h * tq.len + (qvalid ? qrow : 0)) * D + hh * 32, qvalid);
+    sw.init_state(a.sm_log2e * a.sq[(long)i * a.Hq + h] * a.sk[(long)i * a.Hkv + kvh], -1.0e30f);
+    const v8i ones = fpv_ones(lane);
     const int kend = CAUSAL ? min(lk, qrow + 1) : lk;   // this lane's row attends keys 0 .. kend - 1 (token-exact)
     const int diag = 2 * tq.tile;                       // causal: chunks >= diag hold keys beyond the tile's first row
 
-    for (int t = 0; t < n_wg; t++) {
+    for (int t = 0; t < n_wg; t++) {   // step t sweeps chunk t
         v8i qf[KS];
-#pragma unroll
-        for (int s = 0; s < KS; s++) qf[s] = lds_read_frag(qbuf + (s << 11));
-        wait_vmcnt<0>();                  // this wave's pieces of stage t have landed
-        __builtin_amdgcn_s_barrier();     // ... and everyone's; every wave is also done with stage t-1's slot
-        if (t + 1 < n_wg) dma_chunk(t + 1);
-        const unsigned char* kbuf = smem + (t & 1) * STAGE + frag_lane_off;
-        const unsigned char* vbuf = kbuf + CH;
-        // ---- S^T = K.Q^T
+        sw.read_q(qf);
+        sw.wait_stage();
+        if (t + 1 < n_wg) ring.dma_chunk(t + 1);
         v16f s0, s1;
-#pragma unroll
-        for (int r = 0; r < 16; r++) { s0[r] = 0.0f; s1[r] = 0.0f; }
-#pragma unroll
-        for (int s = 0; s < KS; s++) {
-            const v8i ka = lds_read_frag(kbuf + ((0 * KS + s) << 11)), kb = lds_read_frag(kbuf + ((1 * KS + s) << 11));
-            s0 = mfma_f8<FMT, FMT>(ka, qf[s], s0);
-            s1 = mfma_f8<FMT, FMT>(kb, qf[s], s1);
-        }
-        const v8i vf0 = lds_read_frag(vbuf), vf1 = lds_read_frag(vbuf + (1 << 11));
+        v8i vf0, vf1;
+        sw.qk(t, qf, s0, s1, vf0, vf1);
         // ---- ragged tail of the sequence's keys; causal: the diagonal, by token (workgroup-uniform condition)
         const int k0 = t * 64;
         if (__builtin_expect(k0 + 64 > lk || (CAUSAL && t >= diag), 0)) {
@@ -283,109 +214,23 @@ void attn_vfp8_kernel(const VfpAttn a, const int two, const int sel) {
                 sx[r & 15] = key >= kend ? -INFINITY : sx[r & 15];
             }
         }
-        // ---- running max; rescale only when a row's max grew past the headroom of the shifted exponent
-        float mx = max32_after_mfma(s0, s1);
-        {
-            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = max3_raw(__uint_as_float(sw[0]), __uint_as_float(sw[1]), __uint_as_float(sw[1]));
-        }
-        if (__builtin_expect(__any(mx > lim) != 0, 0)) {   // (mx - m_run) c > thr: P' could overflow e4m3
-            const float m_new = fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-#pragma unroll
-            for (int m = 0; m < MB; m++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) o[m][r] *= alpha;
-            if (BYTE) {
-                const float alpha16 = __shfl(alpha, (lane & 15) + 16);
-                lsum[0] *= alpha;
-                lsum[1] *= alpha16;
-            } else {
-                l_run *= alpha;
-            }
-            m_run = m_new;
-            lim = m_new + kRescaleThrByte / c;
-            off8 = __builtin_fmaf((-8.0f * U16) * m_new, c, (8.0f * kPShiftByte + 56.0f + kByteBias) * U16);
-        }
-        v8i pv, pl;
-        if (BYTE) {
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                pv[w] = vfp_byte_exp4(s0[4 * w], s0[4 * w + 1], s0[4 * w + 2], s0[4 * w + 3], c8, off8);
-                pv[4 + w] = vfp_byte_exp4(s1[4 * w], s1[4 * w + 1], s1[4 * w + 2], s1[4 * w + 3], c8, off8);
-            }
-        } else {
-            const float mc = kPShift - m_run * c;
-            float ls = 0.0f;
-#pragma unroll
-            for (int w = 0; w < 8; w++) {
-                const v16f& sx = w < 4 ? s0 : s1;
-                const int jj = w & 3;
-                float e[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) { e[u] = __builtin_amdgcn_exp2f(__builtin_fmaf(sx[4 * jj + u], c, mc)); ls += e[u]; }
-                int ph = cvt_pk_fp8<QATTN_FMT_E4M3, false>(e[0], e[1], 0);
-                ph = cvt_pk_fp8<QATTN_FMT_E4M3, true>(e[2], e[3], ph);
-                pv[w] = ph;
-                int plo = 0;
-                if (two) plo = lo_terms(e, ph, 0);
-                pl[w] = plo;
-            }
-            l_run += ls;
-        }
-        // ---- O^T += V^T.P^T, row sums (V's one scale per (sequence, head) is applied in the epilogue; the low term's 2^-5 rides in the scale word)
-        o[0] = mfma_f8<FMT, QATTN_FMT_E4M3>(vf0, pv, o[0]);
-        o[1] = mfma_f8<FMT, QATTN_FMT_E4M3>(vf1, pv, o[1]);
-        if (!BYTE && two) {
-            o[0] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vf0, pl, o[0], kScaleWordOne);
-            o[1] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vf1, pl, o[1], kScaleWordOne);
-        }
-#pragma unroll
-        for (int m = 2; m < MB; m += 2) {
-            const v8i va = lds_read_frag(vbuf + (m << 11)), vb = lds_read_frag(vbuf + ((m + 1) << 11));
-            o[m] = mfma_f8<FMT, QATTN_FMT_E4M3>(va, pv, o[m]);
-            o[m + 1] = mfma_f8<FMT, QATTN_FMT_E4M3>(vb, pv, o[m + 1]);
-            if (!BYTE && two) {
-                o[m] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(va, pl, o[m], kScaleWordOne);
-                o[m + 1] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vb, pl, o[m + 1], kScaleWordOne);
-            }
-        }
-        if (BYTE) lsum = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ones, pv, lsum, QATTN_FMT_E4M3, QATTN_FMT_E4M3, 0, 0, 0, 0);
+        sw.softmax_pv(s0, s1, vf0, vf1, two, [&] { return ones; });
     }
 
-    // ---- epilogue
-    float l_tot;
-    if (BYTE) {
-        const float s0l = __shfl(lsum[0], lane & 15), s1l = __shfl(lsum[1], lane & 15);
-        l_tot = (lane & 16) ? s1l : s0l;
-    } else {
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
-        l_tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-    }
+    // ---- epilogue (V's one scale per (sequence, head) is applied here)
+    const float l_tot = sw.row_sum();
     const float inv = a.sv[(long)i * a.Hkv + kvh] / l_tot;
-    store_o_rows<MB>(a.out, a.out_fmt, o, inv, orow, hh, qvalid);
-    if (!BYTE && a.lse && hh == 0 && qvalid)  // ln sum_j exp(score_j) = ln2 * (m*c - shift) + ln(l')
-        a.lse[lrow] = 0.6931471805599453f * (m_run * c - kPShift) + __logf(l_tot);
+    store_o_rows<MB>(a.out, a.out_fmt, sw.o, inv, orow, hh, qvalid);
+    if (!BYTE && a.lse && hh == 0 && qvalid) a.lse[lrow] = 0.6931471805599453f * (sw.m_run * sw.c - kPShift) + __logf(l_tot);
     if (a.path && hh == 0 && qvalid) a.path[lrow] = (unsigned char)((!BYTE && two) ? QATTN_PATH_TWO_TERM : QATTN_PATH_ONE_TERM);
-}
-
-template <int D, int FMT, bool BYTE, bool CAUSAL>
-static int launch_vfp_one(const VfpAttn& a, int two, int sel, hipStream_t st) {
-    constexpr int lds = vfp_lds_bytes(D);
-    auto kern = attn_vfp8_kernel<D, FMT, BYTE, CAUSAL>;
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return QATTN_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a.Hq * a.nblk)), dim3(kVfpWaves * 64), lds, st, a, two, sel);
-    return QATTN_OK;
 }
 
 template <int D, int FMT, bool CAUSAL>
 static int launch_vfp_attn(const VfpAttn& a, int precision, hipStream_t st) {
-    if (precision == QATTN_PRECISION_ACCURATE || a.total_k < a.two_term_keys)   // (no tile can see two_term_keys keys: every one is two-term)
-        return launch_vfp_one<D, FMT, false, CAUSAL>(a, 1, kVfpSelAll, st);
-    // FAST: the tiles that see many keys on the one-term sweep (an LSE request: exact exponentials), the others two-term
-    int rc = a.lse ? launch_vfp_one<D, FMT, false, CAUSAL>(a, 0, kVfpSelMany, st) : launch_vfp_one<D, FMT, true, CAUSAL>(a, 0, kVfpSelMany, st);
-    if (rc == QATTN_OK) rc = launch_vfp_one<D, FMT, false, CAUSAL>(a, 1, kVfpSelFew, st);
-    return rc;
+    // (total_k: more than any tile can see)
+    return fpv_precision_ladder(precision, a.total_k, a.two_term_keys, a.lse != nullptr, [&](auto byte, int two, int sel) {
+        return fpv_launch(attn_vfp8_kernel<D, FMT, decltype(byte)::value, CAUSAL>, (unsigned)(a.Hq * a.nblk), fpv_lds_bytes(D), st, a, two, sel);
+    });
 }
 
 template <int D, int IN_FMT, int OUT_FMT>
@@ -413,7 +258,6 @@ static int launch_vfp(const VfpQuant& qa, const VfpAttn& a, int in_fmt, int fp8_
 using namespace qattn;
 
 namespace {
-size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 // the VFRAG images take the room of the KFRAG images: a 64-key chunk is 64 D bytes in both layouts
 size_t vfp_v8_bytes(int B, int Hkv, int total_k, int D) { return qattn_varlen_tensor_bytes(QATTN_LAYOUT_KFRAG, B, Hkv, total_k, D); }
 bool vfp_dims_ok(int B, int Hq, int Hkv, int total_q, int total_k) { return B >= 1 && Hq > 0 && Hkv > 0 && total_q >= 0 && total_k >= 0; }
@@ -452,7 +296,7 @@ int qattn::varlen_fp8pv_forward_impl(const void* q, const void* k, const void* v
         }
     if (((size_t)q | (size_t)k | (size_t)v | (size_t)out) % 16 != 0) return QATTN_ERR_INVALID_ARG;
     // grids: Hq (B + ceil(total_q / 128)) attention workgroups, B + ceil(total / 64) quantise tiles per head (32-bit dimensions)
-    if ((long long)Hq * (B + ceil_div(total_q, kVfpTile)) > 0x7fffffffLL || (long long)B + ceil_div(total_q > total_k ? total_q : total_k, 64) > 0x7fffffffLL)
+    if ((long long)Hq * (B + ceil_div(total_q, kFpvTile)) > 0x7fffffffLL || (long long)B + ceil_div(total_q > total_k ? total_q : total_k, 64) > 0x7fffffffLL)
         return QATTN_ERR_INVALID_ARG;
     const bool smooth = k_mean != nullptr;
     if (smooth && (reinterpret_cast<uintptr_t>(k_mean) & 15u) != 0) return QATTN_ERR_INVALID_ARG;
@@ -484,7 +328,7 @@ int qattn::varlen_fp8pv_forward_impl(const void* q, const void* k, const void* v
     a.sq = qa.scale[0]; a.sk = qa.scale[1]; a.sv = qa.scale[2];
     a.cu_q = cu_seqlens_q; a.cu_k = cu_seqlens_k; a.used = seqused_k;
     a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.total_q = total_q; a.total_k = total_k;
-    a.nblk = B + ceil_div(total_q, kVfpTile);
+    a.nblk = B + ceil_div(total_q, kFpvTile);
     a.out_fmt = in_fmt;
     a.xcd_remap = (Hq % 8 == 0 && xcd_count() == 8) ? 1 : 0;   // (the XCD-contiguous map assumes 8 XCDs; a speed assumption only)
     a.two_term_keys = kTwoTermKeys;

@@ -3,8 +3,8 @@
 // attends the keys j with r + delta - left <= j <= r + delta + right, delta = L_k - L_q (flash-attn's window_size; -1 = unbounded).
 //
 // The pre-pass (zeroing node, abs-max, quantise of q / k / v, the smoothing launches) is the packed FP8-PV entry's own, launched by its
-// body (varlen_fp8pv_forward_impl, qattn_varlen_fp8.hip); this unit holds the attention launch: attn_vfp8_kernel (there) operation for
-// operation, with
+// body (varlen_fp8pv_forward_impl, qattn_varlen_fp8.hip); this unit holds the attention launch: the FP8-PV chunk sweep of
+// qattn_fp8pv_sweep.h, statement for statement what attn_vfp8_kernel (there) runs, with this kernel's own
 //   * the trip range: a 128-row tile sweeps the 64-key chunks klo / 64 .. khi / 64 of [klo, khi], the keys its valid rows attend, and DMAs
 //     no other chunk; the one-term rule of FAST is n = khi - klo + 1 >= two_term_keys;
 //   * the token mask key - row outside [win_lo, win_hi] (and the ragged tail), applied under a workgroup-uniform condition -- the chunk
@@ -20,7 +20,8 @@
 //     ends with l = 0 is scaled by 0 (not by sv / 0) and its LSE is -inf.
 //   * registers: the loop carries the row number alone (the output / LSE offsets are formed before and after the sweep, the row's key
 //     bounds inside the rare masked branch), and the eight equal words of the row-sum MFMA's A operand are spread from one register where
-//     they are used -- the D = 128 byte kernel otherwise kept them in scratch at its 3 waves per SIMD.
+//     they are used (fpv_spread_ones; the other two kernels carry the v8i) -- the D = 128 byte kernel otherwise kept them in scratch at
+//     its 3 waves per SIMD.
 #include "qattn_varlen_fp8.h"
 #include "qattn_varlen_tile.h"
 #include "../../include/qattn_varlen.h"
@@ -30,15 +31,12 @@ namespace qattn {
 
 // BYTE / two / sel: as attn_vfp8_kernel.  left / right: window_left / window_right, >= -1.
 template <int D, int FMT, bool BYTE>
-__global__ __launch_bounds__(kVfpWaves * 64, (VfpShape<D, BYTE>::WPS))
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
 void attn_vfp8_window_kernel(const VfpAttn a, const int two, const int sel, const int left, const int right) {
-    constexpr int NW = kVfpWaves;
-    constexpr int CH = 64 * D, STAGE = 2 * CH, MB = D / 32, KS = D / 64;
-    constexpr int RK = CH / (NW * 1024);   // 1 KiB DMA pieces per wave for the K (and for the V) part of a stage
+    constexpr int CH = 64 * D, MB = D / 32, KS = D / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ql = lane & 31, hh = lane >> 5;
+    FpvSweep<D, FMT, BYTE> sw(smem);
+    const int lane = sw.lane, wave = sw.wave, ql = sw.ql, hh = sw.hh;
 
     const int bid = blockIdx.x;
     int h, j;
@@ -53,8 +51,8 @@ void attn_vfp8_window_kernel(const VfpAttn a, const int two, const int sel, cons
     // (tiles are handed out front to back.  The packed causal kernel walks them back to front, longest sweep first; under a window the
     // sweep length grows only up to left + right + 128 keys and then stays there, so the order matters for (-1, 0) or a left edge of many
     // thousand keys alone -- speed only, not measured, left as it is)
-    const VarlenTile tq = varlen_tile<kVfpTile>(a.cu_q, nullptr, a.B, a.total_q, j);
-    if (tq.tile < 0 || tq.tile * kVfpTile >= tq.len) return;   // no tile of any sequence
+    const VarlenTile tq = varlen_tile<kFpvTile>(a.cu_q, nullptr, a.B, a.total_q, j);
+    if (tq.tile < 0 || tq.tile * kFpvTile >= tq.len) return;   // no tile of any sequence
     const int i = tq.i;
     const int sk0 = clampi(__builtin_amdgcn_readfirstlane(a.cu_k[i]), 0, a.total_k);
     int lk = clampi(__builtin_amdgcn_readfirstlane(a.cu_k[i + 1]), sk0, a.total_k) - sk0;
@@ -68,11 +66,11 @@ void attn_vfp8_window_kernel(const VfpAttn a, const int two, const int sel, cons
     const int win_hi = right < 0 ? lk : clampl(delta + right, -(long)lq - 1, lk);
     // [klo, khi]: the keys the tile's valid rows attend (rows without a key can only lead a sequence: r + win_hi < 0).  Workgroup-uniform,
     // as are the rule of the one-term sweep and the trip range derived from it
-    const int r_first = tq.tile * kVfpTile, r_last = min(r_first + kVfpTile, lq) - 1;
+    const int r_first = tq.tile * kFpvTile, r_last = min(r_first + kFpvTile, lq) - 1;
     const int klo = max(r_first + win_lo, 0), khi = min(r_last + win_hi, lk - 1);
     const int keys = max(khi - klo + 1, 0);
-    if (sel == kVfpSelMany && keys < a.two_term_keys) return;
-    if (sel == kVfpSelFew && keys >= a.two_term_keys) return;
+    if (sel == kFpvSelMany && keys < a.two_term_keys) return;
+    if (sel == kFpvSelFew && keys >= a.two_term_keys) return;
 
     const int kvh = h / (a.Hq / a.Hkv);
     const int qrow = r_first + wave * kQPerWave + ql;   // row within the sequence
@@ -80,16 +78,9 @@ void attn_vfp8_window_kernel(const VfpAttn a, const int two, const int sel, cons
     // (computed where they are used, before and after the sweep: the loop carries qrow alone)
     auto orow_of = [&]() -> long { return ((long)(tq.start + (qvalid ? qrow : 0)) * a.Hq + h) * (2L * D); };   // bytes: rows are a token stride apart
     auto lrow_of = [&]() -> long { return (long)h * a.total_q + tq.start + qrow; };                           // lse / path: [Hq, total_q]
-    if (keys == 0) {   // no key for any row of the tile (lk = 0 included): zero rows, LSE -inf, path code QATTN_PATH_ONE_TERM, no sweep
-        const long orow = orow_of(), lrow = lrow_of();
-        v16f z[MB];
-#pragma unroll
-        for (int m = 0; m < MB; m++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) z[m][r] = 0.0f;
-        store_o_rows<MB>(a.out, a.out_fmt, z, 0.0f, orow, hh, qvalid);
-        if (a.lse && hh == 0 && qvalid) a.lse[lrow] = -INFINITY;
-        if (a.path && hh == 0 && qvalid) a.path[lrow] = (unsigned char)QATTN_PATH_ONE_TERM;
+    if (keys == 0) {   // no key for any row of the tile (lk = 0 included): no sweep
+        const long lrow = lrow_of();
+        fpv_store_empty<D>(a.out, a.out_fmt, orow_of(), a.lse, lrow, a.path, lrow, hh, qvalid);
         return;
     }
     const int c_first = klo >> 6;                   // chunks c_first .. c_first + n_wg - 1 = khi / 64 < nch
@@ -97,78 +88,21 @@ void attn_vfp8_window_kernel(const VfpAttn a, const int two, const int sel, cons
     const int nch = (lk + 63) >> 6;                 // chunks of the sequence's images
 
     const long img = (long)a.Hkv * D * (sk0 + 64L * i) + (long)kvh * nch * CH + (wave << 10);
-    const unsigned char* kg_w = a.k8 + img;
-    const unsigned char* vg_w = a.v8 + img;
-    // stage(t) = {K chunk c_first + t, V chunk c_first + t} -> slot t & 1; every wave copies 2*RK x 1 KiB of it by LDS-DMA
-    const unsigned lane16 = (unsigned)lane << 4;
-    unsigned slot_next = 0;
-    auto dma_chunk = [&](int chunk) {
-        unsigned char* dst = smem + slot_next + (wave << 10);
-        const size_t coff = (size_t)chunk * CH + lane16;
-#pragma unroll
-        for (int r = 0; r < RK; r++) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kg_w + (coff + r * (NW * 1024))),
-                                             (__attribute__((address_space(3))) void*)(dst + r * (NW * 1024)), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vg_w + (coff + r * (NW * 1024))),
-                                             (__attribute__((address_space(3))) void*)(dst + CH + r * (NW * 1024)), 16, 0, 0);
-        }
-        slot_next ^= STAGE;
-    };
-    dma_chunk(c_first);
-
-    // Q^T fragments parked in this lane's own LDS slots
-    unsigned char* qbuf = smem + kVfpStages * STAGE + wave * (KS << 11) + (hh << 10) + (ql << 4);
-    {
-        const unsigned char* qp = a.q8 + (long)a.Hq * D * tq.start + ((long)h * tq.len + (qvalid ? qrow : 0)) * D + hh * 32;
-#pragma unroll
-        for (int s = 0; s < KS; s++) {
-            v4i lo = *reinterpret_cast<const v4i*>(qp + s * 64);
-            v4i hi = *reinterpret_cast<const v4i*>(qp + s * 64 + 16);
-            if (!qvalid) { lo = v4i{0, 0, 0, 0}; hi = v4i{0, 0, 0, 0}; }
-            *reinterpret_cast<v4i*>(qbuf + (s << 11)) = lo;
-            *reinterpret_cast<v4i*>(qbuf + (s << 11) + 512) = hi;
-        }
-    }
-    const float c = a.sm_log2e * a.sq[(long)i * a.Hq + h] * a.sk[(long)i * a.Hkv + kvh];
-
-    v16f o[MB];
-#pragma unroll
-    for (int m = 0; m < MB; m++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) o[m][r] = 0.0f;
-    v4f lsum = {0.0f, 0.0f, 0.0f, 0.0f};
-    int one;  // a word of A of the row-sum MFMA (see WaveState::lsum in qattn_attn_v2.hip): its eight words are equal
-    {
-        const int row = lane & 15, kg = lane >> 4;
-        one = ((row == 0 && !(kg & 1)) || (row == 1 && (kg & 1))) ? 0x38383838 : 0;
-    }
+    FpvRing<D> ring(smem, wave, lane, a.k8 + img, a.v8 + img);
+    ring.dma_chunk(c_first);
+    sw.park_q(a.q8 + (long)a.Hq * D * tq.start + ((long)h * tq.len + (qvalid ? qrow : 0)) * D + hh * 32, qvalid);
     constexpr float kNoKeyYet = -1.0e20f;   // below any raw score, and kNoKeyYet * c stays finite (header comment)
-    float m_run = kNoKeyYet, l_run = 0.0f;
-    float lim = kNoKeyYet, off8 = 0.0f;   // m_run + thr / c and the byte formula's additive constant (set by the row's first unmasked score)
-    constexpr float U16 = 1.0f / 65535.0f;
-    const float c8 = (8.0f * U16) * c;
-    const int frag_lane_off = (hh << 10) + (ql << 4);
+    sw.init_state(a.sm_log2e * a.sq[(long)i * a.Hq + h] * a.sk[(long)i * a.Hkv + kvh], kNoKeyYet);
+    const int one = fpv_ones_word(lane);   // (spread where it is used: header comment, registers)
 
-    for (int t = 0; t < n_wg; t++) {
+    for (int t = 0; t < n_wg; t++) {   // step t sweeps chunk c_first + t
         v8i qf[KS];
-#pragma unroll
-        for (int s = 0; s < KS; s++) qf[s] = lds_read_frag(qbuf + (s << 11));
-        wait_vmcnt<0>();                  // this wave's pieces of stage t have landed
-        __builtin_amdgcn_s_barrier();     // ... and everyone's; every wave is also done with stage t-1's slot
-        if (t + 1 < n_wg) dma_chunk(c_first + t + 1);
-        const unsigned char* kbuf = smem + (t & 1) * STAGE + frag_lane_off;
-        const unsigned char* vbuf = kbuf + CH;
-        // ---- S^T = K.Q^T
+        sw.read_q(qf);
+        sw.wait_stage();
+        if (t + 1 < n_wg) ring.dma_chunk(c_first + t + 1);
         v16f s0, s1;
-#pragma unroll
-        for (int r = 0; r < 16; r++) { s0[r] = 0.0f; s1[r] = 0.0f; }
-#pragma unroll
-        for (int s = 0; s < KS; s++) {
-            const v8i ka = lds_read_frag(kbuf + ((0 * KS + s) << 11)), kb = lds_read_frag(kbuf + ((1 * KS + s) << 11));
-            s0 = mfma_f8<FMT, FMT>(ka, qf[s], s0);
-            s1 = mfma_f8<FMT, FMT>(kb, qf[s], s1);
-        }
-        const v8i vf0 = lds_read_frag(vbuf), vf1 = lds_read_frag(vbuf + (1 << 11));
+        v8i vf0, vf1;
+        sw.qk(t, qf, s0, s1, vf0, vf1);
         // ---- the window's edges by token, and the ragged tail of the sequence's keys.  The condition is workgroup-uniform: over the
         // chunk's keys k0 .. k0 + 63 and the tile's valid rows, key - row spans [k0 - r_last, k0 + 63 - r_first]
         const int k0 = (c_first + t) * 64;
@@ -182,120 +116,26 @@ void attn_vfp8_window_kernel(const VfpAttn a, const int two, const int sel, cons
                 sx[r & 15] = (d < win_lo || d > hi_l) ? -INFINITY : sx[r & 15];
             }
         }
-        // ---- running max; rescale only when a row's max grew past the headroom of the shifted exponent
-        float mx = max32_after_mfma(s0, s1);
-        {
-            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = max3_raw(__uint_as_float(sw[0]), __uint_as_float(sw[1]), __uint_as_float(sw[1]));
-        }
-        if (__builtin_expect(__any(mx > lim) != 0, 0)) {   // (mx - m_run) c > thr: P' could overflow e4m3
-            const float m_new = fmaxf(m_run, mx);           // (a row with every score so far masked: mx = -inf, m_new = m_run = kNoKeyYet, alpha = 1)
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-#pragma unroll
-            for (int m = 0; m < MB; m++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) o[m][r] *= alpha;
-            if (BYTE) {
-                const float alpha16 = __shfl(alpha, (lane & 15) + 16);
-                lsum[0] *= alpha;
-                lsum[1] *= alpha16;
-            } else {
-                l_run *= alpha;
-            }
-            m_run = m_new;
-            lim = m_new + kRescaleThrByte / c;
-            off8 = __builtin_fmaf((-8.0f * U16) * m_new, c, (8.0f * kPShiftByte + 56.0f + kByteBias) * U16);
-        }
-        v8i pv, pl;
-        if (BYTE) {
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                pv[w] = vfp_byte_exp4(s0[4 * w], s0[4 * w + 1], s0[4 * w + 2], s0[4 * w + 3], c8, off8);
-                pv[4 + w] = vfp_byte_exp4(s1[4 * w], s1[4 * w + 1], s1[4 * w + 2], s1[4 * w + 3], c8, off8);
-            }
-        } else {
-            const float mc = kPShift - m_run * c;
-            float ls = 0.0f;
-#pragma unroll
-            for (int w = 0; w < 8; w++) {
-                const v16f& sx = w < 4 ? s0 : s1;
-                const int jj = w & 3;
-                float e[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) { e[u] = __builtin_amdgcn_exp2f(__builtin_fmaf(sx[4 * jj + u], c, mc)); ls += e[u]; }
-                int ph = cvt_pk_fp8<QATTN_FMT_E4M3, false>(e[0], e[1], 0);
-                ph = cvt_pk_fp8<QATTN_FMT_E4M3, true>(e[2], e[3], ph);
-                pv[w] = ph;
-                int plo = 0;
-                if (two) plo = lo_terms(e, ph, 0);
-                pl[w] = plo;
-            }
-            l_run += ls;
-        }
-        // ---- O^T += V^T.P^T, row sums (V's one scale per (sequence, head) is applied in the epilogue; the low term's 2^-5 rides in the scale word)
-        o[0] = mfma_f8<FMT, QATTN_FMT_E4M3>(vf0, pv, o[0]);
-        o[1] = mfma_f8<FMT, QATTN_FMT_E4M3>(vf1, pv, o[1]);
-        if (!BYTE && two) {
-            o[0] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vf0, pl, o[0], kScaleWordOne);
-            o[1] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vf1, pl, o[1], kScaleWordOne);
-        }
-#pragma unroll
-        for (int m = 2; m < MB; m += 2) {
-            const v8i va = lds_read_frag(vbuf + (m << 11)), vb = lds_read_frag(vbuf + ((m + 1) << 11));
-            o[m] = mfma_f8<FMT, QATTN_FMT_E4M3>(va, pv, o[m]);
-            o[m + 1] = mfma_f8<FMT, QATTN_FMT_E4M3>(vb, pv, o[m + 1]);
-            if (!BYTE && two) {
-                o[m] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(va, pl, o[m], kScaleWordOne);
-                o[m + 1] = mfma_pv_lo<FMT, QATTN_FMT_E4M3>(vb, pl, o[m + 1], kScaleWordOne);
-            }
-        }
-        if (BYTE) {
-            // the eight equal words are spread where they are used: carried through the loop they cost the D = 128 kernel 7 registers
-            // more than its 3 waves per SIMD leave, and the compiler kept them in scratch
-            int one_t = one;
-            asm volatile("" : "+v"(one_t));
-            v8i ones;
-#pragma unroll
-            for (int w = 0; w < 8; w++) ones[w] = one_t;
-            lsum = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ones, pv, lsum, QATTN_FMT_E4M3, QATTN_FMT_E4M3, 0, 0, 0, 0);
-        }
+        sw.softmax_pv(s0, s1, vf0, vf1, two, [&] { return fpv_spread_ones(one); });
     }
 
-    // ---- epilogue
-    float l_tot;
-    if (BYTE) {
-        const float s0l = __shfl(lsum[0], lane & 15), s1l = __shfl(lsum[1], lane & 15);
-        l_tot = (lane & 16) ? s1l : s0l;
-    } else {
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
-        l_tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-    }
+    // ---- epilogue (V's one scale per (sequence, head) is applied here)
+    const float l_tot = sw.row_sum();
     const long orow = orow_of(), lrow = lrow_of();
     const bool has_key = l_tot > 0.0f;   // (a row without a key inside a tile that sweeps: every P was 0 -- a zero row, LSE -inf)
     const float inv = has_key ? a.sv[(long)i * a.Hkv + kvh] / l_tot : 0.0f;
-    store_o_rows<MB>(a.out, a.out_fmt, o, inv, orow, hh, qvalid);
-    if (!BYTE && a.lse && hh == 0 && qvalid)  // ln sum_j exp(score_j) = ln2 * (m*c - shift) + ln(l')
-        a.lse[lrow] = has_key ? 0.6931471805599453f * (m_run * c - kPShift) + __logf(l_tot) : -INFINITY;
+    store_o_rows<MB>(a.out, a.out_fmt, sw.o, inv, orow, hh, qvalid);
+    if (!BYTE && a.lse && hh == 0 && qvalid) a.lse[lrow] = has_key ? 0.6931471805599453f * (sw.m_run * sw.c - kPShift) + __logf(l_tot) : -INFINITY;
     if (a.path && hh == 0 && qvalid) a.path[lrow] = (unsigned char)((!BYTE && two) ? QATTN_PATH_TWO_TERM : QATTN_PATH_ONE_TERM);
-}
-
-template <int D, int FMT, bool BYTE>
-static int launch_wfp_one(const VfpAttn& a, int two, int sel, int left, int right, hipStream_t st) {
-    constexpr int lds = vfp_lds_bytes(D);
-    auto kern = attn_vfp8_window_kernel<D, FMT, BYTE>;
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return QATTN_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a.Hq * a.nblk)), dim3(kVfpWaves * 64), lds, st, a, two, sel, left, right);
-    return QATTN_OK;
 }
 
 template <int D, int FMT>
 static int launch_wfp_attn(const VfpAttn& a, int precision, int left, int right, hipStream_t st) {
-    if (precision == QATTN_PRECISION_ACCURATE || a.total_k < a.two_term_keys)   // (no tile can attend two_term_keys keys: every one is two-term)
-        return launch_wfp_one<D, FMT, false>(a, 1, kVfpSelAll, left, right, st);
-    // FAST: the tiles that attend many keys on the one-term sweep (an LSE request: exact exponentials), the others two-term
-    int rc = a.lse ? launch_wfp_one<D, FMT, false>(a, 0, kVfpSelMany, left, right, st) : launch_wfp_one<D, FMT, true>(a, 0, kVfpSelMany, left, right, st);
-    if (rc == QATTN_OK) rc = launch_wfp_one<D, FMT, false>(a, 1, kVfpSelFew, left, right, st);
-    return rc;
+    // (total_k: more than any tile can attend)
+    return fpv_precision_ladder(precision, a.total_k, a.two_term_keys, a.lse != nullptr, [&](auto byte, int two, int sel) {
+        return fpv_launch(attn_vfp8_window_kernel<D, FMT, decltype(byte)::value>, (unsigned)(a.Hq * a.nblk), fpv_lds_bytes(D), st, a, two, sel, left,
+                          right);
+    });
 }
 
 template <int D>
