@@ -32,6 +32,10 @@ from .varlen import fp8_attn_varlen_window_pv_func, fp8_window_attn_pv_func  # n
 # block-sparse attention over 128 x 128 tiles of a boolean block mask: package attributes too, not in __all__
 from .block_sparse import BLOCK_M, BLOCK_N, fp8_block_sparse_attn_func, fp8_block_sparse_attn_pv_func  # noqa: E402
 
+# merging of attention states by their log-sum-exps, the dense fused step with its LSE, attention over several (k, v) sources: package
+# attributes too, not in __all__
+from .merge import fp8_attn_lse_func, fp8_attn_multi_kv_func, merge_attn_states  # noqa: E402
+
 __version__ = "0.1.0"
 
 __all__ = [

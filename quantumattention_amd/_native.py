@@ -48,7 +48,11 @@ EXPORTS = (
     "qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes", "qattn_fp8_quant_attention_varlen_fp8pv_smooth_workspace_bytes",
     "qattn_fp8_quant_attention_varlen_forward_fp8pv",
     "qattn_fp8_quant_attention_varlen_window_forward_fp8pv",
+    "qattn_attention_state_merge",
 )
+FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
+MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
+_MERGE_FMT = {torch.bfloat16: FMT_BF16, torch.float16: FMT_FP16, torch.float32: FMT_FP32}
 BLOCK_SPARSE_BLOCK = 128   # QATTN_BLOCK_SPARSE_BLOCK (include/qattn_block_sparse.h): rows / keys per mask block
 
 
@@ -200,6 +204,10 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_quant_attention_varlen_window_forward_fp8pv.restype = i
     L.qattn_fp8_quant_attention_varlen_window_forward_fp8pv.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, f, i,
                                                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    # merging of attention states (include/qattn_merge.h): n, o[], o_fmt[], o_strides[3n], lse[], lse_strides[3n], out, out_fmt, out_strides[3],
+    # lse_out, lse_out_strides[3], B, H, S, D, stream -- the tables are host arrays
+    L.qattn_attention_state_merge.restype = i
+    L.qattn_attention_state_merge.argtypes = [i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, i, i, i, i, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -922,3 +930,59 @@ def fp8_block_sparse_attention_fp8pv(q: torch.Tensor, k: torch.Tensor, v: torch.
         return out
     return ((out,) + ((lse,) if return_lse else ()) + ((q8, k8, v8, sq, sk, sv) + ((k_mean,) if smooth_k else ()) if return_quant else ())
             + ((path,) if return_path else ()))
+
+
+def merge_addressable(o: torch.Tensor) -> bool:
+    """An O tensor ([B,H,S,D] or packed [total,H,D]) the merge kernel addresses as it is (include/qattn_merge.h): head_dim innermost and
+    dense, base and rows 16-byte aligned, no negative stride."""
+    per16 = 16 // o.element_size()
+    return (o.stride(-1) == 1 and o.data_ptr() % 16 == 0
+            and all(o.shape[i] == 1 or (o.stride(i) >= 0 and o.stride(i) % per16 == 0) for i in range(o.dim() - 1)))
+
+
+def _merge_strides(o: torch.Tensor, lse: torch.Tensor):
+    """{batch, head, row} element strides of one state's O and LSE: dense [B,H,S,D] / [B,H,S], or packed [total,H,D] / [H,total] (B = 1)."""
+    if o.dim() == 4:
+        return (o.stride(0), o.stride(1), o.stride(2)), (lse.stride(0), lse.stride(1), lse.stride(2))
+    return (0, o.stride(1), o.stride(0)), (0, lse.stride(0), lse.stride(1))
+
+
+def attention_state_merge(outs, lses, *, out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None,
+                          out_dtype: Optional[torch.dtype] = None, return_lse: bool = True):
+    """qattn_attention_state_merge (include/qattn_merge.h) in one launch: 2 .. 8 partial states (outs[i], lses[i]) of the same queries over
+    disjoint key sets -> the state over the union.  outs[i]: [B,H,S,D] with lses[i] fp32 [B,H,S], or packed [total,H,D] with [H,total];
+    bf16 / fp16 / fp32, each its own; any strides with head_dim innermost and 16-byte rows go to the kernel as they are (the stride table
+    is built from the tensors; anything else is copied).  out / lse_out: caller's buffers (never copied: they must be addressable), e.g.
+    outs[0] / lses[0] themselves for the in-place accumulate; else fresh dense tensors of out_dtype (default: outs[0]'s).  The caller has
+    validated shapes and dtypes (merge.merge_attn_states).  Returns (out, lse_out), or out without return_lse (no LSE is written then,
+    unless lse_out is given)."""
+    n = len(outs)
+    _require(2 <= n <= MERGE_MAX_PARTIALS and len(lses) == n, f"attention_state_merge takes 2 .. {MERGE_MAX_PARTIALS} states per launch, got {n}")
+    o0 = outs[0]
+    _require(o0.is_cuda and o0.dim() in (3, 4) and lses[0].dim() == o0.dim() - 1, "states must be device tensors [B,H,S,D] / [B,H,S] or [total,H,D] / [H,total]")
+    outs = [o if merge_addressable(o) else o.contiguous() for o in outs]
+    dev = o0.device
+    if o0.dim() == 4:
+        B, H, S, D = o0.shape
+    else:
+        (S, H, D), B = o0.shape, 1
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(o0.shape, dtype=out_dtype or o0.dtype, device=dev)
+        if lse_out is None and return_lse:
+            lse_out = torch.empty(lses[0].shape, dtype=torch.float32, device=dev)
+        _require(out.shape == o0.shape and out.dtype in _MERGE_FMT and merge_addressable(out),
+                 "out must have the states' shape, head_dim innermost and dense, 16-byte aligned rows")
+        _require(lse_out is None or (lse_out.shape == lses[0].shape and lse_out.dtype == torch.float32), "lse_out must be float32 of the LSEs' shape")
+        if B * H * S == 0:
+            return (out, lse_out) if return_lse else out
+        o_str, l_str = zip(*(_merge_strides(o, l) for o, l in zip(outs, lses)))
+        out_str, lout_str = _merge_strides(out, lse_out if lse_out is not None else lses[0])
+        ll = ctypes.c_longlong
+        rc = lib().qattn_attention_state_merge(
+            n, (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), (ctypes.c_int * n)(*[_MERGE_FMT[o.dtype] for o in outs]),
+            (ll * (3 * n))(*[x for st in o_str for x in st]), (ctypes.c_void_p * n)(*[l.data_ptr() for l in lses]),
+            (ll * (3 * n))(*[x for st in l_str for x in st]), out.data_ptr(), _MERGE_FMT[out.dtype], (ll * 3)(*out_str), _ptr(lse_out),
+            (ll * 3)(*lout_str), B, H, S, D, _stream(o0))
+    _check(rc, "qattn_attention_state_merge")
+    return (out, lse_out) if return_lse else out

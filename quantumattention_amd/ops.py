@@ -7,7 +7,7 @@ Unlike the reference -- whose eager impl is aten SDPA on de-quantised inputs and
 only through an Inductor lowering (inductor/kernels/attention.py:1037-1065) -- the implementation here calls
 the hand-written gfx950 kernels through the C ABI directly.  There is no eager/CPU fallback at this level.
 """
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 
@@ -400,3 +400,31 @@ def _(query, key, value, block_mask, fp8_format="e4m3", numerics="compiled", ret
     out = query.new_empty((B, Hq, Sq, value.shape[3]), dtype=value.dtype)
     lse = query.new_empty((B, Hq, Sq) if return_lse else (0,), dtype=torch.float32)
     return out, lse
+
+
+@_custom_op("quantumattention_amd::attention_state_merge", mutates_args=(), device_types=("cuda",))
+def attention_state_merge(outs: Sequence[torch.Tensor], lses: Sequence[torch.Tensor],
+                          out_dtype: Optional[torch.dtype] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Merging of 2 .. 8 attention states in one launch (include/qattn_merge.h): outs[i] [B, H, S, D] with lses[i] fp32 [B, H, S], or packed
+    [total, H, D] with [H, total] -- partial results of the same queries over disjoint key sets, bf16 / fp16 / fp32 each, read through
+    their strides -> (out, lse) over the union, dense, out in out_dtype (default: outs[0]'s).  A partial whose LSE is -inf contributes
+    nothing; a row whose partials are all at -inf is a zero row with LSE -inf.  Reference implementation: merge.merge_attn_states_eager.
+    Arguments are validated by merge.merge_attn_states."""
+    return _native.attention_state_merge(list(outs), list(lses), out_dtype=out_dtype, return_lse=True)
+
+
+@_register_fake("quantumattention_amd::attention_state_merge")
+def _(outs, lses, out_dtype=None):
+    return (outs[0].new_empty(outs[0].shape, dtype=out_dtype or outs[0].dtype), lses[0].new_empty(lses[0].shape, dtype=torch.float32))
+
+
+@_custom_op("quantumattention_amd::attention_state_merge_", mutates_args=("acc", "acc_lse"), device_types=("cuda",))
+def attention_state_merge_(acc: torch.Tensor, acc_lse: torch.Tensor, outs: Sequence[torch.Tensor], lses: Sequence[torch.Tensor]) -> None:
+    """The same merge IN PLACE: the state (acc, acc_lse) is partial 0 and receives the result -- the accumulate of a ring step; outs / lses
+    are the 1 .. 7 further partials and may not overlap acc / acc_lse."""
+    _native.attention_state_merge([acc] + list(outs), [acc_lse] + list(lses), out=acc, lse_out=acc_lse)
+
+
+@_register_fake("quantumattention_amd::attention_state_merge_")
+def _(acc, acc_lse, outs, lses):
+    return None
