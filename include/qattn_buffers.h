@@ -1,7 +1,7 @@
 /*
  * qattn_buffers.h -- the BUFFER CONTRACT of every entry of qattn.h, qattn_strided.h, qattn_smooth.h, qattn_varlen.h, qattn_window.h and
- * qattn_block_sparse.h (documentation only: no declaration).  Held by tests/test_gpu_buffer_contract.py on guarded buffers of exactly
- * these sizes at exactly these alignments.
+ * qattn_block_sparse.h, and of qattn_rope.h (documentation only: no declaration).  Held by tests/test_gpu_buffer_contract.py (qattn_rope.h:
+ * tests/test_gpu_rope_buffer_contract.py) on guarded buffers of exactly these sizes at exactly these alignments.
  *
  *   sizes      a buffer of qattn_*_tensor_bytes / qattn_lse_row_stride / *_workspace_bytes bytes (or of the stated shape) suffices; no entry
  *              reads or writes a byte before a buffer's start or past its end, ragged last tiles included, and no result depends on bytes
@@ -34,6 +34,25 @@
  *   out / lse / row_path  every row of every sequence is written, rows whose window holds no key included (zeros / -inf / the tile's code).
  *   workspace  qattn_fp8_quant_attention_varlen_fp8pv_workspace_bytes (with k_mean: ..._fp8pv_smooth_workspace_bytes) bytes -- the packed
  *              FP8-PV entry's own two functions, there is no third --, 16-byte aligned; no result depends on what it held.
+ *
+ * qattn_rope_quant_qk_fp8 (qattn_rope.h; held by tests/test_gpu_rope_buffer_contract.py):
+ *   q, k       [B,Hq,Sq,D] / [B,Hkv,Skv,D] 16-bit, dense or the 6-stride views of qattn_strided.h, 16-byte aligned; read: the D elements of each row.
+ *   cos_*, sin_*  fp32, 16-byte aligned, rows read as float4: D/2 floats of each of the rows 0 .. S-1 of every batch element (batch stride 0: of
+ *              the one table), row s at base + b batch_stride + s row_stride; S rows suffice -- no row is read for the padding rows of a ragged
+ *              last 64-row tile, and no result depends on a byte outside those rows.
+ *   q8         qattn_fp8_tensor_bytes(QATTN_LAYOUT_ROWMAJOR, B, Hq, Sq, D) bytes, 16-byte aligned (8-byte stores); every byte written.
+ *   k8         qattn_fp8_tensor_bytes(k_layout, B, Hkv, Skv, D) bytes, 16-byte aligned; every byte written, KFRAG: the zero padding up to 64 keys included.
+ *   scale_q, scale_k  fp32 [B,H] or [B,H,S], 4-byte aligned; every element written.
+ *   workspace  qattn_rope_quant_qk_workspace_bytes(B, Hq, Hkv) bytes, 4-byte aligned (head-wise scales; not touched with token-wise ones); no
+ *              result depends on what it held.
+ *
+ * qattn_fp8_rope_quant_attention_forward (qattn_rope.h): q, k, tables, q8, k8 (KFRAG), scale_q, scale_k as above, all written;
+ *   v          dense [B,Hkv,Skv,D] 16-bit, 16-byte aligned.
+ *   v8         qattn_fp8_tensor_bytes(QATTN_LAYOUT_VFRAG, B, Hkv, Skv, D) bytes, 16-byte aligned, and scale_v fp32 [B,Hkv], 4-byte aligned: every
+ *              byte / element written when v_fmt = fp8_fmt; not touched (may be NULL) with a 16-bit V.
+ *   out        dense [B,Hq,Sq,D] in in_fmt, 16-byte aligned; lse (NULL or qattn_lse_row_stride floats per (b,h), 4-byte aligned): as
+ *              qattn_fp8_attention_forward -- every element of out, the Sq floats of each lse row.
+ *   workspace  qattn_fp8_rope_quant_attention_workspace_bytes(B, Hq, Hkv, Sq, Skv, D) bytes, 16-byte aligned; no result depends on what it held.
  */
 #ifndef QATTN_BUFFERS_H_
 #define QATTN_BUFFERS_H_

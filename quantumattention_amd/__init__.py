@@ -36,6 +36,9 @@ from .block_sparse import BLOCK_M, BLOCK_N, fp8_block_sparse_attn_func, fp8_bloc
 # attributes too, not in __all__
 from .merge import fp8_attn_lse_func, fp8_attn_multi_kv_func, merge_attn_states  # noqa: E402
 
+# rotary position embedding fused into the quant pre-pass of q and k (include/qattn_rope.h): package attributes too, not in __all__
+from .rope import apply_rope_eager, fp8_attn_rope_func, rope_quantize_fp8  # noqa: E402
+
 __version__ = "0.1.0"
 
 __all__ = [

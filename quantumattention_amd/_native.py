@@ -49,6 +49,8 @@ EXPORTS = (
     "qattn_fp8_quant_attention_varlen_forward_fp8pv",
     "qattn_fp8_quant_attention_varlen_window_forward_fp8pv",
     "qattn_attention_state_merge",
+    "qattn_rope_quant_qk_workspace_bytes", "qattn_rope_quant_qk_fp8",
+    "qattn_fp8_rope_quant_attention_workspace_bytes", "qattn_fp8_rope_quant_attention_forward",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -208,6 +210,18 @@ def lib() -> ctypes.CDLL:
     # lse_out, lse_out_strides[3], B, H, S, D, stream -- the tables are host arrays
     L.qattn_attention_state_merge.restype = i
     L.qattn_attention_state_merge.argtypes = [i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, i, i, i, i, vp]
+    # RoPE fused into the q / k pre-pass (include/qattn_rope.h): q, k, strides[6], in_fmt, then per table pair (cos, sin, batch stride, row
+    # stride) for q and for k, interleaved, ...
+    ll = ctypes.c_longlong
+    L.qattn_rope_quant_qk_workspace_bytes.restype = sz
+    L.qattn_rope_quant_qk_workspace_bytes.argtypes = [i, i, i]
+    L.qattn_rope_quant_qk_fp8.restype = i
+    L.qattn_rope_quant_qk_fp8.argtypes = [vp, vp, vp, i, vp, vp, ll, ll, vp, vp, ll, ll, i, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, i, vp, sz, vp]
+    L.qattn_fp8_rope_quant_attention_workspace_bytes.restype = sz
+    L.qattn_fp8_rope_quant_attention_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    L.qattn_fp8_rope_quant_attention_forward.restype = i
+    L.qattn_fp8_rope_quant_attention_forward.argtypes = [vp, vp, vp, vp, i, vp, vp, ll, ll, vp, vp, ll, ll, i, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                         i, i, i, i, i, i, i, i, i, i, i, f, i, i, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -986,3 +1000,101 @@ def attention_state_merge(outs, lses, *, out: Optional[torch.Tensor] = None, lse
             (ll * 3)(*lout_str), B, H, S, D, _stream(o0))
     _check(rc, "qattn_attention_state_merge")
     return (out, lse_out) if return_lse else out
+
+
+def rope_table_args(cos: torch.Tensor, sin: torch.Tensor):
+    """A cos / sin pair (fp32 [T, D/2] or [B, T, D/2], already validated by rope.py) as the C entries take it (include/qattn_rope.h):
+    (cos, sin, batch stride, row stride) in floats.  Slices and other views go as they are when the kernels can address them -- entries of a
+    row dense, base 16-byte aligned, strides multiples of 4 floats, the same strides for both tables; anything else is copied."""
+    def ok(t):
+        return (t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(t.shape[d] == 1 or t.stride(d) % 4 == 0 for d in range(t.dim() - 1)))
+    if not (ok(cos) and ok(sin) and cos.stride() == sin.stride()):
+        cos, sin = cos.contiguous(), sin.contiguous()
+    tb = cos.stride(0) if (cos.dim() == 3 and cos.shape[0] > 1) else 0
+    tr = cos.stride(-2) if cos.shape[-2] > 1 else cos.shape[-1]
+    return cos, sin, tb, tr
+
+
+def _strides6(q: torch.Tensor, k: torch.Tensor):
+    """{batch, head, row} element strides of q then of k for the RoPE entries (None: both dense)."""
+    if q.is_contiguous() and k.is_contiguous():
+        return None
+    D = q.shape[3]
+    dense = lambda t: (t.shape[1] * t.shape[2] * D, t.shape[2] * D, D)     # (a dimension of size 1 has no stride of its own)
+    return (ctypes.c_longlong * 6)(*[t.stride(i) if t.shape[i] > 1 else dense(t)[i] for t in (q, k) for i in (0, 1, 2)])
+
+
+def rope_quant_fp8(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, *, interleaved: bool = False, scaling: str = "head-wise",
+                   fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled", layout: int = LAYOUT_ROWMAJOR):
+    """qattn_rope_quant_qk_fp8 on ONE tensor x [B,H,S,D] (include/qattn_rope.h): rotate with the tables, quantise -> (payload, scale), the
+    payload row-major fp8 of x's shape or (layout = LAYOUT_KFRAG, through the entry's k slot) a flat uint8 KFRAG image."""
+    _require(x.is_cuda and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float16), "rope_quant_fp8 needs a 4-D bf16 / fp16 device tensor")
+    _require(layout in (LAYOUT_ROWMAJOR, LAYOUT_KFRAG), "rope_quant_fp8 writes the row-major or the KFRAG layout")
+    x = x if _strided_ok(x) else x.contiguous()
+    B, H, S, D = x.shape
+    L = lib()
+    mode = _scale_mode(scaling)
+    cos, sin, tb, tr = rope_table_args(cos, sin)
+    dev = x.device
+    with torch.cuda.device(dev):
+        if layout == LAYOUT_ROWMAJOR:
+            out = torch.empty((B, H, S, D), dtype=fp8_dtype, device=dev)
+        else:
+            out = torch.empty((L.qattn_fp8_tensor_bytes(layout, B, H, S, D),), dtype=torch.uint8, device=dev)
+        scale = torch.empty((B, H) if mode == SCALE_HEAD else (B, H, S), dtype=torch.float32, device=dev)
+        ws_bytes = L.qattn_rope_quant_qk_workspace_bytes(B, H, H)
+        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+        strides = _strides6(x, x)
+        as_k = layout == LAYOUT_KFRAG
+        tab = (cos.data_ptr(), sin.data_ptr(), tb, tr)
+        none = (None, None, 0, 0)
+        rc = L.qattn_rope_quant_qk_fp8(None if as_k else x.data_ptr(), x.data_ptr() if as_k else None, strides, fmt_of(x.dtype),
+                                       *(none if as_k else tab), *(tab if as_k else none), int(bool(interleaved)),
+                                       None if as_k else out.data_ptr(), out.data_ptr() if as_k else None, layout,
+                                       None if as_k else scale.data_ptr(), scale.data_ptr() if as_k else None, B, H, H, S, S, D,
+                                       fmt_of(fp8_dtype), mode, _numerics(numerics), ws.data_ptr(), ws_bytes, _stream(x))
+    _check(rc, "qattn_rope_quant_qk_fp8")
+    return out, scale
+
+
+def fp8_rope_quant_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos_q: torch.Tensor, sin_q: torch.Tensor,
+                             cos_k: torch.Tensor, sin_k: torch.Tensor, *, interleaved: bool = False, is_causal: bool = False,
+                             scaling: str = "head-wise", fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled", sm_scale: float = 0.0,
+                             precision: str = "auto", pv_16bit: bool = False, return_lse: bool = False, return_quant: bool = False):
+    """qattn_fp8_rope_quant_attention_forward (include/qattn_rope.h): unrotated 16-bit q, k with their cos / sin tables, 16-bit v -> attention
+    output, in one C call: the RoPE + quantise pre-pass of q and k, V through the head-wise quantiser (pv_16bit: kept 16-bit), then the
+    existing fp8 attention entry.  q and k may be strided views (include/qattn_strided.h's rules); v is made dense.
+    return_quant (test output): also a dict of q8 (row-major fp8), k8 (KFRAG bytes), scale_q, scale_k, and v8 / scale_v with an fp8 V.
+    Returns out, or a tuple of out, [lse], [quant]."""
+    B, Hq, Hkv, Sq, Skv, D = _check_qkv(q, k, v)
+    q, k = (t if _strided_ok(t) else t.contiguous() for t in (q, k))
+    v = v.contiguous()
+    L = lib()
+    mode = _scale_mode(scaling)
+    dev = q.device
+    cos_q, sin_q, qtb, qtr = rope_table_args(cos_q, sin_q)
+    cos_k, sin_k, ktb, ktr = rope_table_args(cos_k, sin_k)
+    with torch.cuda.device(dev):
+        out = torch.empty((B, Hq, Sq, D), dtype=q.dtype, device=dev)
+        lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev) if return_lse else None
+        q8 = torch.empty((B, Hq, Sq, D), dtype=fp8_dtype, device=dev)
+        kf = torch.empty((L.qattn_fp8_tensor_bytes(LAYOUT_KFRAG, B, Hkv, Skv, D),), dtype=torch.uint8, device=dev)
+        sq = torch.empty((B, Hq) if mode == SCALE_HEAD else (B, Hq, Sq), dtype=torch.float32, device=dev)
+        sk = torch.empty((B, Hkv) if mode == SCALE_HEAD else (B, Hkv, Skv), dtype=torch.float32, device=dev)
+        vf = sv = None
+        if not pv_16bit:
+            vf = torch.empty((L.qattn_fp8_tensor_bytes(LAYOUT_VFRAG, B, Hkv, Skv, D),), dtype=torch.uint8, device=dev)
+            sv = torch.empty((B, Hkv), dtype=torch.float32, device=dev)
+        ws_bytes = L.qattn_fp8_rope_quant_attention_workspace_bytes(B, Hq, Hkv, Sq, Skv, D)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        rc = L.qattn_fp8_rope_quant_attention_forward(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), _strides6(q, k), fmt_of(q.dtype), cos_q.data_ptr(), sin_q.data_ptr(), qtb, qtr,
+            cos_k.data_ptr(), sin_k.data_ptr(), ktb, ktr, int(bool(interleaved)), out.data_ptr(), _ptr(lse), q8.data_ptr(), kf.data_ptr(),
+            _ptr(vf), sq.data_ptr(), sk.data_ptr(), _ptr(sv), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype),
+            fmt_of(q.dtype) if pv_16bit else fmt_of(fp8_dtype), mode, _numerics(numerics), int(is_causal), float(sm_scale),
+            _precision(precision), LSE_NATURAL, ws.data_ptr(), ws_bytes, _stream(q))
+    _check(rc, "qattn_fp8_rope_quant_attention_forward")
+    if not (return_lse or return_quant):
+        return out
+    quant = {"q8": q8, "k8": kf, "v8": vf, "scale_q": sq, "scale_k": sk, "scale_v": sv}
+    return (out,) + ((lse,) if return_lse else ()) + ((quant,) if return_quant else ())

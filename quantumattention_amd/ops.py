@@ -428,3 +428,46 @@ def attention_state_merge_(acc: torch.Tensor, acc_lse: torch.Tensor, outs: Seque
 @_register_fake("quantumattention_amd::attention_state_merge_")
 def _(acc, acc_lse, outs, lses):
     return None
+
+
+@_custom_op("quantumattention_amd::fp8_rope_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_rope_attention_forward(
+    query: torch.Tensor,
+    key: torch.Tensor,
+    value: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    cos_k: Optional[torch.Tensor] = None,
+    sin_k: Optional[torch.Tensor] = None,
+    interleaved: bool = False,
+    is_causal: bool = False,
+    scaling_method: str = "head-wise",
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    precision: str = "auto",
+    pv_16bit: bool = False,
+    return_lse: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """FP8 attention on UNROTATED 16-bit query / key (include/qattn_rope.h): query [B, Hq, Sq, D], key / value [B, Hkv, Skv, D] bf16 / fp16;
+    cos / sin fp32 [T, D/2] or [B, T, D/2] rotate the query, cos_k / sin_k (default: the query's) the key, inside the quant pre-pass;
+    interleaved: pairs (2i, 2i+1) instead of (i, i + D/2).  Then the fp8 attention entry on the result (pv_16bit: 16-bit P on the 16-bit
+    value).  Returns (out [B, Hq, Sq, D], lse fp32 [B, Hq, Sq] -- or an empty [0] tensor without return_lse).  Reference implementation:
+    rope.apply_rope_eager + the separate calls.  Arguments are validated by rope.fp8_attn_rope_func."""
+    res = _native.fp8_rope_quant_attention(
+        query, key, value, cos, sin, cos if cos_k is None else cos_k, sin if sin_k is None else sin_k, interleaved=interleaved,
+        is_causal=is_causal, scaling=scaling_method, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics,
+        sm_scale=0.0 if scale is None else float(scale), precision=precision, pv_16bit=pv_16bit, return_lse=return_lse)
+    if return_lse:
+        return res
+    return res, torch.empty((0,), dtype=torch.float32, device=query.device)
+
+
+@_register_fake("quantumattention_amd::fp8_rope_attention_forward")
+def _(query, key, value, cos, sin, cos_k=None, sin_k=None, interleaved=False, is_causal=False, scaling_method="head-wise", fp8_format="e4m3",
+      numerics="compiled", precision="auto", pv_16bit=False, return_lse=False, *, scale=None):
+    B, Hq, Sq = query.shape[0], query.shape[1], query.shape[2]
+    out = query.new_empty((B, Hq, Sq, value.shape[3]), dtype=value.dtype)
+    lse = query.new_empty((B, Hq, Sq) if return_lse else (0,), dtype=torch.float32)
+    return out, lse
