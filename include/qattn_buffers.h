@@ -1,7 +1,8 @@
 /*
  * qattn_buffers.h -- the BUFFER CONTRACT of every entry of qattn.h, qattn_strided.h, qattn_smooth.h, qattn_varlen.h, qattn_window.h and
- * qattn_block_sparse.h, and of qattn_rope.h (documentation only: no declaration).  Held by tests/test_gpu_buffer_contract.py (qattn_rope.h:
- * tests/test_gpu_rope_buffer_contract.py) on guarded buffers of exactly these sizes at exactly these alignments.
+ * qattn_block_sparse.h, and of qattn_rope.h and qattn_splitkv.h (documentation only: no declaration).  Held by
+ * tests/test_gpu_buffer_contract.py (qattn_rope.h: tests/test_gpu_rope_buffer_contract.py; qattn_splitkv.h:
+ * tests/test_gpu_splitkv_buffer_contract.py) on guarded buffers of exactly these sizes at exactly these alignments.
  *
  *   sizes      a buffer of qattn_*_tensor_bytes / qattn_lse_row_stride / *_workspace_bytes bytes (or of the stated shape) suffices; no entry
  *              reads or writes a byte before a buffer's start or past its end, ragged last tiles included, and no result depends on bytes
@@ -53,6 +54,25 @@
  *   out        dense [B,Hq,Sq,D] in in_fmt, 16-byte aligned; lse (NULL or qattn_lse_row_stride floats per (b,h), 4-byte aligned): as
  *              qattn_fp8_attention_forward -- every element of out, the Sq floats of each lse row.
  *   workspace  qattn_fp8_rope_quant_attention_workspace_bytes(B, Hq, Hkv, Sq, Skv, D) bytes, 16-byte aligned; no result depends on what it held.
+ *
+ * qattn_fp8_attention_splitkv_forward (qattn_splitkv.h; held by tests/test_gpu_splitkv_buffer_contract.py), rows = B Hq Sq, ns = num_splits:
+ *   q16        dense [B,Hq,Sq,D] 16-bit, 16-byte aligned; read: every element.
+ *   k8_kfrag, v8_vfrag  qattn_fp8_tensor_bytes(QATTN_LAYOUT_KFRAG / _VFRAG, B, Hkv, Skv, D) bytes each, 16-byte aligned; read: of batch element b
+ *              the 64-key chunks 0 .. ceil(L_b / 64) - 1 of every kv head (causal: up to the last chunk a row attends), no other byte.  In
+ *              the chunk that holds key L_b the bytes of the keys >= L_b are read and influence no result, whatever they hold (NaN bytes
+ *              included): K's scores are replaced by -inf, V's bytes are zeroed before the product.
+ *   scale_k, scale_v  fp32 [B,Hkv], 4-byte aligned.   seqused_k: NULL or int32 [B], 4-byte aligned.
+ *   out        dense [B,Hq,Sq,D] in in_fmt, 16-byte aligned; every element written (rows without a key: zeros).
+ *   lse        NULL or fp32 [B,Hq,Sq], 4-byte aligned; every element written (rows without a key: -inf) -- except by a FAST call with ns = 1,
+ *              whose one-term workgroups (byte exponentials) would not write theirs: FAST with lse != NULL runs exact exponentials instead.
+ *   q8         NULL or qattn_fp8_tensor_bytes(QATTN_LAYOUT_ROWMAJOR, B, Hq, Sq, D) bytes, 16-byte aligned; scale_q: NULL or fp32 [B,Hq], 4-byte
+ *              aligned; row_path: NULL or uint8 [B,Hq,Sq], 1-byte aligned.  Every byte / element written.
+ *   partial_o  NULL or fp32 [ns,B,Hq,Sq,D], 16-byte aligned; partial_lse: NULL or fp32 [ns,B,Hq,Sq], 4-byte aligned; partial_path: NULL or
+ *              uint8 [ns,B,Hq,Sq], 1-byte aligned.  ns > 1: every element written (a split that gave a row no key: zeros, -inf,
+ *              QATTN_PATH_ONE_TERM) and left as the sweep wrote it (the merge accumulates in the workspace).  ns = 1: not touched.
+ *   workspace  qattn_fp8_attention_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, num_splits) bytes (num_splits as passed: 0 sizes it for the most splits), 16-byte aligned, always needed (it holds
+ *              whatever optional output is NULL, the pre-pass words and, for ns > 8, the merge's fp32 accumulator); no result depends on
+ *              what it held.
  */
 #ifndef QATTN_BUFFERS_H_
 #define QATTN_BUFFERS_H_

@@ -39,6 +39,9 @@ from .merge import fp8_attn_lse_func, fp8_attn_multi_kv_func, merge_attn_states 
 # rotary position embedding fused into the quant pre-pass of q and k (include/qattn_rope.h): package attributes too, not in __all__
 from .rope import apply_rope_eager, fp8_attn_rope_func, rope_quantize_fp8  # noqa: E402
 
+# split-KV attention of short queries over prepared (quantised once) K / V (include/qattn_splitkv.h): package attributes too, not in __all__
+from .splitkv import PreparedKV, fp8_attn_splitkv_func, prepare_kv_fp8  # noqa: E402
+
 __version__ = "0.1.0"
 
 __all__ = [

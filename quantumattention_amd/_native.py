@@ -51,11 +51,13 @@ EXPORTS = (
     "qattn_attention_state_merge",
     "qattn_rope_quant_qk_workspace_bytes", "qattn_rope_quant_qk_fp8",
     "qattn_fp8_rope_quant_attention_workspace_bytes", "qattn_fp8_rope_quant_attention_forward",
+    "qattn_fp8_attention_splitkv_workspace_bytes", "qattn_splitkv_auto_splits", "qattn_fp8_attention_splitkv_forward",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
 _MERGE_FMT = {torch.bfloat16: FMT_BF16, torch.float16: FMT_FP16, torch.float32: FMT_FP32}
 BLOCK_SPARSE_BLOCK = 128   # QATTN_BLOCK_SPARSE_BLOCK (include/qattn_block_sparse.h): rows / keys per mask block
+SPLITKV_MAX_SPLITS = 64    # QATTN_SPLITKV_MAX_SPLITS (include/qattn_splitkv.h)
 
 
 class PathDesc(ctypes.Structure):
@@ -222,6 +224,16 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_rope_quant_attention_forward.restype = i
     L.qattn_fp8_rope_quant_attention_forward.argtypes = [vp, vp, vp, vp, i, vp, vp, ll, ll, vp, vp, ll, ll, i, vp, vp, vp, vp, vp, vp, vp, vp,
                                                          i, i, i, i, i, i, i, i, i, i, i, f, i, i, vp, sz, vp]
+    # split-KV attention over prepared K / V (include/qattn_splitkv.h): q16, in_fmt, k8_kfrag, v8_vfrag, scale_k, scale_v, out, lse, seqused_k,
+    # B, Hq, Hkv, Sq, Skv, D, fp8_fmt, numerics, is_causal, sm_scale, precision, num_splits, q8, scale_q, row_path, partial_o, partial_lse,
+    # partial_path, workspace, workspace_bytes, stream
+    L.qattn_fp8_attention_splitkv_workspace_bytes.restype = sz
+    L.qattn_fp8_attention_splitkv_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
+    L.qattn_splitkv_auto_splits.restype = i
+    L.qattn_splitkv_auto_splits.argtypes = [i, i, i, i, i, i, i]
+    L.qattn_fp8_attention_splitkv_forward.restype = i
+    L.qattn_fp8_attention_splitkv_forward.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f, i, i,
+                                                      vp, vp, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1098,3 +1110,67 @@ def fp8_rope_quant_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
         return out
     quant = {"q8": q8, "k8": kf, "v8": vf, "scale_q": sq, "scale_k": sk, "scale_v": sv}
     return (out,) + ((lse,) if return_lse else ()) + ((quant,) if return_quant else ())
+
+
+def splitkv_auto_splits(B: int, Hq: int, Hkv: int, Sq: int, Skv: int, D: int, num_cus: int) -> int:
+    """qattn_splitkv_auto_splits (include/qattn_splitkv.h): the num_splits = 0 rule, a pure host function of the shape and the CU count."""
+    return int(lib().qattn_splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, num_cus))
+
+
+def fp8_attention_splitkv(q: torch.Tensor, k_frag: torch.Tensor, v_frag: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor, *,
+                          Skv: int, fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled", is_causal: bool = False,
+                          sm_scale: float = 0.0, precision: str = "accurate", num_splits: int = 0,
+                          seqused_k: Optional[torch.Tensor] = None, return_lse: bool = False, return_partials: bool = False,
+                          return_quant: bool = False, return_path: bool = False):
+    """Split-KV attention over prepared K / V (qattn_fp8_attention_splitkv_forward, include/qattn_splitkv.h).  q [B, Hq, Sq, D] bf16 / fp16;
+    k_frag / v_frag: the KFRAG / VFRAG images (flat uint8) of [B, Hkv, Skv, D] in fp8_dtype with scale_k / scale_v fp32 [B, Hkv];
+    seqused_k int32 [B] on the device or None.  num_splits 0: the auto rule on the device's CU count (resolved here, on the host).
+    Returns out, or a tuple of out, [lse], [partial_o fp32 [ns, B, Hq, Sq, D], partial_lse [ns, B, Hq, Sq], partial_path uint8 -- three
+    empty tensors when the call ran one split], [q8, scale_q], [row_path uint8 [B, Hq, Sq]]."""
+    _require(precision in ("fast", "accurate"), f"Unsupported precision for the split-KV entry: {precision!r} (expected 'fast' or 'accurate')")
+    _require(q.is_cuda and q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16), "query must be a 4-D bf16 / fp16 device tensor")
+    _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
+    q = q.contiguous()
+    B, Hq, Sq, D = q.shape
+    _require(scale_k.dim() == 2 and scale_k.shape[0] == B and scale_k.shape == scale_v.shape, "scale_k / scale_v must be fp32 [B, Hkv]")
+    Hkv = scale_k.shape[1]
+    _require(Hkv > 0 and Hq % Hkv == 0, f"Hq={Hq} is not a multiple of Hkv={Hkv}")
+    L = lib()
+    dev = q.device
+    for name, img, layout in (("k", k_frag, LAYOUT_KFRAG), ("v", v_frag, LAYOUT_VFRAG)):
+        _require(img.device == dev and img.dtype == torch.uint8 and img.is_contiguous()
+                 and img.numel() == L.qattn_fp8_tensor_bytes(layout, B, Hkv, Skv, D), f"the prepared {name} image does not fit [B={B}, Hkv={Hkv}, Skv={Skv}, D={D}]")
+    for name, sc in (("scale_k", scale_k), ("scale_v", scale_v)):
+        _require(sc.dtype == torch.float32 and sc.device == dev and sc.is_contiguous(), f"{name} must be a dense float32 tensor on {dev}")
+    if seqused_k is not None:
+        _require(seqused_k.dtype == torch.int32 and seqused_k.device == dev and tuple(seqused_k.shape) == (B,) and seqused_k.is_contiguous(),
+                 f"seqused_k must be a dense int32 [B] tensor on {dev}")
+    ns = int(num_splits)
+    if ns == 0:
+        ns = splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, torch.cuda.get_device_properties(dev).multi_processor_count)
+    with torch.cuda.device(dev):
+        out = torch.empty((B, Hq, Sq, D), dtype=q.dtype, device=dev)
+        lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev) if return_lse else None
+        po = plse = ppath = q8 = sq = path = None
+        if return_partials:
+            n = ns if ns > 1 else 0
+            po = torch.empty((n, B, Hq, Sq, D), dtype=torch.float32, device=dev)
+            plse = torch.empty((n, B, Hq, Sq), dtype=torch.float32, device=dev)
+            ppath = torch.empty((n, B, Hq, Sq), dtype=torch.uint8, device=dev)
+        if return_quant:
+            q8 = torch.empty((B, Hq, Sq, D), dtype=fp8_dtype, device=dev)
+            sq = torch.empty((B, Hq), dtype=torch.float32, device=dev)
+        if return_path:
+            path = torch.empty((B, Hq, Sq), dtype=torch.uint8, device=dev)
+        ws_bytes = L.qattn_fp8_attention_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, ns)
+        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+        live = lambda t: _ptr(t) if t is not None and t.numel() else None
+        rc = L.qattn_fp8_attention_splitkv_forward(
+            q.data_ptr(), fmt_of(q.dtype), k_frag.data_ptr(), v_frag.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(),
+            _ptr(lse), _ptr(seqused_k), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), int(bool(is_causal)), float(sm_scale),
+            _precision(precision), ns, _ptr(q8), _ptr(sq), _ptr(path), live(po), live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
+    _check(rc, "qattn_fp8_attention_splitkv_forward")
+    if not (return_lse or return_partials or return_quant or return_path):
+        return out
+    return ((out,) + ((lse,) if return_lse else ()) + ((po, plse, ppath) if return_partials else ()) + ((q8, sq) if return_quant else ())
+            + ((path,) if return_path else ()))

@@ -471,3 +471,54 @@ def _(query, key, value, cos, sin, cos_k=None, sin_k=None, interleaved=False, is
     out = query.new_empty((B, Hq, Sq, value.shape[3]), dtype=value.dtype)
     lse = query.new_empty((B, Hq, Sq) if return_lse else (0,), dtype=torch.float32)
     return out, lse
+
+
+@_custom_op("quantumattention_amd::fp8_splitkv_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_splitkv_attention_forward(
+    query: torch.Tensor,
+    k_frag: torch.Tensor,
+    v_frag: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    seqused_k: Optional[torch.Tensor],
+    seqlen_k: int,
+    num_splits: int,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    is_causal: bool = False,
+    precision: str = "accurate",
+    return_lse: bool = False,
+    return_partials: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Split-KV FP8 attention of a short query over PREPARED keys / values (include/qattn_splitkv.h): query [B, Hq, Sq, D] bf16 / fp16;
+    k_frag / v_frag the KFRAG / VFRAG images (flat uint8) of [B, Hkv, seqlen_k, D] with scale_k / scale_v fp32 [B, Hkv]
+    (splitkv.prepare_kv_fp8); seqused_k int32 [B] or None, read on the device; num_splits 1 .. 64 (the caller has resolved the auto rule:
+    the partials' shape depends on it).  Returns (out, lse, partial_o, partial_lse, partial_path); what was not asked for, and the
+    partials of a one-split call, are empty tensors.  Reference implementation: splitkv._splitkv_eager.  Arguments are validated by
+    splitkv.fp8_attn_splitkv_func."""
+    res = _native.fp8_attention_splitkv(
+        query, k_frag, v_frag, scale_k, scale_v, Skv=seqlen_k, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics,
+        is_causal=is_causal, sm_scale=0.0 if scale is None else float(scale), precision=precision, num_splits=num_splits,
+        seqused_k=seqused_k, return_lse=return_lse, return_partials=return_partials)
+    res = res if isinstance(res, tuple) else (res,)
+    none_f = lambda: torch.empty((0,), dtype=torch.float32, device=query.device)
+    out = res[0]
+    lse = res[1] if return_lse else none_f()
+    parts = res[-3:] if return_partials else (none_f(), none_f(), torch.empty((0,), dtype=torch.uint8, device=query.device))
+    return (out, lse) + tuple(parts)
+
+
+@_register_fake("quantumattention_amd::fp8_splitkv_attention_forward")
+def _(query, k_frag, v_frag, scale_k, scale_v, seqused_k, seqlen_k, num_splits, fp8_format="e4m3", numerics="compiled", is_causal=False,
+      precision="accurate", return_lse=False, return_partials=False, *, scale=None):
+    B, Hq, Sq, D = query.shape
+    out = query.new_empty((B, Hq, Sq, D))
+    lse = query.new_empty((B, Hq, Sq) if return_lse else (0,), dtype=torch.float32)
+    n = num_splits if num_splits > 1 else 0
+    if return_partials:
+        return (out, lse, query.new_empty((n, B, Hq, Sq, D), dtype=torch.float32), query.new_empty((n, B, Hq, Sq), dtype=torch.float32),
+                query.new_empty((n, B, Hq, Sq), dtype=torch.uint8))
+    return (out, lse, query.new_empty((0,), dtype=torch.float32), query.new_empty((0,), dtype=torch.float32),
+            query.new_empty((0,), dtype=torch.uint8))
