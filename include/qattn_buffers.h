@@ -1,8 +1,8 @@
 /*
  * qattn_buffers.h -- the BUFFER CONTRACT of every entry of qattn.h, qattn_strided.h, qattn_smooth.h, qattn_varlen.h, qattn_window.h and
- * qattn_block_sparse.h, and of qattn_rope.h and qattn_splitkv.h (documentation only: no declaration).  Held by
+ * qattn_block_sparse.h, and of qattn_rope.h, qattn_splitkv.h and qattn_kvcache.h (documentation only: no declaration).  Held by
  * tests/test_gpu_buffer_contract.py (qattn_rope.h: tests/test_gpu_rope_buffer_contract.py; qattn_splitkv.h:
- * tests/test_gpu_splitkv_buffer_contract.py) on guarded buffers of exactly these sizes at exactly these alignments.
+ * tests/test_gpu_splitkv_buffer_contract.py; qattn_kvcache.h: tests/test_gpu_kvcache_buffer_contract.py) on guarded buffers of exactly these sizes at exactly these alignments.
  *
  *   sizes      a buffer of qattn_*_tensor_bytes / qattn_lse_row_stride / *_workspace_bytes bytes (or of the stated shape) suffices; no entry
  *              reads or writes a byte before a buffer's start or past its end, ragged last tiles included, and no result depends on bytes
@@ -73,6 +73,19 @@
  *   workspace  qattn_fp8_attention_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, num_splits) bytes (num_splits as passed: 0 sizes it for the most splits), 16-byte aligned, always needed (it holds
  *              whatever optional output is NULL, the pre-pass words and, for ns > 8, the merge's fp32 accumulator); no result depends on
  *              what it held.
+ *
+ * qattn_kv_cache_append_fp8 (qattn_kvcache.h; held by tests/test_gpu_kvcache_buffer_contract.py), p_b / n_b as the header defines them:
+ *   k16, v16   [B,Hkv,T,D] 16-bit through the element strides {batch, head, token} of k_strides3 / v_strides3, head_dim innermost and dense;
+ *              base 16-byte aligned, every stride a NON-NEGATIVE multiple of 8 elements (16-byte loads; anything else: QATTN_ERR_INVALID_ARG).  Read: the D elements of the rows of the tokens
+ *              t < min(n_b, capacity - p_b) of batch element b, no other byte -- not the rows of dropped tokens, not the pads between rows.
+ *   k8_kfrag, v8_vfrag  qattn_fp8_tensor_bytes(QATTN_LAYOUT_KFRAG / _VFRAG, B, Hkv, capacity, D) bytes each, 16-byte aligned.  Written: the D bytes
+ *              of each of the keys p_b .. min(p_b + n_b, capacity) - 1 of every kv head of batch element b (16-byte, 8-byte, 4-byte and
+ *              single-byte stores); every other byte -- other keys of the same chunk, the zero padding up to 64 keys -- keeps what it held.
+ *              Never read: no result depends on what the images held.
+ *   scale_k, scale_v  fp32 [B,Hkv], 4-byte aligned; read.
+ *   seqlens    int32 [B], 4-byte aligned; read, and with advance != 0 every element rewritten (min(p_b + n_b, capacity): a value outside
+ *              [0, capacity] comes back clamped); advance = 0: not written.   new_lens: NULL or int32 [B], 4-byte aligned; read.
+ *   No workspace.
  */
 #ifndef QATTN_BUFFERS_H_
 #define QATTN_BUFFERS_H_

@@ -42,6 +42,9 @@ from .rope import apply_rope_eager, fp8_attn_rope_func, rope_quantize_fp8  # noq
 # split-KV attention of short queries over prepared (quantised once) K / V (include/qattn_splitkv.h): package attributes too, not in __all__
 from .splitkv import PreparedKV, fp8_attn_splitkv_func, prepare_kv_fp8  # noqa: E402
 
+# an appendable FP8 K/V cache with fixed scales for the split-KV entry (include/qattn_kvcache.h): package attributes too, not in __all__
+from .kvcache import KVCacheFP8, alloc_kv_cache_fp8, kv_cache_append_fp8, kv_cache_from_prefill_fp8  # noqa: E402
+
 __version__ = "0.1.0"
 
 __all__ = [

@@ -52,6 +52,7 @@ EXPORTS = (
     "qattn_rope_quant_qk_workspace_bytes", "qattn_rope_quant_qk_fp8",
     "qattn_fp8_rope_quant_attention_workspace_bytes", "qattn_fp8_rope_quant_attention_forward",
     "qattn_fp8_attention_splitkv_workspace_bytes", "qattn_splitkv_auto_splits", "qattn_fp8_attention_splitkv_forward",
+    "qattn_kv_cache_append_fp8",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -234,6 +235,10 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_attention_splitkv_forward.restype = i
     L.qattn_fp8_attention_splitkv_forward.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f, i, i,
                                                       vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    # appending to an FP8 K/V cache with fixed scales (include/qattn_kvcache.h): k16, v16, in_fmt, k_strides3, v_strides3, k8_kfrag, v8_vfrag,
+    # scale_k, scale_v, seqlens, new_lens, advance, B, Hkv, T, capacity, D, fp8_fmt, stream
+    L.qattn_kv_cache_append_fp8.restype = i
+    L.qattn_kv_cache_append_fp8.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1174,3 +1179,40 @@ def fp8_attention_splitkv(q: torch.Tensor, k_frag: torch.Tensor, v_frag: torch.T
         return out
     return ((out,) + ((lse,) if return_lse else ()) + ((po, plse, ppath) if return_partials else ()) + ((q8, sq) if return_quant else ())
             + ((path,) if return_path else ()))
+
+
+def kv_append_addressable(t: torch.Tensor) -> bool:
+    """A 4-D view [B, Hkv, T, D] qattn_kv_cache_append_fp8 reads in place (include/qattn_kvcache.h): head_dim innermost and dense, every
+    other stride of a dimension longer than 1 a non-negative multiple of 8 elements, base 16-byte aligned (rows 16-byte aligned)."""
+    return (t.dim() == 4 and (t.shape[3] == 1 or t.stride(3) == 1) and t.data_ptr() % 16 == 0
+            and all(t.shape[i] == 1 or (t.stride(i) >= 0 and t.stride(i) % 8 == 0) for i in (0, 1, 2)))
+
+
+def kv_cache_append_fp8(k_frag: torch.Tensor, v_frag: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor, seqlens: torch.Tensor,
+                        k_new: torch.Tensor, v_new: torch.Tensor, *, capacity: int, fp8_dtype=torch.float8_e4m3fn,
+                        new_lens: Optional[torch.Tensor] = None, advance: bool = True) -> None:
+    """qattn_kv_cache_append_fp8 (include/qattn_kvcache.h): quantise k_new / v_new [B, Hkv, T, D] (bf16 / fp16; dense or a view
+    `kv_append_addressable` accepts, read in place) with the cache's scales fp32 [B, Hkv] and write them into the KFRAG / VFRAG images
+    (flat uint8) of [B, Hkv, capacity, D] from key seqlens[b] on; seqlens int32 [B] and new_lens (int32 [B] or None) are read on the
+    device, seqlens is advanced unless advance is False.  Mutates k_frag, v_frag and seqlens."""
+    _require(k_new.is_cuda and k_new.dim() == 4 and k_new.dtype in (torch.bfloat16, torch.float16), "k_new must be a 4-D bf16 / fp16 device tensor")
+    _require(v_new.shape == k_new.shape and v_new.dtype == k_new.dtype and v_new.device == k_new.device, "k_new and v_new must agree in shape, dtype and device")
+    _require(kv_append_addressable(k_new) and kv_append_addressable(v_new), "k_new / v_new need head_dim innermost and 16-byte-aligned rows")
+    B, Hkv, T, D = k_new.shape
+    L = lib()
+    dev = k_new.device
+    for name, img, layout in (("k", k_frag, LAYOUT_KFRAG), ("v", v_frag, LAYOUT_VFRAG)):
+        _require(img.device == dev and img.dtype == torch.uint8 and img.is_contiguous()
+                 and img.numel() == L.qattn_fp8_tensor_bytes(layout, B, Hkv, capacity, D), f"the cache's {name} image does not fit [B={B}, Hkv={Hkv}, capacity={capacity}, D={D}]")
+    for name, sc in (("scale_k", scale_k), ("scale_v", scale_v)):
+        _require(sc.dtype == torch.float32 and sc.device == dev and sc.is_contiguous() and tuple(sc.shape) == (B, Hkv), f"{name} must be a dense float32 [B, Hkv] tensor on {dev}")
+    for name, t in (("seqlens", seqlens), ("new_lens", new_lens)):
+        _require(t is None and name == "new_lens" or (t is not None and t.dtype == torch.int32 and t.device == dev and tuple(t.shape) == (B,) and t.is_contiguous()),
+                 f"{name} must be a dense int32 [B] tensor on {dev}")
+    dense = (Hkv * T * D, T * D, D)     # (a dimension of size 1 has no stride of its own)
+    s3 = lambda t: (ctypes.c_longlong * 3)(*[t.stride(i) if t.shape[i] > 1 else dense[i] for i in (0, 1, 2)])
+    with torch.cuda.device(dev):
+        rc = L.qattn_kv_cache_append_fp8(k_new.data_ptr(), v_new.data_ptr(), fmt_of(k_new.dtype), s3(k_new), s3(v_new), k_frag.data_ptr(),
+                                         v_frag.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(), seqlens.data_ptr(), _ptr(new_lens),
+                                         int(bool(advance)), B, Hkv, T, capacity, D, fmt_of(fp8_dtype), _stream(k_new))
+    _check(rc, "qattn_kv_cache_append_fp8")

@@ -41,6 +41,40 @@ __host__ __device__ inline int vfrag_offset(int key, int d) {
     return ((d >> 5) << 11) + (hh << 10) + (half << 9) + ((d & 31) << 4) + (w << 2) + i;
 }
 
+// Transposing copy-out of one staged fp8 tile (64 keys, row-major with VSTRIDE-byte rows in LDS) into its VFRAG chunk.
+// A thread owns 8 keys (the two 4-key groups w = 2wh, 2wh+1 of one (half, hh)) x 4 consecutive d: 8 conflict-free
+// ds_read_b32, two 4x4 byte transposes (8 v_perm_b32 each) and four 8-byte stores -- instead of 32 ds_read_u8 and
+// 24 shift/or per 8 output dwords.
+template <int D, int VSTRIDE>
+__device__ __forceinline__ void vfrag_copy_out(const unsigned char* img, unsigned char* og_chunk, int tid) {
+#pragma unroll
+    for (int k = 0; k < (2 * D + 255) / 256; k++) {
+        const int blk = k * 256 + tid;
+        if (2 * D < 256 && blk >= 2 * D) break;
+        // lane bits chosen so that the 32 lanes of a ds_read_b32 group hit 32 different banks of the 33-dword-stride image:
+        // bank = (33*row + 8m + dq) mod 32 = dq + 4hh + 16wh + 8(m&1) + const over (dq&3, hh, wh, m&1)
+        const int wh = blk & 1, hh = (blk >> 3) & 1, half = (blk >> 6) & 1;
+        const int dq = ((blk >> 1) & 3) + 4 * ((blk >> 5) & 1), m = ((blk >> 4) & 1) + 2 * (blk >> 7);
+        const int d0 = 32 * m + 4 * dq;
+        unsigned o[2][4];
+#pragma unroll
+        for (int wi = 0; wi < 2; wi++) {
+            const unsigned char* src = img + (32 * half + 8 * (2 * wh + wi) + 4 * hh) * VSTRIDE + d0;
+            const unsigned r0 = *reinterpret_cast<const unsigned*>(src), r1 = *reinterpret_cast<const unsigned*>(src + VSTRIDE);
+            const unsigned r2 = *reinterpret_cast<const unsigned*>(src + 2 * VSTRIDE), r3 = *reinterpret_cast<const unsigned*>(src + 3 * VSTRIDE);
+            const unsigned t0 = __builtin_amdgcn_perm(r1, r0, 0x05010400u), t1 = __builtin_amdgcn_perm(r1, r0, 0x07030602u);
+            const unsigned t2 = __builtin_amdgcn_perm(r3, r2, 0x05010400u), t3 = __builtin_amdgcn_perm(r3, r2, 0x07030602u);
+            o[wi][0] = __builtin_amdgcn_perm(t2, t0, 0x05040100u);
+            o[wi][1] = __builtin_amdgcn_perm(t2, t0, 0x07060302u);
+            o[wi][2] = __builtin_amdgcn_perm(t3, t1, 0x05040100u);
+            o[wi][3] = __builtin_amdgcn_perm(t3, t1, 0x07060302u);
+        }
+        unsigned char* dst = og_chunk + ((((m * 2 + hh) * 2 + half) * 32 + 4 * dq) << 4) + 8 * wh;
+#pragma unroll
+        for (int j = 0; j < 4; j++) *reinterpret_cast<uint2*>(dst + 16 * j) = make_uint2(o[0][j], o[1][j]);
+    }
+}
+
 __device__ inline float bf16_bits_to_f32(unsigned short b) { return __uint_as_float(((unsigned)b) << 16); }
 __device__ inline float fp16_bits_to_f32(unsigned short b) {
     _Float16 h;

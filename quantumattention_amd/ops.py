@@ -522,3 +522,31 @@ def _(query, k_frag, v_frag, scale_k, scale_v, seqused_k, seqlen_k, num_splits, 
                 query.new_empty((n, B, Hq, Sq), dtype=torch.uint8))
     return (out, lse, query.new_empty((0,), dtype=torch.float32), query.new_empty((0,), dtype=torch.float32),
             query.new_empty((0,), dtype=torch.uint8))
+
+
+@_custom_op("quantumattention_amd::fp8_kv_cache_append_", mutates_args=("k_frag", "v_frag", "seqlens"), device_types=("cuda",))
+def fp8_kv_cache_append_(
+    k_frag: torch.Tensor,
+    v_frag: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    seqlens: torch.Tensor,
+    k_new: torch.Tensor,
+    v_new: torch.Tensor,
+    new_lens: Optional[torch.Tensor],
+    capacity: int,
+    fp8_format: str = "e4m3",
+    advance: bool = True,
+) -> None:
+    """Append to an FP8 K/V cache with fixed scales IN PLACE (include/qattn_kvcache.h): k_new / v_new [B, Hkv, T, D] bf16 / fp16 are
+    quantised with scale_k / scale_v fp32 [B, Hkv] and written into the KFRAG / VFRAG images k_frag / v_frag (flat uint8) of
+    [B, Hkv, capacity, D] from key seqlens[b] on; seqlens int32 [B] and new_lens (int32 [B] or None) are read on the device, seqlens is
+    advanced unless advance is False.  Reference implementation: kvcache._append_eager.  Arguments are validated by
+    kvcache.kv_cache_append_fp8."""
+    _native.kv_cache_append_fp8(k_frag, v_frag, scale_k, scale_v, seqlens, k_new, v_new, capacity=capacity,
+                                fp8_dtype=_native.fp8_dtype_of(fp8_format), new_lens=new_lens, advance=advance)
+
+
+@_register_fake("quantumattention_amd::fp8_kv_cache_append_")
+def _(k_frag, v_frag, scale_k, scale_v, seqlens, k_new, v_new, new_lens, capacity, fp8_format="e4m3", advance=True):
+    return None

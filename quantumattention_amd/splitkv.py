@@ -12,8 +12,9 @@ Numerics (include/qattn_splitkv.h): q is quantised head-wise by the quant pre-pa
 `_native.quant_fp8(..., scaling="head-wise", layout=KFRAG / VFRAG)` -- bit for bit what `fp8_block_sparse_attn_pv_func(pv_precision="fp8")`
 attends; both products run on the FP8 matrix pipe.  Package attributes, not names of `__all__` (that list mirrors the reference).
 
-Not offered: an appendable or paged cache (head-wise scales over the whole tensor cannot grow), key smoothing on
-prepared keys, precision="auto", the 16-bit-P.V numerics, sliding windows, strided views."""
+An appendable cache with FIXED scales is kvcache.KVCacheFP8 (kv_cache_append_fp8): a PreparedKV this entry attends
+unchanged.  Not offered: a paged cache, scales that grow with the tensor, key smoothing on prepared keys,
+precision="auto", the 16-bit-P.V numerics, sliding windows, strided views."""
 import math
 from typing import Optional, Tuple
 
@@ -41,7 +42,9 @@ class PreparedKV:
       scale_k, scale_v fp32 [B, Hkv], head-wise over the WHOLE tensors
       shape            (B, Hkv, Skv, D);   fp8_format "e4m3" / "e5m2";   dtype: the 16-bit source dtype (the output dtype of a call);
       numerics         the quantiser's numerics ("compiled" / "eager");   layout "frag" / "rowmajor"
-    Treat it as immutable: the scales cover exactly these keys (nothing can be appended)."""
+    Treat what `prepare_kv_fp8` returns as immutable: its scales cover exactly these keys, so nothing can be appended to it.  The appendable
+    kind is the subclass kvcache.KVCacheFP8 -- fixed scales, a capacity and device-side lengths (alloc_kv_cache_fp8,
+    kv_cache_from_prefill_fp8, kv_cache_append_fp8); a paged cache is not offered."""
 
     __slots__ = ("k", "v", "scale_k", "scale_v", "shape", "fp8_format", "dtype", "numerics", "layout")
 
