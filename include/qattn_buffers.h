@@ -1,8 +1,9 @@
 /*
  * qattn_buffers.h -- the BUFFER CONTRACT of every entry of qattn.h, qattn_strided.h, qattn_smooth.h, qattn_varlen.h, qattn_window.h and
- * qattn_block_sparse.h, and of qattn_rope.h, qattn_splitkv.h and qattn_kvcache.h (documentation only: no declaration).  Held by
+ * qattn_block_sparse.h, and of qattn_rope.h, qattn_splitkv.h, qattn_kvcache.h and qattn_paged.h (documentation only: no declaration).  Held by
  * tests/test_gpu_buffer_contract.py (qattn_rope.h: tests/test_gpu_rope_buffer_contract.py; qattn_splitkv.h:
- * tests/test_gpu_splitkv_buffer_contract.py; qattn_kvcache.h: tests/test_gpu_kvcache_buffer_contract.py) on guarded buffers of exactly these sizes at exactly these alignments.
+ * tests/test_gpu_splitkv_buffer_contract.py; qattn_kvcache.h: tests/test_gpu_kvcache_buffer_contract.py; qattn_paged.h:
+ * tests/test_gpu_paged_buffer_contract.py) on guarded buffers of exactly these sizes at exactly these alignments.
  *
  *   sizes      a buffer of qattn_*_tensor_bytes / qattn_lse_row_stride / *_workspace_bytes bytes (or of the stated shape) suffices; no entry
  *              reads or writes a byte before a buffer's start or past its end, ragged last tiles included, and no result depends on bytes
@@ -86,6 +87,19 @@
  *   seqlens    int32 [B], 4-byte aligned; read, and with advance != 0 every element rewritten (min(p_b + n_b, capacity): a value outside
  *              [0, capacity] comes back clamped); advance = 0: not written.   new_lens: NULL or int32 [B], 4-byte aligned; read.
  *   No workspace.
+ *
+ * qattn_paged_kv_cache_append_fp8 and qattn_fp8_attention_paged_splitkv_forward (qattn_paged.h; held by tests/test_gpu_paged_buffer_contract.py):
+ * every line of qattn_kv_cache_append_fp8 / qattn_fp8_attention_splitkv_forward above with capacity = max_pages page_size, except
+ *   k_pool, v_pool  qattn_fp8_tensor_bytes(QATTN_LAYOUT_KFRAG / _VFRAG, num_pages, Hkv, page_size, D) bytes each, 16-byte aligned, in place of
+ *              k8_kfrag / v8_vfrag.  Append: written are the D bytes of each appended key, at key j % page_size of page
+ *              clamp(block_table[b][j / page_size], 0, num_pages - 1); every other byte of the pool keeps what it held; never read.
+ *              Attention: read are the chunks of the pages the table names for the chunks 0 .. ceil(L_b / 64) - 1 of sequence b
+ *              (causal: up to the last chunk a row attends), no other byte; bytes behind L_b in the chunk that holds key L_b influence
+ *              no result, as in the contiguous entry.
+ *   block_table  int32 [B, max_pages] with a row stride of table_stride >= max_pages elements, 4-byte aligned; read: the entries of the
+ *              pages that hold the appended keys / the chunks named above, no other entry; each clamped before it forms an address.
+ *   seqused_k  int32 [B], 4-byte aligned, REQUIRED by the attention entry.
+ *   workspace  qattn_fp8_attention_paged_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, num_splits) bytes, 16-byte aligned (the append: none).
  */
 #ifndef QATTN_BUFFERS_H_
 #define QATTN_BUFFERS_H_

@@ -37,6 +37,9 @@
  * that is not 16-byte aligned, a misaligned row (k16 / v16 not 16-byte aligned, a stride that is no multiple of 8), a negative stride,
  * a non-positive dimension, a capacity above 2^31 - 64, a grid beyond 2^31 - 1 workgroups; QATTN_ERR_UNSUPPORTED_DIM for D outside {64, 128, 256};
  * QATTN_ERR_UNSUPPORTED_FMT.  Buffers: include/qattn_buffers.h.
+ *
+ * A PAGED cache (a pool of fixed-size pages behind a block table) is include/qattn_paged.h: qattn_paged_kv_cache_append_fp8 is this entry
+ * with another store address per chunk, and an image of shape (num_pages, Hkv, page_size, D) made here is a pool there, byte for byte.
  */
 #ifndef QATTN_KVCACHE_H_
 #define QATTN_KVCACHE_H_

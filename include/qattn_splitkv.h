@@ -63,6 +63,9 @@
  * misaligned (16 bytes: q16, k8_kfrag, v8_vfrag, out, q8, partial_o, workspace) pointer, a non-positive dimension, B or Hq above 65535, an
  * unknown numerics / precision, num_splits outside 0 .. 64, a partial_* pointer with num_splits = 0, a grid beyond 2^31 - 1 workgroups; QATTN_ERR_UNSUPPORTED_DIM for D outside
  * {64, 128, 256} or Hq % Hkv != 0; QATTN_ERR_UNSUPPORTED_FMT; QATTN_ERR_WORKSPACE.  No host synchronisation, no allocation, graph-capture safe.
+ *
+ * The same entry over a PAGED cache (a pool of fixed-size pages behind a block table): qattn_fp8_attention_paged_splitkv_forward,
+ * include/qattn_paged.h -- the bits of this entry on the images gathered through the table.
  */
 #ifndef QATTN_SPLITKV_H_
 #define QATTN_SPLITKV_H_

@@ -45,6 +45,9 @@ from .splitkv import PreparedKV, fp8_attn_splitkv_func, prepare_kv_fp8  # noqa: 
 # an appendable FP8 K/V cache with fixed scales for the split-KV entry (include/qattn_kvcache.h): package attributes too, not in __all__
 from .kvcache import KVCacheFP8, alloc_kv_cache_fp8, kv_cache_append_fp8, kv_cache_from_prefill_fp8  # noqa: E402
 
+# a paged FP8 K/V cache (a pool of pages behind a block table) for split-KV decode (include/qattn_paged.h): package attributes too, not in __all__
+from .paged import PagedKVCacheFP8, alloc_paged_kv_cache_fp8, fp8_attn_paged_func, paged_kv_cache_append_fp8  # noqa: E402
+
 __version__ = "0.1.0"
 
 __all__ = [

@@ -53,6 +53,7 @@ EXPORTS = (
     "qattn_fp8_rope_quant_attention_workspace_bytes", "qattn_fp8_rope_quant_attention_forward",
     "qattn_fp8_attention_splitkv_workspace_bytes", "qattn_splitkv_auto_splits", "qattn_fp8_attention_splitkv_forward",
     "qattn_kv_cache_append_fp8",
+    "qattn_paged_kv_cache_append_fp8", "qattn_fp8_attention_paged_splitkv_workspace_bytes", "qattn_fp8_attention_paged_splitkv_forward",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -239,6 +240,16 @@ def lib() -> ctypes.CDLL:
     # scale_k, scale_v, seqlens, new_lens, advance, B, Hkv, T, capacity, D, fp8_fmt, stream
     L.qattn_kv_cache_append_fp8.restype = i
     L.qattn_kv_cache_append_fp8.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
+    # the paged cache (include/qattn_paged.h).  Append: k16, v16, in_fmt, k_strides3, v_strides3, k_pool, v_pool, scale_k, scale_v, block_table,
+    # table_stride, seqlens, new_lens, advance, B, Hkv, T, num_pages, page_size, max_pages, D, fp8_fmt, stream.  Attention: q16, in_fmt, k_pool,
+    # v_pool, block_table, table_stride, num_pages, page_size, max_pages, then the split-KV entry's arguments from scale_k on
+    L.qattn_paged_kv_cache_append_fp8.restype = i
+    L.qattn_paged_kv_cache_append_fp8.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, ll, vp, vp, i, i, i, i, i, i, i, i, i, vp]
+    L.qattn_fp8_attention_paged_splitkv_workspace_bytes.restype = sz
+    L.qattn_fp8_attention_paged_splitkv_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
+    L.qattn_fp8_attention_paged_splitkv_forward.restype = i
+    L.qattn_fp8_attention_paged_splitkv_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f, i, i,
+                                                            vp, vp, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1216,3 +1227,101 @@ def kv_cache_append_fp8(k_frag: torch.Tensor, v_frag: torch.Tensor, scale_k: tor
                                          v_frag.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(), seqlens.data_ptr(), _ptr(new_lens),
                                          int(bool(advance)), B, Hkv, T, capacity, D, fmt_of(fp8_dtype), _stream(k_new))
     _check(rc, "qattn_kv_cache_append_fp8")
+
+
+def _paged_pool_checks(L, k_pool, v_pool, block_table, scale_k, scale_v, dev, B, Hkv, num_pages, page_size, D):
+    """the pools, the table and the scales of a paged cache (include/qattn_paged.h); returns (max_pages, table_stride)"""
+    _require(isinstance(page_size, int) and page_size >= 64 and page_size % 64 == 0, f"page_size must be a positive multiple of 64, got {page_size}")
+    _require(isinstance(num_pages, int) and num_pages > 0, f"num_pages must be positive, got {num_pages}")
+    for name, img, layout in (("k", k_pool, LAYOUT_KFRAG), ("v", v_pool, LAYOUT_VFRAG)):
+        _require(img.device == dev and img.dtype == torch.uint8 and img.is_contiguous()
+                 and img.numel() == L.qattn_fp8_tensor_bytes(layout, num_pages, Hkv, page_size, D),
+                 f"the {name} pool does not fit [num_pages={num_pages}, Hkv={Hkv}, page_size={page_size}, D={D}]")
+    _require(block_table.dtype == torch.int32 and block_table.device == dev and block_table.dim() == 2 and block_table.shape[0] == B
+             and block_table.shape[1] > 0 and block_table.stride(1) == 1 and (B == 1 or block_table.stride(0) >= block_table.shape[1]),
+             f"block_table must be an int32 [B={B}, max_pages] tensor on {dev} with dense rows")
+    for name, sc in (("scale_k", scale_k), ("scale_v", scale_v)):
+        _require(sc.dtype == torch.float32 and sc.device == dev and sc.is_contiguous() and tuple(sc.shape) == (B, Hkv), f"{name} must be a dense float32 [B, Hkv] tensor on {dev}")
+    max_pages = block_table.shape[1]
+    return max_pages, (block_table.stride(0) if B > 1 else max_pages)
+
+
+def paged_kv_cache_append_fp8(k_pool: torch.Tensor, v_pool: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor, block_table: torch.Tensor,
+                              seqlens: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, *, num_pages: int, page_size: int,
+                              fp8_dtype=torch.float8_e4m3fn, new_lens: Optional[torch.Tensor] = None, advance: bool = True) -> None:
+    """qattn_paged_kv_cache_append_fp8 (include/qattn_paged.h): kv_cache_append_fp8 into the pools k_pool / v_pool (flat uint8: the KFRAG /
+    VFRAG images of [num_pages, Hkv, page_size, D]) through block_table int32 [B, max_pages]; capacity = max_pages page_size.  The table,
+    seqlens and new_lens are read on the device.  Mutates k_pool, v_pool and seqlens."""
+    _require(k_new.is_cuda and k_new.dim() == 4 and k_new.dtype in (torch.bfloat16, torch.float16), "k_new must be a 4-D bf16 / fp16 device tensor")
+    _require(v_new.shape == k_new.shape and v_new.dtype == k_new.dtype and v_new.device == k_new.device, "k_new and v_new must agree in shape, dtype and device")
+    _require(kv_append_addressable(k_new) and kv_append_addressable(v_new), "k_new / v_new need head_dim innermost and 16-byte-aligned rows")
+    B, Hkv, T, D = k_new.shape
+    L = lib()
+    dev = k_new.device
+    max_pages, tstride = _paged_pool_checks(L, k_pool, v_pool, block_table, scale_k, scale_v, dev, B, Hkv, num_pages, page_size, D)
+    for name, t in (("seqlens", seqlens), ("new_lens", new_lens)):
+        _require(t is None and name == "new_lens" or (t is not None and t.dtype == torch.int32 and t.device == dev and tuple(t.shape) == (B,) and t.is_contiguous()),
+                 f"{name} must be a dense int32 [B] tensor on {dev}")
+    dense = (Hkv * T * D, T * D, D)     # (a dimension of size 1 has no stride of its own)
+    s3 = lambda t: (ctypes.c_longlong * 3)(*[t.stride(i) if t.shape[i] > 1 else dense[i] for i in (0, 1, 2)])
+    with torch.cuda.device(dev):
+        rc = L.qattn_paged_kv_cache_append_fp8(k_new.data_ptr(), v_new.data_ptr(), fmt_of(k_new.dtype), s3(k_new), s3(v_new), k_pool.data_ptr(),
+                                               v_pool.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(), block_table.data_ptr(), tstride,
+                                               seqlens.data_ptr(), _ptr(new_lens), int(bool(advance)), B, Hkv, T, num_pages, page_size, max_pages,
+                                               D, fmt_of(fp8_dtype), _stream(k_new))
+    _check(rc, "qattn_paged_kv_cache_append_fp8")
+
+
+def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor,
+                                block_table: torch.Tensor, seqused_k: torch.Tensor, *, Skv: int, num_pages: int, page_size: int,
+                                fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled", is_causal: bool = False, sm_scale: float = 0.0,
+                                precision: str = "accurate", num_splits: int = 0, return_lse: bool = False, return_partials: bool = False,
+                                return_quant: bool = False, return_path: bool = False):
+    """Split-KV attention over a paged cache (qattn_fp8_attention_paged_splitkv_forward, include/qattn_paged.h): fp8_attention_splitkv with
+    the pools (flat uint8: the KFRAG / VFRAG images of [num_pages, Hkv, page_size, D]) and block_table int32 [B, max_pages] in place of the
+    contiguous images; Skv <= max_pages page_size is the logical bound, seqused_k int32 [B] is required.  Returns what
+    fp8_attention_splitkv returns."""
+    _require(precision in ("fast", "accurate"), f"Unsupported precision for the split-KV entry: {precision!r} (expected 'fast' or 'accurate')")
+    _require(q.is_cuda and q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16), "query must be a 4-D bf16 / fp16 device tensor")
+    _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
+    q = q.contiguous()
+    B, Hq, Sq, D = q.shape
+    _require(scale_k.dim() == 2 and scale_k.shape[0] == B, "scale_k / scale_v must be fp32 [B, Hkv]")
+    Hkv = scale_k.shape[1]
+    _require(Hkv > 0 and Hq % Hkv == 0, f"Hq={Hq} is not a multiple of Hkv={Hkv}")
+    L = lib()
+    dev = q.device
+    max_pages, tstride = _paged_pool_checks(L, k_pool, v_pool, block_table, scale_k, scale_v, dev, B, Hkv, num_pages, page_size, D)
+    _require(isinstance(Skv, int) and 0 < Skv <= max_pages * page_size, f"Skv must be in 1 .. max_pages * page_size = {max_pages * page_size}, got {Skv}")
+    _require(seqused_k is not None and seqused_k.dtype == torch.int32 and seqused_k.device == dev and tuple(seqused_k.shape) == (B,)
+             and seqused_k.is_contiguous(), f"seqused_k must be a dense int32 [B] tensor on {dev}")
+    ns = int(num_splits)
+    if ns == 0:
+        ns = splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, torch.cuda.get_device_properties(dev).multi_processor_count)
+    with torch.cuda.device(dev):
+        out = torch.empty((B, Hq, Sq, D), dtype=q.dtype, device=dev)
+        lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev) if return_lse else None
+        po = plse = ppath = q8 = sq = path = None
+        if return_partials:
+            n = ns if ns > 1 else 0
+            po = torch.empty((n, B, Hq, Sq, D), dtype=torch.float32, device=dev)
+            plse = torch.empty((n, B, Hq, Sq), dtype=torch.float32, device=dev)
+            ppath = torch.empty((n, B, Hq, Sq), dtype=torch.uint8, device=dev)
+        if return_quant:
+            q8 = torch.empty((B, Hq, Sq, D), dtype=fp8_dtype, device=dev)
+            sq = torch.empty((B, Hq), dtype=torch.float32, device=dev)
+        if return_path:
+            path = torch.empty((B, Hq, Sq), dtype=torch.uint8, device=dev)
+        ws_bytes = L.qattn_fp8_attention_paged_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, ns)
+        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+        live = lambda t: _ptr(t) if t is not None and t.numel() else None
+        rc = L.qattn_fp8_attention_paged_splitkv_forward(
+            q.data_ptr(), fmt_of(q.dtype), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), tstride, num_pages, page_size, max_pages,
+            scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(), _ptr(lse), seqused_k.data_ptr(), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype),
+            _numerics(numerics), int(bool(is_causal)), float(sm_scale), _precision(precision), ns, _ptr(q8), _ptr(sq), _ptr(path), live(po),
+            live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
+    _check(rc, "qattn_fp8_attention_paged_splitkv_forward")
+    if not (return_lse or return_partials or return_quant or return_path):
+        return out
+    return ((out,) + ((lse,) if return_lse else ()) + ((po, plse, ppath) if return_partials else ()) + ((q8, sq) if return_quant else ())
+            + ((path,) if return_path else ()))

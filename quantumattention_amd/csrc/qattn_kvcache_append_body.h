@@ -1,0 +1,86 @@
+// qattn_kvcache_append_body.h -- the BODY of the append kernel, included inside the two kernel definitions of qattn_kvcache_append.h (no
+// include guard: it is text, not declarations).  QATTN_KVA_PAGED selects where the workgroup's chunk is stored: 0, the contiguous image --
+// statement for statement the kernel qattn_kvcache_append.hip held before the paged entry existed, so that its device code stays what it
+// was; 1, the pool through the block table `pg` (include/qattn_paged.h).  Shared as text, not as an inlined function, for the reason
+// qattn_splitkv_body.h gives.
+// In scope: template parameters D, IN_FMT, OUT_FMT; arguments a (KvAppendArgs) and -- paged -- pg (KvPages).
+    constexpr int VPR = D / 8;             // 16-byte input vectors per row
+    constexpr int ITERS = 64 * VPR / 256;  // vectors per thread
+    constexpr int KPAD = 64 * D + (64 * D / 512) * 16;  // KFRAG image + 16 B per 512 B     (the staging images of quant_multi_kernel)
+    constexpr int VSTRIDE = D + 4;                      // VFRAG staging: fp8 row-major
+    constexpr int LDS_BYTES = KPAD > 64 * VSTRIDE ? KPAD : 64 * VSTRIDE;
+    __shared__ __attribute__((aligned(16))) unsigned char img[LDS_BYTES];
+    const int tid = threadIdx.x, z = blockIdx.y;
+    const int g = (int)(blockIdx.x / (unsigned)a.nchunk), ci = (int)(blockIdx.x % (unsigned)a.nchunk);
+    const int b = g / a.Hkv, h = g % a.Hkv;
+    int p, end;
+    kv_append_range(a.seqlens, a.new_lens, b, a.T, a.capacity, p, end);
+    const long key0 = 64L * (p / 64 + ci);   // first key of this workgroup's chunk
+    if (p >= end || key0 >= end) return;     // (workgroup-uniform: nothing is appended -- new_lens 0, a full cache -- or nothing of this chunk)
+    // the chunk's keys [lo, hi) are the tokens [key0 + lo - p, key0 + hi - p) of the call
+    const int lo = p > key0 ? (int)(p - key0) : 0, hi = end - key0 < 64 ? (int)(end - key0) : 64;
+    const float scale = a.scale[z][g];
+    const float rinv = 1.0f / scale;
+    const uint4* xg = a.x[z] + (long)b * a.sb[z] + (long)h * a.sh[z] + (key0 - p) * a.st[z];   // row of chunk key 0 (not touched below lo)
+    const long st = a.st[z];
+    uint4 held[ITERS];
+#pragma unroll
+    for (int it = 0; it < ITERS; it++) {
+        const int vec = it * 256 + tid;
+        const int r = vec / VPR;
+        held[it] = make_uint4(0, 0, 0, 0);
+        if (r >= lo && r < hi) held[it] = load_nt(xg + (long)r * st + vec % VPR);
+    }
+#pragma unroll
+    for (int it = 0; it < ITERS; it++) {
+        const int vec = it * 256 + tid;
+        const int r = vec / VPR, d0 = (vec % VPR) * 8;
+        const int2 lohi = quant8<IN_FMT, OUT_FMT>(held[it], scale, rinv, has_nonfinite16<IN_FMT>(held[it]));   // NaN stays NaN, +-inf clamps to +-qmax
+        if (z == 0) {
+            const int o = kfrag_offset<D>(r, d0);
+            *reinterpret_cast<int2*>(img + o + ((o >> 9) << 4)) = lohi;
+        } else {
+            *reinterpret_cast<int*>(img + r * VSTRIDE + d0) = lohi.x;
+            *reinterpret_cast<int*>(img + r * VSTRIDE + d0 + 4) = lohi.y;
+        }
+    }
+    __syncthreads();
+#if QATTN_KVA_PAGED
+    // key0 < end <= capacity = max_pages page_size: the entry read is one of the pages that cover [p, end); its clamp keeps the chunk inside
+    // the pool whatever the table holds
+    const int cs = (int)(key0 >> 6);
+    int page = pg.table[(long)b * pg.stride + cs / pg.pc];
+    page = page < 0 ? 0 : page > pg.num_pages - 1 ? pg.num_pages - 1 : page;
+    unsigned char* og = a.img[z] + (((long)page * a.Hkv + h) * pg.pc + cs % pg.pc) * (64L * D);   // the chunk in the pool
+#else
+    const long Sp = ((long)a.capacity + 63) / 64 * 64;
+    unsigned char* og = a.img[z] + ((long)g * Sp + key0) * D;   // the chunk in the image
+#endif
+    const bool whole = lo == 0 && hi == 64;
+    if (z == 0) {
+        // piece i of a KFRAG chunk = [t:2][s:D/64][hh:2][half:2][key:32] holds 16 channels of ONE key, 32 t + key
+        for (int i = tid; i < 64 * D / 16; i += 256) {
+            const int r = 32 * (i / (2 * D)) + (i & 31);
+            if (whole || (r >= lo && r < hi)) reinterpret_cast<uint4*>(og)[i] = *reinterpret_cast<const uint4*>(img + i * 16 + ((i >> 5) << 4));
+        }
+    } else if (whole) {
+        vfrag_copy_out<D, VSTRIDE>(img, og, tid);
+    } else {
+        // word wd of a VFRAG chunk = [m:D/32][hh:2][half:2][d:32][w:4] holds channel 32 m + d of the 4 keys 32 half + 8 w + 4 hh + (0..3):
+        // a word store where all four are appended, byte stores of the appended ones otherwise -- the others' bytes are neither read nor written
+        for (int wd = tid; wd < 64 * D / 4; wd += 256) {
+            const int w = wd & 3, dl = (wd >> 2) & 31, half = (wd >> 7) & 1, hh = (wd >> 8) & 1, m = wd >> 9;
+            const int kb = 32 * half + 8 * w + 4 * hh;
+            if (kb + 4 <= lo || kb >= hi) continue;
+            const unsigned char* src = img + kb * VSTRIDE + 32 * m + dl;
+            const unsigned b0 = src[0], b1 = src[VSTRIDE], b2 = src[2 * VSTRIDE], b3 = src[3 * VSTRIDE];
+            if (kb >= lo && kb + 4 <= hi) {
+                *reinterpret_cast<unsigned*>(og + 4 * wd) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+            } else {
+                const unsigned bytes[4] = {b0, b1, b2, b3};
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (kb + i >= lo && kb + i < hi) og[4 * wd + i] = (unsigned char)bytes[i];
+            }
+        }
+    }

@@ -1,0 +1,257 @@
+// qattn_splitkv_attn.h -- the split-KV sweep kernel and its host driver, shared by the two entries that differ only in WHERE a head's 64-key
+// chunks live: qattn_fp8_attention_splitkv_forward (qattn_splitkv_fp8.hip: contiguous KFRAG / VFRAG images, include/qattn_splitkv.h) and
+// qattn_fp8_attention_paged_splitkv_forward (qattn_paged_splitkv_fp8.hip: a pool of pages behind a block table, include/qattn_paged.h).
+// The kernel body is qattn_splitkv_body.h, compiled once per chunk addressing; each unit instantiates its own kernels only, and the
+// contiguous kernel is, statement for statement, the kernel qattn_splitkv_fp8.hip held before the paged entry existed.
+#pragma once
+#include <limits.h>
+
+#include "qattn_fp8pv_sweep.h"
+#include "qattn_varlen_tile.h"
+#include "../../include/qattn_merge.h"
+#include "../../include/qattn_splitkv.h"
+
+namespace qattn {
+
+struct SkvAttn {
+    const unsigned char *q8, *k8, *v8;   // q8 row-major [B, Hq, Sq, D]; the KFRAG / VFRAG images of [B, Hkv, Skv, D] (PAGED: the pools)
+    const float *sq, *sk, *sv;           // [B, Hq], [B, Hkv], [B, Hkv]
+    const int* used;                     // seqused_k [B] or nullptr
+    void* out;                           // ns = 1: the call's outputs
+    float* lse;
+    unsigned char* path;
+    float* po;                           // ns > 1: [ns][B Hq Sq][D], [ns][B Hq Sq], [ns][B Hq Sq] (ppath may be nullptr)
+    float* plse;
+    unsigned char* ppath;
+    long part_rows;                      // B Hq Sq
+    int out_fmt, Hkv, G, Sq, Skv;
+    int rows, ntile;                     // packed rows G Sq of a kv head, and their 128-row tiles
+    int ns, nchunks;                     // splits; 64-key chunks of a head's images
+    int causal, two_term_keys;
+    float sm_log2e;
+};
+
+// PAGED: the block table (include/qattn_paged.h).  Logical chunk c of (b, hkv) is chunk c % pc of page clamp(table[b][c / pc]): physical
+// chunk (page Hkv + hkv) pc + c % pc of the pool.
+struct SkvPages {
+    const int* table;   // [B][stride]
+    long stride;
+    int num_pages, pc;  // pages of the pool; 64-key chunks per page
+};
+
+// Physical chunk of chunk `ch` of kv head hkv of the page a RAW table entry names.  The clamp is what keeps every address inside the
+// pool, whatever the table holds; it is applied here, where the entry forms an address, so that the entry's load can be issued a step
+// ahead of its use without its wait following it.  (Everything is workgroup-uniform.)
+__device__ __forceinline__ int skv_phys(const SkvPages& pg, int entry, int Hkv, int hkv, int ch) {
+    const int page = __builtin_amdgcn_readfirstlane(clampi(entry, 0, pg.num_pages - 1));
+    return (page * Hkv + hkv) * pg.pc + ch;
+}
+
+// this lane's piece of an fp32 row: o[m][4 j + i] is column 32 m + 8 j + 4 hh + i (the map of store_o_rows), four floats at a time
+template <int MB>
+__device__ __forceinline__ void store_o_rows_f32(float* row, const v16f (&o)[MB], float inv, int hh, bool valid) {
+    float* op = row + 4 * hh;
+#pragma unroll
+    for (int m = 0; m < MB; m++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const v4f x = {o[m][4 * j] * inv, o[m][4 * j + 1] * inv, o[m][4 * j + 2] * inv, o[m][4 * j + 3] * inv};
+            if (valid) *reinterpret_cast<v4f*>(op + 32 * m + 8 * j) = x;
+        }
+}
+
+// The V chunk of a stage, in LDS, with the bytes of its keys >= nvalid set to zero; all four waves call it (workgroup-uniform), after the
+// stage has landed and before anyone reads it.  Only the chunk that holds key L_b needs it: a prepared image holds ALL Skv keys, so behind
+// the used ones sit bytes the caller does not vouch for (a cache slot not yet filled: NaN patterns included).  Their P is exactly 0 -- the
+// masked scores are -inf -- but 0 x NaN is NaN in the matrix pipe.  (K needs nothing: a NaN score is replaced by -inf, not multiplied.)
+// VFRAG: the 16-byte piece at offset o holds, for one channel, the keys 32 half + 8 w + 4 hh + i at byte 4 w + i, half = bit 9, hh = bit 10.
+template <int D>
+__device__ __forceinline__ void skv_zero_v_tail(unsigned char* vst, int nvalid) {
+    constexpr int CH = 64 * D;
+    for (int o = (int)threadIdx.x * 16; o < CH; o += kFpvWaves * 64 * 16) {
+        v4i x = *reinterpret_cast<v4i*>(vst + o);
+        const int key0 = 32 * ((o >> 9) & 1) + 4 * ((o >> 10) & 1);
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const int left = nvalid - (key0 + 8 * w);   // keys of this word that are valid: bytes 0 .. left - 1
+            const unsigned keep = left >= 4 ? 0xffffffffu : left <= 0 ? 0u : (1u << (8 * left)) - 1u;
+            x[w] = (int)((unsigned)x[w] & keep);
+        }
+        *reinterpret_cast<v4i*>(vst + o) = x;
+    }
+    lds_barrier();
+}
+
+// The two kernels: one body (qattn_splitkv_body.h), compiled once per chunk addressing.  BYTE / two / sel: as attn_vfp8_window_kernel.
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_splitkv_fp8_kernel(const SkvAttn a, const int two, const int sel) {
+#define QATTN_SKV_PAGED 0
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_PAGED
+}
+
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_paged_splitkv_fp8_kernel(const SkvAttn a, const SkvPages pg, const int two, const int sel) {
+#define QATTN_SKV_PAGED 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_PAGED
+}
+
+template <int D, int FMT, bool PAGED>
+static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, unsigned grid, int max_keys, int precision, bool want_lse, hipStream_t st) {
+    return fpv_precision_ladder(precision, max_keys, a.two_term_keys, want_lse, [&](auto byte, int two, int sel) {
+        if constexpr (PAGED) return fpv_launch(attn_paged_splitkv_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg, two, sel);
+        else return fpv_launch(attn_splitkv_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, two, sel);
+    });
+}
+
+template <int D, bool PAGED>
+static int launch_skv_d(const SkvAttn& a, const SkvPages& pg, unsigned grid, int max_keys, int fp8_fmt, int precision, bool want_lse, hipStream_t st) {
+    return fp8_fmt == QATTN_FMT_E4M3 ? launch_skv_fmt<D, QATTN_FMT_E4M3, PAGED>(a, pg, grid, max_keys, precision, want_lse, st)
+                                     : launch_skv_fmt<D, QATTN_FMT_E5M2, PAGED>(a, pg, grid, max_keys, precision, want_lse, st);
+}
+
+inline bool skv_dims_ok(int B, int Hq, int Hkv, int Sq, int Skv) { return B > 0 && Hq > 0 && Hkv > 0 && Sq > 0 && Skv > 0; }
+inline bool skv_d_ok(int D) { return D == 64 || D == 128 || D == 256; }
+
+// the sections of the workspace, in order (each up256)
+struct SkvWs {
+    size_t q8, sq, qws, po, plse, ppath, acc, acc_lse;
+    size_t total() const { return q8 + sq + qws + po + plse + ppath + acc + acc_lse; }
+};
+inline SkvWs skv_ws(int B, int Hq, int Sq, int D, int ns) {
+    const size_t rows = (size_t)B * Hq * Sq;
+    SkvWs w = {};
+    w.q8 = up256(qattn_fp8_tensor_bytes(QATTN_LAYOUT_ROWMAJOR, B, Hq, Sq, D));
+    w.sq = up256(sizeof(float) * (size_t)B * Hq);
+    w.qws = up256(qattn_quant_workspace_bytes(B, Hq, Sq, D, QATTN_SCALE_HEAD));
+    if (ns > 1) {
+        w.po = up256(sizeof(float) * ns * rows * D);
+        w.plse = up256(sizeof(float) * ns * rows);
+        w.ppath = up256((size_t)ns * rows);
+    }
+    if (ns > QATTN_MERGE_MAX_PARTIALS) {
+        w.acc = up256(sizeof(float) * rows * D);
+        w.acc_lse = up256(sizeof(float) * rows);
+    }
+    return w;
+}
+
+// splitkv_path_kernel's launch (qattn_splitkv_fp8.hip): row_path of a merged row from the per-split path bytes
+int skv_launch_path(const float* plse, const unsigned char* ppath, unsigned char* path, long rows, int ns, hipStream_t st);
+
+// Both entries, from their common arguments on: k8 / v8 are the contiguous images of [B, Hkv, Skv, D] or -- PAGED, with pg filled in and
+// checked by the caller -- the pools.
+template <bool PAGED>
+int skv_forward(const void* q16, int in_fmt, const void* k8, const void* v8, const SkvPages& pg, const float* scale_k, const float* scale_v,
+                void* out, float* lse, const int* seqused_k, int B, int Hq, int Hkv, int Sq, int Skv, int D, int fp8_fmt, int numerics,
+                int is_causal, float sm_scale, int precision, int num_splits, void* q8, float* scale_q, unsigned char* row_path,
+                float* partial_o, float* partial_lse, unsigned char* partial_path, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!q16 || !k8 || !v8 || !scale_k || !scale_v || !out) return QATTN_ERR_INVALID_ARG;
+    if (!skv_dims_ok(B, Hq, Hkv, Sq, Skv)) return QATTN_ERR_INVALID_ARG;
+    if (!skv_d_ok(D) || Hq % Hkv != 0) return QATTN_ERR_UNSUPPORTED_DIM;
+    if (in_fmt != QATTN_FMT_BF16 && in_fmt != QATTN_FMT_FP16) return QATTN_ERR_UNSUPPORTED_FMT;
+    if (fp8_fmt != QATTN_FMT_E4M3 && fp8_fmt != QATTN_FMT_E5M2) return QATTN_ERR_UNSUPPORTED_FMT;
+    if (numerics != QATTN_NUMERICS_COMPILED && numerics != QATTN_NUMERICS_EAGER) return QATTN_ERR_INVALID_ARG;
+    if (precision != QATTN_PRECISION_FAST && precision != QATTN_PRECISION_ACCURATE) return QATTN_ERR_INVALID_ARG;
+    if (num_splits < 0 || num_splits > QATTN_SPLITKV_MAX_SPLITS) return QATTN_ERR_INVALID_ARG;
+    if (B > 65535 || Hq > 65535) return QATTN_ERR_INVALID_ARG;   // (the merge's grid)
+    if (Skv > 0x7fffffff - (1 << 15)) return QATTN_ERR_INVALID_ARG;   // (the split plan's key numbers stay in 32 bits)
+    if (((size_t)q16 | (size_t)k8 | (size_t)v8 | (size_t)out | (size_t)q8 | (size_t)partial_o | (size_t)workspace) % 16 != 0)
+        return QATTN_ERR_INVALID_ARG;
+    const int G = Hq / Hkv;
+    if ((long long)G * Sq > 0x7fffffffLL) return QATTN_ERR_INVALID_ARG;
+    const int ntile = ceil_div(G * Sq, kFpvTile);
+    // num_splits = 0: the grid and the workspace are checked for the most splits the rule can pick -- qattn_..._workspace_bytes(..., 0) --
+    // so that every check is done before the device is asked for its CU count; the partial buffers' shape would not be known to the caller
+    if (num_splits == 0 && (partial_o || partial_lse || partial_path)) return QATTN_ERR_INVALID_ARG;
+    const int nkb_all = ceil_div(Skv, 128);
+    const int ns_most = num_splits > 0 ? num_splits : (nkb_all < QATTN_SPLITKV_MAX_SPLITS ? nkb_all : QATTN_SPLITKV_MAX_SPLITS);
+    if ((long long)B * Hkv * ntile * ns_most > 0x7fffffffLL) return QATTN_ERR_INVALID_ARG;   // (one workgroup per work item: a 32-bit grid)
+    if (!workspace || workspace_bytes < skv_ws(B, Hq, Sq, D, ns_most).total()) return QATTN_ERR_WORKSPACE;
+    const int ns = num_splits > 0 ? num_splits : qattn_splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, cu_count());
+    const SkvWs ws = skv_ws(B, Hq, Sq, D, ns);
+    hipStream_t st = (hipStream_t)stream;
+    unsigned char* w = (unsigned char*)workspace;
+    unsigned char* q8w = w;         w += ws.q8;
+    float* sqw = (float*)w;         w += ws.sq;
+    void* qws = w;                  w += ws.qws;
+    float* pow_ = (float*)w;        w += ws.po;
+    float* plsew = (float*)w;       w += ws.plse;
+    unsigned char* ppathw = w;      w += ws.ppath;
+    float* acc = (float*)w;         w += ws.acc;
+    float* acc_lse = (float*)w;
+    unsigned char* q8p = q8 ? (unsigned char*)q8 : q8w;
+    float* sq = scale_q ? scale_q : sqw;
+    float* po = partial_o ? partial_o : pow_;
+    float* plse = partial_lse ? partial_lse : plsew;
+    unsigned char* ppath = partial_path ? partial_path : ((row_path && ns > 1) ? ppathw : nullptr);
+
+    int rc = qattn_quant_fp8(q16, in_fmt, q8p, sq, B, Hq, Sq, D, fp8_fmt, QATTN_SCALE_HEAD, numerics, QATTN_LAYOUT_ROWMAJOR, qws,
+                             qattn_quant_workspace_bytes(B, Hq, Sq, D, QATTN_SCALE_HEAD), stream);
+    if (rc != QATTN_OK) return rc;
+
+    const long rows = (long)B * Hq * Sq;
+    SkvAttn a;
+    __builtin_memset(&a, 0, sizeof(a));
+    a.q8 = q8p; a.k8 = (const unsigned char*)k8; a.v8 = (const unsigned char*)v8;
+    a.sq = sq; a.sk = scale_k; a.sv = scale_v;
+    a.used = seqused_k;
+    a.out = out; a.lse = lse; a.path = row_path;
+    a.po = po; a.plse = plse; a.ppath = ppath;
+    a.part_rows = rows;
+    a.out_fmt = in_fmt; a.Hkv = Hkv; a.G = G; a.Sq = Sq; a.Skv = Skv;
+    a.rows = G * Sq; a.ntile = ntile;
+    a.ns = ns; a.nchunks = ceil_div(Skv, 64);
+    a.causal = is_causal ? 1 : 0;
+    a.two_term_keys = kTwoTermKeys;
+    a.sm_log2e = (sm_scale > 0.0f ? sm_scale : 1.0f / sqrtf((float)D)) * 1.4426950408889634f;
+    // the most keys a split can own; the sweep asks for the LSE whenever it feeds the merge
+    const int nkb = ceil_div(Skv, 128);
+    const long long span = 128LL * ceil_div(nkb, ns);
+    const int max_keys = span < Skv ? (int)span : Skv;
+    const bool want_lse = lse != nullptr || ns > 1;
+    const unsigned grid = (unsigned)((long long)B * Hkv * ntile * ns);
+    if (D == 64) rc = launch_skv_d<64, PAGED>(a, pg, grid, max_keys, fp8_fmt, precision, want_lse, st);
+    else if (D == 128) rc = launch_skv_d<128, PAGED>(a, pg, grid, max_keys, fp8_fmt, precision, want_lse, st);
+    else rc = launch_skv_d<256, PAGED>(a, pg, grid, max_keys, fp8_fmt, precision, want_lse, st);
+    if (rc != QATTN_OK) return rc;
+    if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
+    if (ns == 1) return QATTN_OK;
+
+    // ---- the merge: partials 0 .. 7 (into the accumulator when more follow), then 7 more per launch in place, the last one into out
+    constexpr int top = QATTN_MERGE_MAX_PARTIALS;
+    const long long os3[3] = {(long long)Hq * Sq * D, (long long)Sq * D, D}, ls3[3] = {(long long)Hq * Sq, Sq, 1};
+    auto merge = [&](const float* o0, const float* l0, int first, int n_more, void* dst, int dst_fmt, float* dst_lse) -> int {
+        const void* o[top];
+        const float* l[top];
+        int fmt[top];
+        long long ostr[3 * top], lstr[3 * top];
+        int n = 0;
+        if (o0) { o[n] = o0; l[n] = l0; n++; }
+        for (int i = 0; i < n_more; i++, n++) { o[n] = po + (size_t)(first + i) * rows * D; l[n] = plse + (size_t)(first + i) * rows; }
+        for (int i = 0; i < n; i++) {
+            fmt[i] = QATTN_FMT_FP32;
+            for (int j = 0; j < 3; j++) { ostr[3 * i + j] = os3[j]; lstr[3 * i + j] = ls3[j]; }
+        }
+        return qattn_attention_state_merge(n, o, fmt, ostr, l, lstr, dst, dst_fmt, os3, dst_lse, ls3, B, Hq, Sq, D, stream);
+    };
+    if (ns <= top) {
+        rc = merge(nullptr, nullptr, 0, ns, out, in_fmt, lse);
+    } else {
+        rc = merge(nullptr, nullptr, 0, top, acc, QATTN_FMT_FP32, acc_lse);
+        int done = top;
+        while (rc == QATTN_OK && ns - done > top - 1) {
+            rc = merge(acc, acc_lse, done, top - 1, acc, QATTN_FMT_FP32, acc_lse);
+            done += top - 1;
+        }
+        if (rc == QATTN_OK) rc = merge(acc, acc_lse, done, ns - done, out, in_fmt, lse);
+    }
+    if (rc != QATTN_OK) return rc;
+    if (row_path) return skv_launch_path(plse, ppath, row_path, rows, ns, st);
+    return QATTN_OK;
+}
+
+}  // namespace qattn

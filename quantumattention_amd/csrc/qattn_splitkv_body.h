@@ -1,0 +1,138 @@
+// qattn_splitkv_body.h -- the BODY of the split-KV sweep kernel, included inside the two kernel definitions of qattn_splitkv_attn.h (no include
+// guard: it is text, not declarations).  QATTN_SKV_PAGED selects where a head's 64-key chunks are fetched from: 0, the contiguous images
+// (a.k8 / a.v8 + the head's offset, chunk c is chunk c) -- statement for statement the kernel qattn_splitkv_fp8.hip held before the paged
+// entry existed, so that its device code stays what it was; 1, the pools through the block table `pg` (include/qattn_paged.h).  A body
+// shared as text, not as an inlined function: wrapped in a function the compiler's inlining and register allocation came out differently
+// for the contiguous kernels (profiles/paged/code_objects_vs_parent.log).
+// In scope: template parameters D, FMT, BYTE; arguments a (SkvAttn), two, sel and -- paged -- pg (SkvPages).
+    constexpr int CH = 64 * D, MB = D / 32, KS = D / 64;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    FpvSweep<D, FMT, BYTE> sw(smem);
+    const int lane = sw.lane, wave = sw.wave, ql = sw.ql, hh = sw.hh;
+
+    // block -> (kv head b Hkv + hkv, tile, split): the splits of a tile are neighbours, the tiles of a kv head follow each other.
+    // (Handing each XCD a contiguous range of kv heads, as the other launchers do, was measured and moved no time: not kept.)
+    const int bid = blockIdx.x, per_head = a.ntile * a.ns;
+    const int kvh = bid / per_head, rest = bid % per_head;
+    const int s = rest % a.ns, tile = rest / a.ns;
+    int L = a.Skv;
+    if (a.used) L = clampi(__builtin_amdgcn_readfirstlane(a.used[kvh / a.Hkv]), 0, a.Skv);
+    // the split plan (workgroup-uniform, as everything down to the row numbers)
+    const int nkb = (L + 127) >> 7, per = (nkb + a.ns - 1) / a.ns;
+    const int k_begin = 128 * s * per, k_end = min(128 * (s + 1) * per, L);
+    const int r_first = tile * kFpvTile, r_last = min(r_first + kFpvTile, a.rows) - 1;
+    // positions of the tile's valid rows: [smin, smax] (a tile that crosses a head boundary holds a last and a first position)
+    const int g_first = r_first / a.Sq, g_last = r_last / a.Sq;
+    const int smin = g_first != g_last ? 0 : r_first - g_first * a.Sq, smax = g_first != g_last ? a.Sq - 1 : r_last - g_first * a.Sq;
+    const int delta = L - a.Sq;   // causal: position p attends the keys j <= p + delta
+    const int khi = a.causal ? min(k_end - 1, smax + delta) : k_end - 1;
+    const int keys = max(khi - k_begin + 1, 0);   // the keys this workgroup sweeps
+    if (sel == kFpvSelMany && keys < a.two_term_keys) return;
+    if (sel == kFpvSelFew && keys >= a.two_term_keys) return;
+
+    const int r = r_first + wave * kQPerWave + ql;   // packed row
+    const bool rvalid = r < a.rows;
+    const int g = min(r / a.Sq, a.G - 1);            // (padding rows: the last head's scale)
+    const long grow = (long)kvh * a.rows + r;        // row of the dense [B Hq Sq] index space
+    if (keys == 0) {   // no key for any row of the tile in this split (L = 0, a split past the last block, a split above the causal edge)
+        if (a.ns == 1) {
+            fpv_store_empty<D>(a.out, a.out_fmt, (rvalid ? grow : 0L) * (2L * D), a.lse, grow, a.path, grow, hh, rvalid);
+        } else {
+            const long prow = (long)s * a.part_rows + (rvalid ? grow : 0L);
+            v16f z[MB];
+#pragma unroll
+            for (int m = 0; m < MB; m++)
+#pragma unroll
+                for (int e = 0; e < 16; e++) z[m][e] = 0.0f;
+            store_o_rows_f32<MB>(a.po + prow * D, z, 0.0f, hh, rvalid);
+            if (hh == 0 && rvalid) a.plse[prow] = -INFINITY;
+            if (a.ppath && hh == 0 && rvalid) a.ppath[prow] = (unsigned char)QATTN_PATH_ONE_TERM;
+        }
+        return;
+    }
+    const int c_first = k_begin >> 6;               // chunks c_first .. khi / 64 <= (L - 1) / 64 < nchunks
+    const int n_wg = (khi >> 6) - c_first + 1;
+
+#if QATTN_SKV_PAGED
+    // The ring's base is the pool itself; a step's chunk is (page Hkv + hkv) pc + its chunk within the page.  (p_idx, p_ch) count pages and
+    // chunks-in-page along the sweep -- one division here, none in the loop -- and always stand at the chunk whose DMA is issued NEXT;
+    // e_next is the RAW table entry of that chunk's page, loaded when the sweep enters the page: a step before the DMA that needs it.
+    // The chunks c_first .. c_first + n_wg - 1 lie below ceil(L / 64), so their entries lie below ceil(L / page_size) <= max_pages: the
+    // only ones read.  skv_phys clamps an entry where it forms the address.
+    const int phk = kvh % a.Hkv;
+    const int* prow = pg.table + (long)(kvh / a.Hkv) * pg.stride;
+    int p_idx = c_first / pg.pc, p_ch = c_first % pg.pc;
+    FpvRing<D> ring(smem, wave, lane, a.k8 + (wave << 10), a.v8 + (wave << 10));
+    int e_next = prow[p_idx];
+    ring.dma_chunk(skv_phys(pg, e_next, a.Hkv, phk, p_ch));
+    if (++p_ch == pg.pc) {
+        p_ch = 0;
+        p_idx++;
+        if (n_wg > 1) e_next = prow[p_idx];
+    }
+#else
+    const long img = (long)kvh * a.nchunks * CH + (wave << 10);
+    FpvRing<D> ring(smem, wave, lane, a.k8 + img, a.v8 + img);
+    ring.dma_chunk(c_first);
+#endif
+    sw.park_q(a.q8 + (rvalid ? grow : (long)kvh * a.rows) * D + hh * 32, rvalid);
+    constexpr float kNoKeyYet = -1.0e20f;   // (attn_vfp8_window_kernel's header comment)
+    sw.init_state(a.sm_log2e * a.sq[(long)kvh * a.G + g] * a.sk[kvh], kNoKeyYet);
+    const int one = fpv_ones_word(lane);
+    // the last key this lane's row attends, and the first chunk end that crosses the causal edge of some valid row
+    const int hi_l = (a.causal && rvalid) ? min(L - 1, r - g * a.Sq + delta) : L - 1;
+    const int edge = a.causal ? smin + delta : INT_MAX;
+
+    for (int t = 0; t < n_wg; t++) {   // step t sweeps chunk c_first + t
+        const int k0 = (c_first + t) * 64;
+        if (__builtin_expect(k0 + 64 > L, 0)) {   // the chunk that holds key L: its stage is waited for here, ahead of the step's own (then idle) wait
+            sw.wait_stage();
+            skv_zero_v_tail<D>(smem + (t & 1) * (2 * CH) + CH, L - k0);
+        }
+        v8i qf[KS];
+        sw.read_q(qf);
+        sw.wait_stage();
+#if QATTN_SKV_PAGED
+        if (t + 1 < n_wg) {
+            ring.dma_chunk(skv_phys(pg, e_next, a.Hkv, phk, p_ch));
+            if (++p_ch == pg.pc) {   // the chunk after this one opens a page: its entry is in flight during this step's products
+                p_ch = 0;
+                p_idx++;
+                if (t + 2 < n_wg) e_next = prow[p_idx];
+            }
+        }
+#else
+        if (t + 1 < n_wg) ring.dma_chunk(c_first + t + 1);
+#endif
+        v16f s0, s1;
+        v8i vf0, vf1;
+        sw.qk(t, qf, s0, s1, vf0, vf1);
+        // ---- the ragged tail at L and the causal edge by token, under a workgroup-uniform condition
+        if (__builtin_expect(k0 + 64 > L || k0 + 63 > edge, 0)) {
+            const int base = k0 + 4 * hh;
+#pragma unroll
+            for (int e = 0; e < 32; e++) {
+                const int key = base + 32 * (e >> 4) + (e & 3) + 8 * ((e & 15) >> 2);
+                v16f& sx = (e >> 4) ? s1 : s0;
+                sx[e & 15] = key > hi_l ? -INFINITY : sx[e & 15];
+            }
+        }
+        sw.softmax_pv(s0, s1, vf0, vf1, two, [&] { return fpv_spread_ones(one); });
+    }
+
+    // ---- epilogue (V's one scale per kv head is applied here)
+    const float l_tot = sw.row_sum();
+    const bool has_key = l_tot > 0.0f;   // (a row without a key inside a workgroup that sweeps: every P was 0 -- a zero row, LSE -inf)
+    const float inv = has_key ? a.sv[kvh] / l_tot : 0.0f;
+    const float lse_row = has_key ? 0.6931471805599453f * (sw.m_run * sw.c - kPShift) + __logf(l_tot) : -INFINITY;
+    const unsigned char code = (unsigned char)((!BYTE && two) ? QATTN_PATH_TWO_TERM : QATTN_PATH_ONE_TERM);
+    if (a.ns == 1) {
+        store_o_rows<MB>(a.out, a.out_fmt, sw.o, inv, (rvalid ? grow : 0L) * (2L * D), hh, rvalid);
+        if (!BYTE && a.lse && hh == 0 && rvalid) a.lse[grow] = lse_row;
+        if (a.path && hh == 0 && rvalid) a.path[grow] = code;
+    } else {
+        const long prow = (long)s * a.part_rows + (rvalid ? grow : 0L);
+        store_o_rows_f32<MB>(a.po + prow * D, sw.o, inv, hh, rvalid);
+        if (!BYTE && hh == 0 && rvalid) a.plse[prow] = lse_row;
+        if (a.ppath && hh == 0 && rvalid) a.ppath[prow] = code;
+    }

@@ -15,8 +15,9 @@ behind them.
 Rollback (speculative decoding: the rejected tokens of a draft) is `cache.seqlens.sub_(n)`: legal because bytes behind `seqlens` influence
 no output bit of the attention entry, and the next append overwrites them.
 
-Package attributes, not names of `__all__` (that list mirrors the reference).  Not offered: a paged cache (block table), re-scaling a live
-cache, token-wise K or chunk-wise V scales, key smoothing on cached keys."""
+Package attributes, not names of `__all__` (that list mirrors the reference).  A paged cache (a pool of pages behind a block table) is
+paged.py's (alloc_paged_kv_cache_fp8, paged_kv_cache_append_fp8, fp8_attn_paged_func).  Not offered: re-scaling a
+live cache, token-wise K or chunk-wise V scales, key smoothing on cached keys."""
 import math
 from typing import Optional
 

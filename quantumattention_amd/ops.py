@@ -550,3 +550,84 @@ def fp8_kv_cache_append_(
 @_register_fake("quantumattention_amd::fp8_kv_cache_append_")
 def _(k_frag, v_frag, scale_k, scale_v, seqlens, k_new, v_new, new_lens, capacity, fp8_format="e4m3", advance=True):
     return None
+
+
+@_custom_op("quantumattention_amd::fp8_paged_splitkv_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_paged_splitkv_attention_forward(
+    query: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    seqlen_k: int,
+    num_pages: int,
+    page_size: int,
+    num_splits: int,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    is_causal: bool = False,
+    precision: str = "accurate",
+    return_lse: bool = False,
+    return_partials: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Split-KV FP8 attention of a short query over a PAGED cache (include/qattn_paged.h): fp8_splitkv_attention_forward with the pools
+    k_pool / v_pool (flat uint8: the KFRAG / VFRAG images of [num_pages, Hkv, page_size, D]) and block_table int32 [B, max_pages] in place
+    of the contiguous images; seqlen_k <= max_pages page_size is the logical bound, seqused_k int32 [B] is required; table and lengths are
+    read on the device.  Returns (out, lse, partial_o, partial_lse, partial_path) as that op does.  Reference implementation:
+    paged._attend_eager.  Arguments are validated by paged.fp8_attn_paged_func."""
+    res = _native.fp8_attention_paged_splitkv(
+        query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, Skv=seqlen_k, num_pages=num_pages, page_size=page_size,
+        fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics, is_causal=is_causal, sm_scale=0.0 if scale is None else float(scale),
+        precision=precision, num_splits=num_splits, return_lse=return_lse, return_partials=return_partials)
+    res = res if isinstance(res, tuple) else (res,)
+    none_f = lambda: torch.empty((0,), dtype=torch.float32, device=query.device)
+    out = res[0]
+    lse = res[1] if return_lse else none_f()
+    parts = res[-3:] if return_partials else (none_f(), none_f(), torch.empty((0,), dtype=torch.uint8, device=query.device))
+    return (out, lse) + tuple(parts)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_splitkv_attention_forward")
+def _(query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, seqlen_k, num_pages, page_size, num_splits, fp8_format="e4m3",
+      numerics="compiled", is_causal=False, precision="accurate", return_lse=False, return_partials=False, *, scale=None):
+    B, Hq, Sq, D = query.shape
+    out = query.new_empty((B, Hq, Sq, D))
+    lse = query.new_empty((B, Hq, Sq) if return_lse else (0,), dtype=torch.float32)
+    n = num_splits if num_splits > 1 else 0
+    if return_partials:
+        return (out, lse, query.new_empty((n, B, Hq, Sq, D), dtype=torch.float32), query.new_empty((n, B, Hq, Sq), dtype=torch.float32),
+                query.new_empty((n, B, Hq, Sq), dtype=torch.uint8))
+    return (out, lse, query.new_empty((0,), dtype=torch.float32), query.new_empty((0,), dtype=torch.float32),
+            query.new_empty((0,), dtype=torch.uint8))
+
+
+@_custom_op("quantumattention_amd::fp8_paged_kv_cache_append_", mutates_args=("k_pool", "v_pool", "seqlens"), device_types=("cuda",))
+def fp8_paged_kv_cache_append_(
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens: torch.Tensor,
+    k_new: torch.Tensor,
+    v_new: torch.Tensor,
+    new_lens: Optional[torch.Tensor],
+    num_pages: int,
+    page_size: int,
+    fp8_format: str = "e4m3",
+    advance: bool = True,
+) -> None:
+    """Append to a PAGED FP8 K/V cache IN PLACE (include/qattn_paged.h): fp8_kv_cache_append_ into the pools k_pool / v_pool (flat uint8: the
+    KFRAG / VFRAG images of [num_pages, Hkv, page_size, D]) through block_table int32 [B, max_pages]; capacity = max_pages page_size.
+    Reference implementation: paged._append_eager.  Arguments are validated by paged.paged_kv_cache_append_fp8."""
+    _native.paged_kv_cache_append_fp8(k_pool, v_pool, scale_k, scale_v, block_table, seqlens, k_new, v_new, num_pages=num_pages,
+                                      page_size=page_size, fp8_dtype=_native.fp8_dtype_of(fp8_format), new_lens=new_lens, advance=advance)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_kv_cache_append_")
+def _(k_pool, v_pool, scale_k, scale_v, block_table, seqlens, k_new, v_new, new_lens, num_pages, page_size, fp8_format="e4m3", advance=True):
+    return None

@@ -13,8 +13,9 @@ Numerics (include/qattn_splitkv.h): q is quantised head-wise by the quant pre-pa
 attends; both products run on the FP8 matrix pipe.  Package attributes, not names of `__all__` (that list mirrors the reference).
 
 An appendable cache with FIXED scales is kvcache.KVCacheFP8 (kv_cache_append_fp8): a PreparedKV this entry attends
-unchanged.  Not offered: a paged cache, scales that grow with the tensor, key smoothing on prepared keys,
-precision="auto", the 16-bit-P.V numerics, sliding windows, strided views."""
+unchanged.  A PAGED cache (a pool of pages behind a block table) is paged.PagedKVCacheFP8 with its own entry, fp8_attn_paged_func
+(DESIGN.md section 4.19): the bits of this entry on the gathered cache.  Not offered: scales that grow with the
+tensor, key smoothing on prepared keys, precision="auto", the 16-bit-P.V numerics, sliding windows, strided views."""
 import math
 from typing import Optional, Tuple
 
@@ -44,7 +45,7 @@ class PreparedKV:
       numerics         the quantiser's numerics ("compiled" / "eager");   layout "frag" / "rowmajor"
     Treat what `prepare_kv_fp8` returns as immutable: its scales cover exactly these keys, so nothing can be appended to it.  The appendable
     kind is the subclass kvcache.KVCacheFP8 -- fixed scales, a capacity and device-side lengths (alloc_kv_cache_fp8,
-    kv_cache_from_prefill_fp8, kv_cache_append_fp8); a paged cache is not offered."""
+    kv_cache_from_prefill_fp8, kv_cache_append_fp8); a paged cache is paged.PagedKVCacheFP8 (not a PreparedKV: fp8_attn_paged_func)."""
 
     __slots__ = ("k", "v", "scale_k", "scale_v", "shape", "fp8_format", "dtype", "numerics", "layout")
 
