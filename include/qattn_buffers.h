@@ -1,6 +1,6 @@
 /*
  * qattn_buffers.h -- the BUFFER CONTRACT of every entry of qattn.h, qattn_strided.h, qattn_smooth.h, qattn_varlen.h, qattn_window.h and
- * qattn_block_sparse.h, and of qattn_rope.h, qattn_splitkv.h, qattn_kvcache.h and qattn_paged.h (documentation only: no declaration).  Held by
+ * qattn_block_sparse.h, and of qattn_rope.h, qattn_splitkv.h, qattn_kvcache.h, qattn_paged.h and qattn_paged_varlen.h (documentation only: no declaration).  Held by
  * tests/test_gpu_buffer_contract.py (qattn_rope.h: tests/test_gpu_rope_buffer_contract.py; qattn_splitkv.h:
  * tests/test_gpu_splitkv_buffer_contract.py; qattn_kvcache.h: tests/test_gpu_kvcache_buffer_contract.py; qattn_paged.h:
  * tests/test_gpu_paged_buffer_contract.py) on guarded buffers of exactly these sizes at exactly these alignments.
@@ -100,6 +100,27 @@
  *              pages that hold the appended keys / the chunks named above, no other entry; each clamped before it forms an address.
  *   seqused_k  int32 [B], 4-byte aligned, REQUIRED by the attention entry.
  *   workspace  qattn_fp8_attention_paged_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, num_splits) bytes, 16-byte aligned (the append: none).
+ *
+ * qattn_fp8_attention_paged_varlen_forward (qattn_paged_varlen.h; held by tests/test_gpu_paged_varlen_buffer_contract.py): k_pool, v_pool,
+ * block_table, scale_k, scale_v and seqused_k as the paged attention entry above (L_i, the entries and chunks read: per sequence i), and
+ *   q16        [total_q, Hq, D] 16-bit through the element strides {token, head} of q_strides2 (NULL: dense), head_dim innermost and dense;
+ *              base 16-byte aligned, both strides NON-NEGATIVE multiples of 8 elements.  Read: the D elements of each (token, head) row of
+ *              the tokens that belong to a sequence, no other byte -- not the pads between rows or heads.
+ *   cu_seqlens_q  int32 [B + 1], 4-byte aligned; read, every extent clamped into [0, total_q].
+ *   out        dense [total_q, Hq, D] in in_fmt, 16-byte aligned.   lse: NULL or fp32 [Hq, total_q], 4-byte aligned (FAST with ns = 1: as the
+ *              split-KV entry).   row_path: NULL or uint8 [Hq, total_q], 1-byte aligned.
+ *   q8         NULL or Hq total_q D bytes, 16-byte aligned: sequence i's row-major [Hq, Sq_i, D] slab at byte Hq D start_i.   scale_q: NULL or
+ *              fp32 [B, Hq], 4-byte aligned: every element written, an idle sequence's too.
+ *   partial_o  NULL or fp32 [ns, total_q, Hq, D], 16-byte aligned; partial_lse: NULL or fp32 [ns, Hq, total_q], 4-byte aligned; partial_path:
+ *              NULL or uint8 [ns, Hq, total_q], 1-byte aligned.  ns > 1: written and left as the sweep wrote them; ns = 1: not touched.
+ *   written    of out, lse, row_path, q8 and the partials: every element of every token that belongs to a sequence (a row without a key:
+ *              zeros, -inf, QATTN_PATH_ONE_TERM) -- with a consistent cu_seqlens_q whose last entry is total_q, every element.  The rows
+ *              of tokens that belong to no sequence (cu_seqlens_q[B] < total_q) have unspecified contents: out, lse and row_path rows of
+ *              such tokens are written by the merge with ns > 1 (from partials nobody wrote) and not at all with ns = 1.
+ *   workspace  qattn_fp8_attention_paged_varlen_workspace_bytes(B, Hq, Hkv, total_q, Skv, D, num_splits) bytes (num_splits as passed: 0 sizes
+ *              it for the most splits), 16-byte aligned, needed whenever total_q > 0 (total_q = 0: nothing is launched or written, the
+ *              workspace's size is not looked at); it holds whatever optional output is NULL, the pre-pass's abs-max words and, for ns > 8, the merge's fp32 accumulator; no
+ *              result depends on what it held.
  */
 #ifndef QATTN_BUFFERS_H_
 #define QATTN_BUFFERS_H_

@@ -55,7 +55,8 @@
  * aligned (pools 16 bytes, block_table 4 bytes).  Buffers: include/qattn_buffers.h.
  *
  * Not offered: page allocation, copy-on-write, re-scaling, a per-call table whose batch differs from the scales' and lengths', sliding
- * windows.
+ * windows.  Queries of a DIFFERENT count per sequence (a serving step that mixes prefill chunks and decodes), packed as [total_q, Hq, D]
+ * under cu_seqlens_q: include/qattn_paged_varlen.h.
  */
 #ifndef QATTN_PAGED_H_
 #define QATTN_PAGED_H_

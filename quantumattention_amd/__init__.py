@@ -47,6 +47,8 @@ from .kvcache import KVCacheFP8, alloc_kv_cache_fp8, kv_cache_append_fp8, kv_cac
 
 # a paged FP8 K/V cache (a pool of pages behind a block table) for split-KV decode (include/qattn_paged.h): package attributes too, not in __all__
 from .paged import PagedKVCacheFP8, alloc_paged_kv_cache_fp8, fp8_attn_paged_func, paged_kv_cache_append_fp8  # noqa: E402
+# ... under PACKED queries, a different count per sequence slot (include/qattn_paged_varlen.h): a package attribute, not in __all__
+from .paged_varlen import fp8_attn_paged_varlen_func  # noqa: E402
 
 __version__ = "0.1.0"
 

@@ -54,6 +54,7 @@ EXPORTS = (
     "qattn_fp8_attention_splitkv_workspace_bytes", "qattn_splitkv_auto_splits", "qattn_fp8_attention_splitkv_forward",
     "qattn_kv_cache_append_fp8",
     "qattn_paged_kv_cache_append_fp8", "qattn_fp8_attention_paged_splitkv_workspace_bytes", "qattn_fp8_attention_paged_splitkv_forward",
+    "qattn_fp8_attention_paged_varlen_workspace_bytes", "qattn_paged_varlen_auto_splits", "qattn_fp8_attention_paged_varlen_forward",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -250,6 +251,16 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_attention_paged_splitkv_forward.restype = i
     L.qattn_fp8_attention_paged_splitkv_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f, i, i,
                                                             vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    # packed queries over the paged cache (include/qattn_paged_varlen.h): q16, q_strides2, in_fmt, k_pool, v_pool, block_table, table_stride,
+    # num_pages, page_size, max_pages, scale_k, scale_v, out, lse, cu_seqlens_q, seqused_k, B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, fp8_fmt,
+    # numerics, is_causal, sm_scale, precision, num_splits, q8, scale_q, row_path, partial_o, partial_lse, partial_path, workspace, bytes, stream
+    L.qattn_fp8_attention_paged_varlen_workspace_bytes.restype = sz
+    L.qattn_fp8_attention_paged_varlen_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
+    L.qattn_paged_varlen_auto_splits.restype = i
+    L.qattn_paged_varlen_auto_splits.argtypes = [i, i, i, i, i, i, i, i]
+    L.qattn_fp8_attention_paged_varlen_forward.restype = i
+    L.qattn_fp8_attention_paged_varlen_forward.argtypes = [vp, vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i,
+                                                           f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1321,6 +1332,83 @@ def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: t
             _numerics(numerics), int(bool(is_causal)), float(sm_scale), _precision(precision), ns, _ptr(q8), _ptr(sq), _ptr(path), live(po),
             live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
     _check(rc, "qattn_fp8_attention_paged_splitkv_forward")
+    if not (return_lse or return_partials or return_quant or return_path):
+        return out
+    return ((out,) + ((lse,) if return_lse else ()) + ((po, plse, ppath) if return_partials else ()) + ((q8, sq) if return_quant else ())
+            + ((path,) if return_path else ()))
+
+
+def paged_varlen_auto_splits(B: int, Hq: int, Hkv: int, total_q: int, max_seqlen_q: int, Skv: int, D: int, num_cus: int) -> int:
+    """qattn_paged_varlen_auto_splits (include/qattn_paged_varlen.h): the num_splits = 0 rule of the packed paged entry, a pure host function."""
+    return int(lib().qattn_paged_varlen_auto_splits(B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, num_cus))
+
+
+def paged_varlen_q_addressable(q: torch.Tensor) -> bool:
+    """A 3-D view [total_q, Hq, D] qattn_fp8_attention_paged_varlen_forward reads in place: head_dim innermost and dense, token and head
+    strides of a dimension longer than 1 non-negative multiples of 8 elements, base 16-byte aligned (rows 16-byte aligned)."""
+    return (q.dim() == 3 and (q.shape[2] == 1 or q.stride(2) == 1) and q.data_ptr() % 16 == 0
+            and all(q.shape[i] == 1 or (q.stride(i) >= 0 and q.stride(i) % 8 == 0) for i in (0, 1)))
+
+
+def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor,
+                               block_table: torch.Tensor, seqused_k: torch.Tensor, cu_seqlens_q: torch.Tensor, *, max_seqlen_q: int, Skv: int,
+                               num_pages: int, page_size: int, fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled",
+                               is_causal: bool = False, sm_scale: float = 0.0, precision: str = "accurate", num_splits: int = 0,
+                               return_lse: bool = False, return_partials: bool = False, return_quant: bool = False, return_path: bool = False):
+    """Split-KV attention of PACKED queries over a paged cache (qattn_fp8_attention_paged_varlen_forward, include/qattn_paged_varlen.h).
+    q [total_q, Hq, D] bf16 / fp16, dense or a view `paged_varlen_q_addressable` accepts (read in place); cu_seqlens_q int32 [B + 1] and
+    seqused_k int32 [B] on the device; the pools, the table and the scales as fp8_attention_paged_splitkv.  num_splits 0: the auto rule on
+    the device's CU count (resolved here, on the host).  Returns out [total_q, Hq, D], or a tuple of out, [lse [Hq, total_q]], [partial_o
+    fp32 [ns, total_q, Hq, D], partial_lse [ns, Hq, total_q], partial_path uint8 -- three empty tensors when the call ran one split],
+    [q8 [Hq total_q D] flat, scale_q [B, Hq]], [row_path uint8 [Hq, total_q]]."""
+    _require(precision in ("fast", "accurate"), f"Unsupported precision for the split-KV entry: {precision!r} (expected 'fast' or 'accurate')")
+    _require(q.is_cuda and q.dim() == 3 and q.dtype in (torch.bfloat16, torch.float16), "query must be a 3-D bf16 / fp16 device tensor [total_q, Hq, D]")
+    _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
+    total_q, Hq, D = q.shape
+    if total_q and not paged_varlen_q_addressable(q):
+        q = q.contiguous()
+    _require(scale_k.dim() == 2, "scale_k / scale_v must be fp32 [B, Hkv]")
+    B, Hkv = scale_k.shape
+    _require(Hkv > 0 and Hq % Hkv == 0, f"Hq={Hq} is not a multiple of Hkv={Hkv}")
+    L = lib()
+    dev = q.device
+    max_pages, tstride = _paged_pool_checks(L, k_pool, v_pool, block_table, scale_k, scale_v, dev, B, Hkv, num_pages, page_size, D)
+    _require(isinstance(Skv, int) and 0 < Skv <= max_pages * page_size, f"Skv must be in 1 .. max_pages * page_size = {max_pages * page_size}, got {Skv}")
+    _require(isinstance(max_seqlen_q, int) and max_seqlen_q >= 1, f"max_seqlen_q must be an integer >= 1, got {max_seqlen_q}")
+    _require(seqused_k is not None and seqused_k.dtype == torch.int32 and seqused_k.device == dev and tuple(seqused_k.shape) == (B,)
+             and seqused_k.is_contiguous(), f"seqused_k must be a dense int32 [B] tensor on {dev}")
+    _require(cu_seqlens_q.dtype == torch.int32 and cu_seqlens_q.device == dev and tuple(cu_seqlens_q.shape) == (B + 1,)
+             and cu_seqlens_q.is_contiguous(), f"cu_seqlens_q must be a dense int32 [B + 1] tensor on {dev}")
+    ns = int(num_splits)
+    if ns == 0:
+        ns = paged_varlen_auto_splits(B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, torch.cuda.get_device_properties(dev).multi_processor_count)
+    with torch.cuda.device(dev):
+        out = torch.empty((total_q, Hq, D), dtype=q.dtype, device=dev)
+        lse = torch.empty((Hq, total_q), dtype=torch.float32, device=dev) if return_lse else None
+        po = plse = ppath = q8 = sq = path = None
+        if return_partials:
+            n = ns if ns > 1 else 0
+            po = torch.empty((n, total_q, Hq, D), dtype=torch.float32, device=dev)
+            plse = torch.empty((n, Hq, total_q), dtype=torch.float32, device=dev)
+            ppath = torch.empty((n, Hq, total_q), dtype=torch.uint8, device=dev)
+        if return_quant:
+            q8 = torch.empty((Hq * total_q * D,), dtype=fp8_dtype, device=dev)
+            sq = torch.empty((B, Hq), dtype=torch.float32, device=dev)
+        if return_path:
+            path = torch.empty((Hq, total_q), dtype=torch.uint8, device=dev)
+        rc = 0
+        if total_q:
+            ws_bytes = L.qattn_fp8_attention_paged_varlen_workspace_bytes(B, Hq, Hkv, total_q, Skv, D, ns)
+            ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+            live = lambda t: _ptr(t) if t is not None and t.numel() else None
+            dense = (Hq * D, D)     # (a dimension of size 1 has no stride of its own)
+            s2 = (ctypes.c_longlong * 2)(*[q.stride(i) if q.shape[i] > 1 else dense[i] for i in (0, 1)])
+            rc = L.qattn_fp8_attention_paged_varlen_forward(
+                q.data_ptr(), s2, fmt_of(q.dtype), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), tstride, num_pages, page_size,
+                max_pages, scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), seqused_k.data_ptr(), B, Hq,
+                Hkv, total_q, max_seqlen_q, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), int(bool(is_causal)), float(sm_scale),
+                _precision(precision), ns, live(q8), _ptr(sq), live(path), live(po), live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
+    _check(rc, "qattn_fp8_attention_paged_varlen_forward")
     if not (return_lse or return_partials or return_quant or return_path):
         return out
     return ((out,) + ((lse,) if return_lse else ()) + ((po, plse, ppath) if return_partials else ()) + ((q8, sq) if return_quant else ())

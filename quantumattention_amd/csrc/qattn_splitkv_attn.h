@@ -3,6 +3,9 @@
 // qattn_fp8_attention_paged_splitkv_forward (qattn_paged_splitkv_fp8.hip: a pool of pages behind a block table, include/qattn_paged.h).
 // The kernel body is qattn_splitkv_body.h, compiled once per chunk addressing; each unit instantiates its own kernels only, and the
 // contiguous kernel is, statement for statement, the kernel qattn_splitkv_fp8.hip held before the paged entry existed.
+// A third compilation of the body, paged K / V under PACKED queries of a different count per sequence, belongs to
+// qattn_fp8_attention_paged_varlen_forward (qattn_paged_varlen_splitkv_fp8.hip, include/qattn_paged_varlen.h); that entry has a driver of
+// its own and shares the launch ladder, the merge chain (skv_merge_chain) and the path launch with skv_forward.
 #pragma once
 #include <limits.h>
 
@@ -37,6 +40,14 @@ struct SkvPages {
     const int* table;   // [B][stride]
     long stride;
     int num_pages, pc;  // pages of the pool; 64-key chunks per page
+};
+
+// VARQ: packed queries (include/qattn_paged_varlen.h).  q8 / out / the partials are [total_q, Hq, D]-shaped and the LSE-like outputs
+// [Hq, total_q]; sequence i owns the tokens [clamp(cu[i]), clamp(cu[i + 1])).  SkvAttn then carries ntile = B + ceil(G total_q / 128) (tile
+// slots per kv head) and part_rows = total_q Hq; its Sq and rows are not read.
+struct SkvVarq {
+    const int* cu;   // cu_seqlens_q [B + 1]
+    int B, total_q, Hq;
 };
 
 // Physical chunk of chunk `ch` of kv head hkv of the page a RAW table entry names.  The clamp is what keeps every address inside the
@@ -87,7 +98,9 @@ template <int D, int FMT, bool BYTE>
 __global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
 void attn_splitkv_fp8_kernel(const SkvAttn a, const int two, const int sel) {
 #define QATTN_SKV_PAGED 0
+#define QATTN_SKV_VARQ 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
 }
 
@@ -95,22 +108,51 @@ template <int D, int FMT, bool BYTE>
 __global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
 void attn_paged_splitkv_fp8_kernel(const SkvAttn a, const SkvPages pg, const int two, const int sel) {
 #define QATTN_SKV_PAGED 1
+#define QATTN_SKV_VARQ 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
 }
 
-template <int D, int FMT, bool PAGED>
-static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, unsigned grid, int max_keys, int precision, bool want_lse, hipStream_t st) {
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_paged_varlen_splitkv_fp8_kernel(const SkvAttn a, const SkvPages pg, const SkvVarq vq, const int two, const int sel) {
+#define QATTN_SKV_PAGED 1
+#define QATTN_SKV_VARQ 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+// which of the three kernels a launch runs
+constexpr int kSkvContig = 0, kSkvPaged = 1, kSkvPagedVarq = 2;
+
+template <int D, int FMT, int MODE>
+static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, unsigned grid, int max_keys, int precision, bool want_lse,
+                          hipStream_t st) {
     return fpv_precision_ladder(precision, max_keys, a.two_term_keys, want_lse, [&](auto byte, int two, int sel) {
-        if constexpr (PAGED) return fpv_launch(attn_paged_splitkv_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg, two, sel);
+        if constexpr (MODE == kSkvPagedVarq)
+            return fpv_launch(attn_paged_varlen_splitkv_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg, vq, two, sel);
+        else if constexpr (MODE == kSkvPaged)
+            return fpv_launch(attn_paged_splitkv_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg, two, sel);
         else return fpv_launch(attn_splitkv_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, two, sel);
     });
 }
 
-template <int D, bool PAGED>
-static int launch_skv_d(const SkvAttn& a, const SkvPages& pg, unsigned grid, int max_keys, int fp8_fmt, int precision, bool want_lse, hipStream_t st) {
-    return fp8_fmt == QATTN_FMT_E4M3 ? launch_skv_fmt<D, QATTN_FMT_E4M3, PAGED>(a, pg, grid, max_keys, precision, want_lse, st)
-                                     : launch_skv_fmt<D, QATTN_FMT_E5M2, PAGED>(a, pg, grid, max_keys, precision, want_lse, st);
+template <int D, int MODE>
+static int launch_skv_d(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, unsigned grid, int max_keys, int fp8_fmt, int precision,
+                        bool want_lse, hipStream_t st) {
+    return fp8_fmt == QATTN_FMT_E4M3 ? launch_skv_fmt<D, QATTN_FMT_E4M3, MODE>(a, pg, vq, grid, max_keys, precision, want_lse, st)
+                                     : launch_skv_fmt<D, QATTN_FMT_E5M2, MODE>(a, pg, vq, grid, max_keys, precision, want_lse, st);
+}
+
+// every head dimension of one entry
+template <int MODE>
+static int launch_skv(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, unsigned grid, int max_keys, int D, int fp8_fmt, int precision,
+                      bool want_lse, hipStream_t st) {
+    if (D == 64) return launch_skv_d<64, MODE>(a, pg, vq, grid, max_keys, fp8_fmt, precision, want_lse, st);
+    if (D == 128) return launch_skv_d<128, MODE>(a, pg, vq, grid, max_keys, fp8_fmt, precision, want_lse, st);
+    return launch_skv_d<256, MODE>(a, pg, vq, grid, max_keys, fp8_fmt, precision, want_lse, st);
 }
 
 inline bool skv_dims_ok(int B, int Hq, int Hkv, int Sq, int Skv) { return B > 0 && Hq > 0 && Hkv > 0 && Sq > 0 && Skv > 0; }
@@ -141,6 +183,42 @@ inline SkvWs skv_ws(int B, int Hq, int Sq, int D, int ns) {
 
 // splitkv_path_kernel's launch (qattn_splitkv_fp8.hip): row_path of a merged row from the per-split path bytes
 int skv_launch_path(const float* plse, const unsigned char* ppath, unsigned char* path, long rows, int ns, hipStream_t st);
+
+// the num_splits = 0 rule from the count of (kv head, tile) work items on (qattn_splitkv_fp8.hip): residency, the key-block cap, the
+// fewest splits with the same blocks per split.  Both auto_splits functions are this on their own tile count.
+int skv_auto_splits_of_tiles(long long tiles, int Skv, int D, int num_cus);
+
+// The merge of ns > 1 fp32 partials po [ns][rows][D] / plse [ns][rows] into out / lse: partials 0 .. 7 (into the accumulator when more
+// follow), then 7 more per launch in place, the last one into out.  os3 / ls3: the element strides (batch, head, query) every partial,
+// the accumulator and the destination share -- dense [B, Hq, Sq, D] / [B, Hq, Sq], or the packed conventions of include/qattn_merge.h with
+// B = 1, Sq = total_q.  acc / acc_lse are read only with ns > QATTN_MERGE_MAX_PARTIALS.
+inline int skv_merge_chain(const float* po, const float* plse, int ns, long rows, const long long (&os3)[3], const long long (&ls3)[3], int B,
+                           int Hq, int Sq, int D, void* out, int out_fmt, float* lse, float* acc, float* acc_lse, void* stream) {
+    constexpr int top = QATTN_MERGE_MAX_PARTIALS;
+    auto merge = [&](const float* o0, const float* l0, int first, int n_more, void* dst, int dst_fmt, float* dst_lse) -> int {
+        const void* o[top];
+        const float* l[top];
+        int fmt[top];
+        long long ostr[3 * top], lstr[3 * top];
+        int n = 0;
+        if (o0) { o[n] = o0; l[n] = l0; n++; }
+        for (int i = 0; i < n_more; i++, n++) { o[n] = po + (size_t)(first + i) * rows * D; l[n] = plse + (size_t)(first + i) * rows; }
+        for (int i = 0; i < n; i++) {
+            fmt[i] = QATTN_FMT_FP32;
+            for (int j = 0; j < 3; j++) { ostr[3 * i + j] = os3[j]; lstr[3 * i + j] = ls3[j]; }
+        }
+        return qattn_attention_state_merge(n, o, fmt, ostr, l, lstr, dst, dst_fmt, os3, dst_lse, ls3, B, Hq, Sq, D, stream);
+    };
+    if (ns <= top) return merge(nullptr, nullptr, 0, ns, out, out_fmt, lse);
+    int rc = merge(nullptr, nullptr, 0, top, acc, QATTN_FMT_FP32, acc_lse);
+    int done = top;
+    while (rc == QATTN_OK && ns - done > top - 1) {
+        rc = merge(acc, acc_lse, done, top - 1, acc, QATTN_FMT_FP32, acc_lse);
+        done += top - 1;
+    }
+    if (rc == QATTN_OK) rc = merge(acc, acc_lse, done, ns - done, out, out_fmt, lse);
+    return rc;
+}
 
 // Both entries, from their common arguments on: k8 / v8 are the contiguous images of [B, Hkv, Skv, D] or -- PAGED, with pg filled in and
 // checked by the caller -- the pools.
@@ -214,41 +292,13 @@ int skv_forward(const void* q16, int in_fmt, const void* k8, const void* v8, con
     const int max_keys = span < Skv ? (int)span : Skv;
     const bool want_lse = lse != nullptr || ns > 1;
     const unsigned grid = (unsigned)((long long)B * Hkv * ntile * ns);
-    if (D == 64) rc = launch_skv_d<64, PAGED>(a, pg, grid, max_keys, fp8_fmt, precision, want_lse, st);
-    else if (D == 128) rc = launch_skv_d<128, PAGED>(a, pg, grid, max_keys, fp8_fmt, precision, want_lse, st);
-    else rc = launch_skv_d<256, PAGED>(a, pg, grid, max_keys, fp8_fmt, precision, want_lse, st);
+    rc = launch_skv<PAGED ? kSkvPaged : kSkvContig>(a, pg, SkvVarq{}, grid, max_keys, D, fp8_fmt, precision, want_lse, st);
     if (rc != QATTN_OK) return rc;
     if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
     if (ns == 1) return QATTN_OK;
 
-    // ---- the merge: partials 0 .. 7 (into the accumulator when more follow), then 7 more per launch in place, the last one into out
-    constexpr int top = QATTN_MERGE_MAX_PARTIALS;
     const long long os3[3] = {(long long)Hq * Sq * D, (long long)Sq * D, D}, ls3[3] = {(long long)Hq * Sq, Sq, 1};
-    auto merge = [&](const float* o0, const float* l0, int first, int n_more, void* dst, int dst_fmt, float* dst_lse) -> int {
-        const void* o[top];
-        const float* l[top];
-        int fmt[top];
-        long long ostr[3 * top], lstr[3 * top];
-        int n = 0;
-        if (o0) { o[n] = o0; l[n] = l0; n++; }
-        for (int i = 0; i < n_more; i++, n++) { o[n] = po + (size_t)(first + i) * rows * D; l[n] = plse + (size_t)(first + i) * rows; }
-        for (int i = 0; i < n; i++) {
-            fmt[i] = QATTN_FMT_FP32;
-            for (int j = 0; j < 3; j++) { ostr[3 * i + j] = os3[j]; lstr[3 * i + j] = ls3[j]; }
-        }
-        return qattn_attention_state_merge(n, o, fmt, ostr, l, lstr, dst, dst_fmt, os3, dst_lse, ls3, B, Hq, Sq, D, stream);
-    };
-    if (ns <= top) {
-        rc = merge(nullptr, nullptr, 0, ns, out, in_fmt, lse);
-    } else {
-        rc = merge(nullptr, nullptr, 0, top, acc, QATTN_FMT_FP32, acc_lse);
-        int done = top;
-        while (rc == QATTN_OK && ns - done > top - 1) {
-            rc = merge(acc, acc_lse, done, top - 1, acc, QATTN_FMT_FP32, acc_lse);
-            done += top - 1;
-        }
-        if (rc == QATTN_OK) rc = merge(acc, acc_lse, done, ns - done, out, in_fmt, lse);
-    }
+    rc = skv_merge_chain(po, plse, ns, rows, os3, ls3, B, Hq, Sq, D, out, in_fmt, lse, acc, acc_lse, stream);
     if (rc != QATTN_OK) return rc;
     if (row_path) return skv_launch_path(plse, ppath, row_path, rows, ns, st);
     return QATTN_OK;

@@ -4,7 +4,28 @@
 // entry existed, so that its device code stays what it was; 1, the pools through the block table `pg` (include/qattn_paged.h).  A body
 // shared as text, not as an inlined function: wrapped in a function the compiler's inlining and register allocation came out differently
 // for the contiguous kernels (profiles/paged/code_objects_vs_parent.log).
-// In scope: template parameters D, FMT, BYTE; arguments a (SkvAttn), two, sel and -- paged -- pg (SkvPages).
+// QATTN_SKV_VARQ (with QATTN_SKV_PAGED; include/qattn_paged_varlen.h) selects where a workgroup's QUERY rows live: 0, the dense
+// [B, Hq, Sq, D] tensors, every sequence with a.Sq queries; 1, packed tensors [total_q, Hq, D] cut by cu_seqlens_q (`vq`, SkvVarq): the
+// workgroup finds its (sequence, tile) by the binary search of qattn_varlen_tile.h on the packed-row starts G cu[i], and the sequence's
+// own Sq_i stands wherever the dense kernels read a.Sq.  The names that differ are macros (SKV_SQ, SKV_ROWS, SKV_QROW, SKV_QROW0, SKV_OROW,
+// SKV_LROW), so that with the switch off the text the compiler sees is token for token what it was
+// (profiles/paged_varlen/code_objects_vs_parent.log).
+// In scope: template parameters D, FMT, BYTE; arguments a (SkvAttn), two, sel, -- paged -- pg (SkvPages) and -- packed queries -- vq.
+#if QATTN_SKV_VARQ
+#define SKV_SQ Sq_i
+#define SKV_ROWS rows_i
+#define SKV_QROW qrow     // this lane's row of q8, in rows of D bytes
+#define SKV_QROW0 qrow0   // ... and the first row of the kv head's group: what a padding lane reads
+#define SKV_OROW orow     // row of the token-major [total_q, Hq] space: out, partial_o
+#define SKV_LROW lrow     // row of the head-major [Hq, total_q] space: lse, row_path, partial_lse, partial_path
+#else
+#define SKV_SQ a.Sq
+#define SKV_ROWS a.rows
+#define SKV_QROW grow
+#define SKV_QROW0 ((long)kvh * a.rows)
+#define SKV_OROW grow
+#define SKV_LROW grow
+#endif
     constexpr int CH = 64 * D, MB = D / 32, KS = D / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     FpvSweep<D, FMT, BYTE> sw(smem);
@@ -13,40 +34,69 @@
     // block -> (kv head b Hkv + hkv, tile, split): the splits of a tile are neighbours, the tiles of a kv head follow each other.
     // (Handing each XCD a contiguous range of kv heads, as the other launchers do, was measured and moved no time: not kept.)
     const int bid = blockIdx.x, per_head = a.ntile * a.ns;
+#if QATTN_SKV_VARQ
+    // a.ntile = B + ceil(G total_q / 128) tile slots per kv head; slot jt belongs to the largest sequence i with i + floor(G start_i / 128)
+    // <= jt (strictly increasing in i: consecutive values differ by at least ceil(G Sq_i / 128)) as its tile jt - that -- or to no tile.
+    // Every extent is clamped (include/qattn_varlen.h), so no table content moves a row out of [0, total_q).
+    const int hkv = bid / per_head, rest = bid % per_head;
+    const int s = rest % a.ns, jt = rest / a.ns;
+    int seq = 0, seq_hi = vq.B - 1;
+    while (seq < seq_hi) {   // (workgroup-uniform)
+        const int mid = (seq + seq_hi + 1) >> 1;
+        const int st = clampi(__builtin_amdgcn_readfirstlane(vq.cu[mid]), 0, vq.total_q);
+        if (mid + (a.G * st) / kFpvTile <= jt) seq = mid;
+        else seq_hi = mid - 1;
+    }
+    const int q_start = clampi(__builtin_amdgcn_readfirstlane(vq.cu[seq]), 0, vq.total_q);
+    const int Sq_i = clampi(__builtin_amdgcn_readfirstlane(vq.cu[seq + 1]), q_start, vq.total_q) - q_start;
+    const int rows_i = a.G * Sq_i;
+    const int tile = jt - (seq + (a.G * q_start) / kFpvTile);
+    if (tile < 0 || tile > ((rows_i - 1) >> 7)) return;   // before any other memory is touched (rows_i = 0: -1 >> 7 = -1)
+    const int kvh = seq * a.Hkv + hkv;                    // (sequence, kv head): scales, seqused_k and the table's row as in the dense kernels
+#else
     const int kvh = bid / per_head, rest = bid % per_head;
     const int s = rest % a.ns, tile = rest / a.ns;
+#endif
     int L = a.Skv;
     if (a.used) L = clampi(__builtin_amdgcn_readfirstlane(a.used[kvh / a.Hkv]), 0, a.Skv);
     // the split plan (workgroup-uniform, as everything down to the row numbers)
     const int nkb = (L + 127) >> 7, per = (nkb + a.ns - 1) / a.ns;
     const int k_begin = 128 * s * per, k_end = min(128 * (s + 1) * per, L);
-    const int r_first = tile * kFpvTile, r_last = min(r_first + kFpvTile, a.rows) - 1;
+    const int r_first = tile * kFpvTile, r_last = min(r_first + kFpvTile, SKV_ROWS) - 1;
     // positions of the tile's valid rows: [smin, smax] (a tile that crosses a head boundary holds a last and a first position)
-    const int g_first = r_first / a.Sq, g_last = r_last / a.Sq;
-    const int smin = g_first != g_last ? 0 : r_first - g_first * a.Sq, smax = g_first != g_last ? a.Sq - 1 : r_last - g_first * a.Sq;
-    const int delta = L - a.Sq;   // causal: position p attends the keys j <= p + delta
+    const int g_first = r_first / SKV_SQ, g_last = r_last / SKV_SQ;
+    const int smin = g_first != g_last ? 0 : r_first - g_first * SKV_SQ, smax = g_first != g_last ? SKV_SQ - 1 : r_last - g_first * SKV_SQ;
+    const int delta = L - SKV_SQ;   // causal: position p attends the keys j <= p + delta
     const int khi = a.causal ? min(k_end - 1, smax + delta) : k_end - 1;
     const int keys = max(khi - k_begin + 1, 0);   // the keys this workgroup sweeps
     if (sel == kFpvSelMany && keys < a.two_term_keys) return;
     if (sel == kFpvSelFew && keys >= a.two_term_keys) return;
 
     const int r = r_first + wave * kQPerWave + ql;   // packed row
-    const bool rvalid = r < a.rows;
-    const int g = min(r / a.Sq, a.G - 1);            // (padding rows: the last head's scale)
+    const bool rvalid = r < SKV_ROWS;
+    const int g = min(r / SKV_SQ, a.G - 1);          // (padding rows: the last head's scale)
+#if QATTN_SKV_VARQ
+    // q8 is the packed pre-pass's: sequence i's [Hq, Sq_i, D] slab at row Hq start_i, the kv head's packed rows consecutive in it; the
+    // outputs are packed by token.  (A padding row's token may lie outside the sequence: every use is under rvalid.)
+    const int tok = q_start + (r - g * Sq_i), head = hkv * a.G + g;
+    const long qrow0 = (long)vq.Hq * q_start + (long)hkv * rows_i, qrow = qrow0 + r;
+    const long orow = (long)tok * vq.Hq + head, lrow = (long)head * vq.total_q + tok;
+#else
     const long grow = (long)kvh * a.rows + r;        // row of the dense [B Hq Sq] index space
+#endif
     if (keys == 0) {   // no key for any row of the tile in this split (L = 0, a split past the last block, a split above the causal edge)
         if (a.ns == 1) {
-            fpv_store_empty<D>(a.out, a.out_fmt, (rvalid ? grow : 0L) * (2L * D), a.lse, grow, a.path, grow, hh, rvalid);
+            fpv_store_empty<D>(a.out, a.out_fmt, (rvalid ? SKV_OROW : 0L) * (2L * D), a.lse, SKV_LROW, a.path, SKV_LROW, hh, rvalid);
         } else {
-            const long prow = (long)s * a.part_rows + (rvalid ? grow : 0L);
+            const long prow = (long)s * a.part_rows + (rvalid ? SKV_OROW : 0L), plrow = (long)s * a.part_rows + (rvalid ? SKV_LROW : 0L);
             v16f z[MB];
 #pragma unroll
             for (int m = 0; m < MB; m++)
 #pragma unroll
                 for (int e = 0; e < 16; e++) z[m][e] = 0.0f;
             store_o_rows_f32<MB>(a.po + prow * D, z, 0.0f, hh, rvalid);
-            if (hh == 0 && rvalid) a.plse[prow] = -INFINITY;
-            if (a.ppath && hh == 0 && rvalid) a.ppath[prow] = (unsigned char)QATTN_PATH_ONE_TERM;
+            if (hh == 0 && rvalid) a.plse[plrow] = -INFINITY;
+            if (a.ppath && hh == 0 && rvalid) a.ppath[plrow] = (unsigned char)QATTN_PATH_ONE_TERM;
         }
         return;
     }
@@ -75,12 +125,12 @@
     FpvRing<D> ring(smem, wave, lane, a.k8 + img, a.v8 + img);
     ring.dma_chunk(c_first);
 #endif
-    sw.park_q(a.q8 + (rvalid ? grow : (long)kvh * a.rows) * D + hh * 32, rvalid);
+    sw.park_q(a.q8 + (rvalid ? SKV_QROW : SKV_QROW0) * D + hh * 32, rvalid);
     constexpr float kNoKeyYet = -1.0e20f;   // (attn_vfp8_window_kernel's header comment)
     sw.init_state(a.sm_log2e * a.sq[(long)kvh * a.G + g] * a.sk[kvh], kNoKeyYet);
     const int one = fpv_ones_word(lane);
     // the last key this lane's row attends, and the first chunk end that crosses the causal edge of some valid row
-    const int hi_l = (a.causal && rvalid) ? min(L - 1, r - g * a.Sq + delta) : L - 1;
+    const int hi_l = (a.causal && rvalid) ? min(L - 1, r - g * SKV_SQ + delta) : L - 1;
     const int edge = a.causal ? smin + delta : INT_MAX;
 
     for (int t = 0; t < n_wg; t++) {   // step t sweeps chunk c_first + t
@@ -127,12 +177,18 @@
     const float lse_row = has_key ? 0.6931471805599453f * (sw.m_run * sw.c - kPShift) + __logf(l_tot) : -INFINITY;
     const unsigned char code = (unsigned char)((!BYTE && two) ? QATTN_PATH_TWO_TERM : QATTN_PATH_ONE_TERM);
     if (a.ns == 1) {
-        store_o_rows<MB>(a.out, a.out_fmt, sw.o, inv, (rvalid ? grow : 0L) * (2L * D), hh, rvalid);
-        if (!BYTE && a.lse && hh == 0 && rvalid) a.lse[grow] = lse_row;
-        if (a.path && hh == 0 && rvalid) a.path[grow] = code;
+        store_o_rows<MB>(a.out, a.out_fmt, sw.o, inv, (rvalid ? SKV_OROW : 0L) * (2L * D), hh, rvalid);
+        if (!BYTE && a.lse && hh == 0 && rvalid) a.lse[SKV_LROW] = lse_row;
+        if (a.path && hh == 0 && rvalid) a.path[SKV_LROW] = code;
     } else {
-        const long prow = (long)s * a.part_rows + (rvalid ? grow : 0L);
+        const long prow = (long)s * a.part_rows + (rvalid ? SKV_OROW : 0L), plrow = (long)s * a.part_rows + (rvalid ? SKV_LROW : 0L);
         store_o_rows_f32<MB>(a.po + prow * D, sw.o, inv, hh, rvalid);
-        if (!BYTE && hh == 0 && rvalid) a.plse[prow] = lse_row;
-        if (a.ppath && hh == 0 && rvalid) a.ppath[prow] = code;
+        if (!BYTE && hh == 0 && rvalid) a.plse[plrow] = lse_row;
+        if (a.ppath && hh == 0 && rvalid) a.ppath[plrow] = code;
     }
+#undef SKV_SQ
+#undef SKV_ROWS
+#undef SKV_QROW
+#undef SKV_QROW0
+#undef SKV_OROW
+#undef SKV_LROW

@@ -79,7 +79,11 @@ static_assert(skv_resident<64>() == 3 && skv_resident<128>() == 2 && skv_residen
 
 extern "C" int qattn_splitkv_auto_splits(int B, int Hq, int Hkv, int Sq, int Skv, int D, int num_cus) {
     if (!skv_dims_ok(B, Hq, Hkv, Sq, Skv) || !skv_d_ok(D) || Hq % Hkv != 0 || num_cus <= 0) return 1;
-    const long long tiles = (long long)B * Hkv * (((long long)(Hq / Hkv) * Sq + kFpvTile - 1) / kFpvTile);
+    return skv_auto_splits_of_tiles((long long)B * Hkv * (((long long)(Hq / Hkv) * Sq + kFpvTile - 1) / kFpvTile), Skv, D, num_cus);
+}
+
+// (tiles >= 1, Skv >= 1, D supported, num_cus >= 1: checked by the callers)
+int qattn::skv_auto_splits_of_tiles(long long tiles, int Skv, int D, int num_cus) {
     const long long slots = (long long)num_cus * (D == 64 ? skv_resident<64>() : D == 128 ? skv_resident<128>() : skv_resident<256>());
     long long ns = slots / tiles;
     const int nkb = ceil_div(Skv, 128);

@@ -337,3 +337,40 @@ extern "C" int qattn_fp8_quant_attention_varlen_forward_smooth(const void* q, co
     return varlen_forward_impl(q, k, v, strides, in_fmt, out, lse, cu_seqlens_q, cu_seqlens_k, seqused_k, B, Hq, Hkv, total_q, total_k, D, fp8_fmt,
                                numerics, is_causal, sm_scale, q8, k8, scale_q, scale_k, workspace, workspace_bytes, stream, k_mean, nullptr);
 }
+
+// (at the end of the unit: the kernels above keep the order in which the entries first ask for them, and with it the unit's device code)
+// q's slice (z = 0) of the two pre-pass launches: the skip_k grids of launch_varlen_d
+template <int D, int IN_FMT, int OUT_FMT>
+static void launch_varlen_quant_q_fmt(const VarlenQuant& qa, int numerics, hipStream_t st) {
+    hipLaunchKernelGGL((varlen_amax_kernel<D, IN_FMT>), dim3((unsigned)(qa.B + ceil_div(qa.total[0], kVarlenAmaxRows)), qa.H[0], 1), dim3(256), 0, st, qa);
+    hipLaunchKernelGGL((varlen_quant_kernel<D, IN_FMT, OUT_FMT>), dim3((unsigned)(qa.B + ceil_div(qa.total[0], kVarlenQuantRows)), qa.H[0], 1), dim3(256),
+                       0, st, qa, numerics);
+}
+template <int D>
+static void launch_varlen_quant_q(const VarlenQuant& qa, int in_fmt, int fp8_fmt, int numerics, hipStream_t st) {
+    if (in_fmt == QATTN_FMT_BF16) {
+        if (fp8_fmt == QATTN_FMT_E4M3) launch_varlen_quant_q_fmt<D, QATTN_FMT_BF16, QATTN_FMT_E4M3>(qa, numerics, st);
+        else launch_varlen_quant_q_fmt<D, QATTN_FMT_BF16, QATTN_FMT_E5M2>(qa, numerics, st);
+    } else {
+        if (fp8_fmt == QATTN_FMT_E4M3) launch_varlen_quant_q_fmt<D, QATTN_FMT_FP16, QATTN_FMT_E4M3>(qa, numerics, st);
+        else launch_varlen_quant_q_fmt<D, QATTN_FMT_FP16, QATTN_FMT_E5M2>(qa, numerics, st);
+    }
+}
+
+// The packed pre-pass on q ALONE (the skip_k grids): zeroing node, abs-max, quantise -- for a caller whose keys are prepared already
+// (qattn_paged_varlen_splitkv_fp8.hip).  Arguments are the caller's to check: D supported, formats valid, total >= 1, B >= 1.
+int qattn::varlen_quant_q(const void* q16, long token_stride, long head_stride, int in_fmt, const int* cu_seqlens_q, int B, int Hq, int total_q, int D,
+                   int fp8_fmt, int numerics, unsigned* amax, void* q8, float* scale_q, hipStream_t st) {
+    VarlenQuant qa;
+    __builtin_memset(&qa, 0, sizeof(qa));
+    qa.x[0] = (const unsigned char*)q16;
+    qa.ts[0] = token_stride; qa.hs[0] = head_stride;
+    qa.cu[0] = cu_seqlens_q;
+    qa.total[0] = total_q; qa.H[0] = Hq; qa.B = B;
+    qa.amax[0] = amax; qa.x8[0] = (unsigned char*)q8; qa.scale[0] = scale_q;
+    if (zero_words(amax, (long)B * Hq, st) != hipSuccess) return QATTN_ERR_LAUNCH;
+    if (D == 64) launch_varlen_quant_q<64>(qa, in_fmt, fp8_fmt, numerics, st);
+    else if (D == 128) launch_varlen_quant_q<128>(qa, in_fmt, fp8_fmt, numerics, st);
+    else launch_varlen_quant_q<256>(qa, in_fmt, fp8_fmt, numerics, st);
+    return hipGetLastError() == hipSuccess ? QATTN_OK : QATTN_ERR_LAUNCH;
+}

@@ -631,3 +631,59 @@ def fp8_paged_kv_cache_append_(
 @_register_fake("quantumattention_amd::fp8_paged_kv_cache_append_")
 def _(k_pool, v_pool, scale_k, scale_v, block_table, seqlens, k_new, v_new, new_lens, num_pages, page_size, fp8_format="e4m3", advance=True):
     return None
+
+
+@_custom_op("quantumattention_amd::fp8_paged_varlen_splitkv_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_paged_varlen_splitkv_attention_forward(
+    query: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    max_seqlen_q: int,
+    seqlen_k: int,
+    num_pages: int,
+    page_size: int,
+    num_splits: int,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    is_causal: bool = False,
+    precision: str = "accurate",
+    return_lse: bool = False,
+    return_partials: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Split-KV FP8 attention of PACKED queries over a paged cache (include/qattn_paged_varlen.h): query [total_q, Hq, D] cut by
+    cu_seqlens_q int32 [B + 1], a different count per sequence slot; the pools, the table, seqused_k and seqlen_k as
+    fp8_paged_splitkv_attention_forward; num_splits >= 1 (resolved by the caller).  Returns (out [total_q, Hq, D], lse [Hq, total_q],
+    partial_o [ns, total_q, Hq, D], partial_lse [ns, Hq, total_q], partial_path); what was not asked for is an empty tensor.  Reference
+    implementation: paged._attend_varlen_eager.  Arguments are validated by paged.fp8_attn_paged_varlen_func."""
+    res = _native.fp8_attention_paged_varlen(
+        query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, cu_seqlens_q, max_seqlen_q=max_seqlen_q, Skv=seqlen_k,
+        num_pages=num_pages, page_size=page_size, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics, is_causal=is_causal,
+        sm_scale=0.0 if scale is None else float(scale), precision=precision, num_splits=num_splits, return_lse=return_lse,
+        return_partials=return_partials)
+    res = res if isinstance(res, tuple) else (res,)
+    none_f = lambda: torch.empty((0,), dtype=torch.float32, device=query.device)
+    out = res[0]
+    lse = res[1] if return_lse else none_f()
+    parts = res[-3:] if return_partials else (none_f(), none_f(), torch.empty((0,), dtype=torch.uint8, device=query.device))
+    return (out, lse) + tuple(parts)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_varlen_splitkv_attention_forward")
+def _(query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, cu_seqlens_q, max_seqlen_q, seqlen_k, num_pages, page_size, num_splits,
+      fp8_format="e4m3", numerics="compiled", is_causal=False, precision="accurate", return_lse=False, return_partials=False, *, scale=None):
+    total_q, Hq, D = query.shape
+    out = query.new_empty((total_q, Hq, D))
+    lse = query.new_empty((Hq, total_q) if return_lse else (0,), dtype=torch.float32)
+    n = num_splits if num_splits > 1 else 0
+    if return_partials:
+        return (out, lse, query.new_empty((n, total_q, Hq, D), dtype=torch.float32), query.new_empty((n, Hq, total_q), dtype=torch.float32),
+                query.new_empty((n, Hq, total_q), dtype=torch.uint8))
+    return (out, lse, query.new_empty((0,), dtype=torch.float32), query.new_empty((0,), dtype=torch.float32),
+            query.new_empty((0,), dtype=torch.uint8))

@@ -20,7 +20,8 @@ hold anything.  A page shared by several sequences (a common prefix) needs equal
 sequences that append into the same page in one call have two writers: undefined.
 
 Package attributes, not names of `__all__` (that list mirrors the reference).  Not offered: page allocation, copy-on-write, re-scaling,
-a per-call table whose batch differs from the cache's slots, sliding windows."""
+a per-call table whose batch differs from the cache's slots, sliding windows.  Queries of a different count per sequence slot (packed
+[total_q, Hq, D] under cu_seqlens_q): `fp8_attn_paged_varlen_func`, paged_varlen.py."""
 import math
 from typing import Optional, Tuple
 

@@ -1,0 +1,185 @@
+"""PACKED variable-length queries over the paged FP8 K/V cache: `fp8_attn_paged_varlen_func` (include/qattn_paged_varlen.h, DESIGN.md
+section 4.20) -- one call for a serving step that mixes chunked prefill, decode and idle slots.
+
+`fp8_attn_paged_func` takes q [B, Hq, Sq, D]: every sequence slot has Sq queries.  A continuous-batching step does not: a few slots are
+in chunked prefill with hundreds of queries, many decode one token (or a few speculative ones), some are idle.  Here q is
+[total_q, Hq, D], slot b owns the tokens cu_seqlens_q[b] .. cu_seqlens_q[b + 1] -- the call shape of flash-attn's / vLLM's
+`flash_attn_varlen_func(q, ..., cu_seqlens_q, max_seqlen_q, seqused_k, block_table, causal=True)`.
+
+    cu = torch.tensor([0, 512, 513, 513, 514], dtype=torch.int32, device="cuda")     # a prefill chunk, a decode, an idle slot, a decode
+    out = fp8_attn_paged_varlen_func(q, cache, cu, 512, causal=True, max_seqlen_k=longest_live_sequence)   # [total_q, Hq, D]
+
+The rule: for every slot with queries, the rows of every output are, bit for bit, those of `fp8_attn_paged_func` on that slot alone.
+
+A package attribute, not a name of `__all__`.  Not offered: a packed [total, Hkv, D] append (the padded
+`paged_kv_cache_append_fp8(..., new_lens=)` serves a mixed step), sliding windows, a per-call table whose batch differs from the cache's
+slots, the contiguous `KVCacheFP8`."""
+import math
+from typing import Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from . import _native, nn
+from .kvcache import _is_int
+from .paged import PagedKVCacheFP8, _cache_reason, _lens_reason, gather_paged_eager
+from .splitkv import _CPU_NUM_CUS, MAX_SPLITS, PreparedKV, _splitkv_eager
+from .utils import checks
+
+
+def _q_rows_addressable(q: Tensor) -> bool:
+    """head_dim innermost and dense, token and head strides of a dimension longer than 1 non-negative multiples of 8 elements, the first
+    element 16-byte aligned in its storage: the rows the pre-pass loads 16 bytes at a time"""
+    # (while Dynamo traces, the storage offset is not to be had: the op's binding checks the real pointer)
+    aligned = torch.compiler.is_dynamo_compiling() or q.storage_offset() % 8 == 0
+    return ((q.shape[2] == 1 or q.stride(2) == 1) and aligned
+            and all(q.shape[i] == 1 or (q.stride(i) >= 0 and q.stride(i) % 8 == 0) for i in (0, 1)))
+
+
+def paged_varlen_attn_input_reason(q, cache, cu_seqlens_q, max_seqlen_q, seqused_k=None, scale=None, num_splits=0,
+                                   max_seqlen_k=None) -> Optional[str]:
+    """The first rule the arguments of `fp8_attn_paged_varlen_func` break, or None.  Shapes, dtypes, devices and strides only: the CONTENTS
+    of cu_seqlens_q, seqused_k and the block table are read on the device."""
+    if not isinstance(q, Tensor) or q.dim() != 3:
+        return "NYI: query must be a 3-D tensor [total_q, Hq, head_dim]"
+    if q.requires_grad:
+        return "NYI: query must be a leaf tensor (no backward)"
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        return f"Expected query to have dtype torch.float16 or torch.bfloat16, but got query.dtype: {q.dtype} instead."
+    reason = _cache_reason(cache)
+    if reason:
+        return reason
+    B = cache.batch_size
+    _, Hkv, _, D = cache.shape
+    if cache.dtype != q.dtype:
+        return f"Expected query to have the cache's dtype, but got {q.dtype} and {cache.dtype} instead."
+    if q.shape[-1] != D:
+        return f"Expect query, key and value to have the same head dimension but got {q.shape[-1]} and {D}."
+    if q.shape[1] == 0:
+        return "Expected a non-empty head count"
+    if q.shape[1] % Hkv != 0:
+        return f"Expect the number of query heads to be a multiple of the key/value heads but got Hq={q.shape[1]} and Hkv={Hkv}."
+    if (q.shape[1] // Hkv) * q.shape[0] > 2 ** 31 - 1:
+        return f"(Hq / Hkv) * total_q must stay below 2^31 (the packed row index), got {(q.shape[1] // Hkv) * q.shape[0]}"
+    if q.device != cache.device:
+        return f"Expected query and the cache to be on the same device, but got {q.device} and {cache.device} instead."
+    if q.shape[0] > 0 and not _q_rows_addressable(q):
+        return (f"Expected query to have head_dim innermost and 16-byte-aligned rows (strides that are multiples of 8 elements), but got "
+                f"strides {tuple(q.stride())} at storage offset {q.storage_offset()}; pass query.contiguous()")
+    if not isinstance(cu_seqlens_q, Tensor) or cu_seqlens_q.dtype != torch.int32:
+        return f"Expected cu_seqlens_q to be a torch.int32 tensor, but got {getattr(cu_seqlens_q, 'dtype', type(cu_seqlens_q))}"
+    if tuple(cu_seqlens_q.shape) != (B + 1,):
+        return f"Expected cu_seqlens_q to have shape [{B + 1}] (the cache's slots + 1), but got {list(cu_seqlens_q.shape)}."
+    if cu_seqlens_q.device != q.device:
+        return f"Expected cu_seqlens_q to be on {q.device}, but got {cu_seqlens_q.device} instead."
+    if not cu_seqlens_q.is_contiguous():
+        return "Expected cu_seqlens_q to be contiguous"
+    if not (_is_int(max_seqlen_q) and max_seqlen_q >= 1):
+        return f"max_seqlen_q must be an integer >= 1 (the most queries of a sequence), got {max_seqlen_q!r}"
+    reason = _lens_reason("seqused_k" if seqused_k is not None else "cache.seqlens", cache.seqlens if seqused_k is None else seqused_k, B, q.device)
+    if reason:
+        return reason
+    if max_seqlen_k is not None and not (_is_int(max_seqlen_k) and 1 <= max_seqlen_k <= cache.capacity):
+        return f"max_seqlen_k must be None or an integer in 1 .. max_pages_per_seq * page_size = {cache.capacity}, got {max_seqlen_k!r}"
+    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or not 0 <= num_splits <= MAX_SPLITS:
+        return f"num_splits must be 0 (choose) or an integer in 1 .. {MAX_SPLITS}, got {num_splits!r}"
+    if scale is not None and not (isinstance(scale, (int, float)) and not isinstance(scale, bool) and math.isfinite(scale) and scale > 0):
+        return f"scale must be a finite number > 0 (or None for 1/sqrt(head_dim)), got {scale!r}"
+    return None
+
+
+@torch.compiler.assume_constant_result
+def _resolve_varlen_splits(num_splits: int, B: int, Hq: int, Hkv: int, total_q: int, max_seqlen_q: int, Skv: int, D: int, device) -> int:
+    """num_splits = 0 -> qattn_paged_varlen_auto_splits on the device's CU count: a pure function of host ints (it reads neither
+    cu_seqlens_q nor seqused_k), so a trace-time constant."""
+    if num_splits:
+        return num_splits
+    cus = torch.cuda.get_device_properties(device).multi_processor_count if torch.device(device).type == "cuda" else _CPU_NUM_CUS
+    return _native.paged_varlen_auto_splits(B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, cus)
+
+
+def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, ns, precision):
+    """CPU tensors and config.attention.force_eager_fallback: per sequence slot, splitkv._splitkv_eager on the slot's queries and on its
+    keys gathered through the table, scattered into the packed outputs.  Rows of tokens that belong to no sequence: zeros.  (This path
+    reads cu_seqlens_q, seqused_k and the table on the host.)"""
+    total_q, Hq, D = q.shape
+    B = cache.batch_size
+    n = ns if ns > 1 else 0
+    out = torch.zeros((total_q, Hq, D), dtype=q.dtype, device=q.device)
+    lse = torch.zeros((Hq, total_q), dtype=torch.float32, device=q.device)
+    po = torch.zeros((n, total_q, Hq, D), dtype=torch.float32, device=q.device) if n else torch.empty((0,), dtype=torch.float32, device=q.device)
+    plse = torch.zeros((n, Hq, total_q), dtype=torch.float32, device=q.device) if n else torch.empty((0,), dtype=torch.float32, device=q.device)
+    ppath = torch.zeros((n, Hq, total_q), dtype=torch.uint8, device=q.device) if n else torch.empty((0,), dtype=torch.uint8, device=q.device)
+    if total_q == 0:
+        return out, lse, po, plse, ppath
+    kv = gather_paged_eager(cache, Skv)
+    cu = cu_seqlens_q.tolist()
+    for b in range(B):
+        start = min(max(int(cu[b]), 0), total_q)
+        end = min(max(int(cu[b + 1]), start), total_q)
+        if end == start:
+            continue
+        one = PreparedKV(kv.k[b:b + 1], kv.v[b:b + 1], kv.scale_k[b:b + 1], kv.scale_v[b:b + 1], (1,) + tuple(kv.shape[1:]), kv.fp8_format,
+                         kv.dtype, kv.numerics, "rowmajor")
+        o, l, p_o, p_l, p_p = _splitkv_eager(q[start:end].transpose(0, 1)[None], one, causal, scale, seqused_k[b:b + 1], ns, precision)
+        out[start:end] = o[0].transpose(0, 1)
+        lse[:, start:end] = l[0]
+        if n:
+            po[:, start:end] = p_o[:, 0].transpose(1, 2)
+            plse[:, :, start:end] = p_l[:, 0]
+            ppath[:, :, start:end] = p_p[:, 0]
+    return out, lse, po, plse, ppath
+
+
+def fp8_attn_paged_varlen_func(q, cache: PagedKVCacheFP8, cu_seqlens_q: Tensor, max_seqlen_q: int, *, causal: bool = False,
+                               scale: Optional[float] = None, seqused_k: Optional[Tensor] = None, max_seqlen_k: Optional[int] = None,
+                               num_splits: int = 0, precision: str = "accurate", return_lse: bool = False, return_partials: bool = False):
+    """`fp8_attn_paged_func` for PACKED queries, a different count per sequence slot.
+
+    q [total_q, Hq, D] in cache.dtype; a view with D innermost and 16-byte-aligned rows (a slice of a packed QKV projection) goes in as it
+    is.  cu_seqlens_q: int32 [cache.batch_size + 1] on the device; slot b owns the tokens clamp(cu[b], 0, total_q) .. clamp(cu[b + 1],
+    that, total_q), Sq_b of them (0: an idle slot), and attends the first L_b = clamp(seqused_k[b], 0, Skv) keys of slot b.  causal:
+    bottom-right per sequence -- position p attends the keys j <= p + L_b - Sq_b.  max_seqlen_q: a host int >= 1, the most queries of a
+    slot: read by the num_splits = 0 rule only.  seqused_k (default cache.seqlens), max_seqlen_k, scale, num_splits, precision: as
+    `fp8_attn_paged_func`.
+
+    Returns out [total_q, Hq, D]; with return_lse, lse fp32 [Hq, total_q] (flash-attn's packed layout); with return_partials, partial_o fp32
+    [ns, total_q, Hq, D], partial_lse [ns, Hq, total_q] and partial_path uint8 [ns, Hq, total_q] (three empty tensors with one split).
+    For every slot with Sq_b > 0 these rows are, bit for bit, `fp8_attn_paged_func` on that slot alone (q[cu[b]:cu[b+1]] as
+    [1, Hq, Sq_b, D], a one-slot cache on the same pools) with the same max_seqlen_k and num_splits > 0.  Rows of tokens that belong to
+    no slot (cu[B] < total_q: a padded token bucket) have unspecified contents.  total_q = 0 returns empty tensors.
+    Everything is read on the device: no host synchronisation, graph-capture safe, and a captured call follows the later contents of
+    cu_seqlens_q, seqused_k and the table.  CPU tensors and config.attention.force_eager_fallback run the eager definition
+    (`_attend_varlen_eager`); on the device there is no fallback.  Unsupported input raises ValueError(reason)."""
+    if precision not in ("accurate", "fast"):
+        raise ValueError(f"Unsupported precision: {precision!r} (expected 'accurate' or 'fast'; 'auto' is not offered by the split-KV entries)")
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = paged_varlen_attn_input_reason(q, cache, cu_seqlens_q, max_seqlen_q, seqused_k, scale, num_splits, max_seqlen_k)
+        if reason:
+            raise ValueError(reason)
+    total_q, Hq, D = q.shape
+    B, Hkv = cache.batch_size, cache.shape[1]
+    Skv = cache.capacity if max_seqlen_k is None else int(max_seqlen_k)
+    used = cache.seqlens if seqused_k is None else seqused_k
+    ns = _resolve_varlen_splits(num_splits, B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, q.device)
+    eager = (not q.is_cuda or checks.config_value("attention.force_eager_fallback")) and not torch.compiler.is_dynamo_compiling()
+    if eager:
+        if cache.layout != "rowmajor":
+            raise ValueError("the eager definition needs a cache made on a CPU device or under config.attention.force_eager_fallback")
+        out, lse, po, plse, ppath = _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, used, Skv, ns, precision)
+    else:
+        if cache.layout != "frag":
+            raise ValueError("this cache holds row-major bytes for the eager definition; make it on the device without "
+                             "config.attention.force_eager_fallback")
+        ok, why = nn._pre_check_can_use_hip_attention(device=q.device)
+        if not ok:
+            raise ValueError(why)
+        out, lse, po, plse, ppath = nn._ops().fp8_paged_varlen_splitkv_attention_forward(
+            q, cache.k, cache.v, cache.scale_k, cache.scale_v, cache.block_table, used, cu_seqlens_q, int(max_seqlen_q), Skv, cache.num_pages,
+            cache.page_size, ns, cache.fp8_format, cache.numerics, bool(causal), precision, bool(return_lse), bool(return_partials), scale=scale)
+    res: Tuple = (out,)
+    if return_lse:
+        res += (lse,)
+    if return_partials:
+        res += (po, plse, ppath)
+    return res if len(res) > 1 else out
