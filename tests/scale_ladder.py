@@ -401,3 +401,118 @@ def bound_of(ref):
 def moved(ref, mut):
     """per row: max over the channels of |mut - ref| / bound"""
     return (np.abs(mut - ref) / bound_of(ref)).max(-1)
+
+
+# ---- the FP8-PV family: block-sparse / packed / window FP8-PV, split-KV over prepared K / V, the fixed-scale and paged caches ---------------
+# (tests/test_cpu_scale_ladder_fp8pv.py: the teeth; tests/test_gpu_scale_ladder_fp8pv.py: the kernels.)  These entries keep ONE fp8 V scale
+# per (batch entry, kv head) and apply it once in the epilogue; the split-KV kernels pack the rows of the G query heads of a kv head into
+# 128-row tiles (packed row r = g Sq + p), so that `g`, and with it scale_q, differs per lane.
+# (D, Sq, Skv, causal, dtype, fp8): the smallest shapes that hold a tile with rows of two heads in one wave (Sq 1), a tile that crosses a
+# head boundary (Sq 70: 140 packed rows; Sq 130: 260 rows, a ragged third tile), one-term FAST workgroups (>= 1024 keys in a split: 1100 /
+# 1, 2304 / 1) and two-term ones.  Batch entry b uses the first used_lengths(Skv)[b] keys: the second entry ends inside a key block.
+FP8PV_CASES = [
+    (128, 1, 1100, True, torch.bfloat16, "e4m3"),
+    (64, 5, 2304, True, torch.float16, "e4m3"),
+    (256, 130, 1100, True, torch.bfloat16, "e4m3"),
+    (128, 130, 2304, False, torch.float16, "e5m2"),
+    (128, 70, 1100, True, torch.bfloat16, "e4m3"),
+]
+SPLITS = (1, 3, 9)
+TILE = 128                                        # packed query rows per workgroup of the split-KV kernels (include/qattn_splitkv.h)
+PACKED_SQ = (130, 5)                              # queries per sequence of the packed-query cases: the ladder's two batch entries
+SPARSE_GAIN, SPARSE_SHARE = 4.0, 16               # group ladder: the even heads of a GQA group carry +-4 on D / 16 channels per row
+
+
+def used_lengths(Skv):
+    return [Skv, Skv - 64]
+
+
+@functools.lru_cache(maxsize=None)
+def head_ladder_plain_v(D, Sq, Skv):
+    """the head ladder's q and k (e and f) with the plain V over {-1, 0, 1}: no chunk gains -- the FP8-PV family keeps one scale_v per head"""
+    lad, plain = head_ladder(D, Sq, Skv), head_ladder(D, Sq, Skv, gains=False)
+    return Ladder(lad.q.copy(), lad.k.copy(), plain.v.copy(), e_k=lad.e_k, e_q=lad.e_q, g=plain.g, e_v=plain.e_v)
+
+
+@functools.lru_cache(maxsize=None)
+def group_ladder(D, Sq, Skv, gains=True):
+    """The in-group ladder: K dense +-1 codes x 2^e, e = E_HEAD[b, h_kv]; inside every GQA group the EVEN query heads carry sparse codes
+    (+-4 on D / 16 seeded channels per row, 0 elsewhere) and the ODD heads dense +-1 codes, all x 2^(-e).  Every row's scores keep a standard
+    deviation of 1 (16 D / 16 = D), every non-zero element of a head sits at the head's abs-max (bytes 0 or +- the largest code), and
+    scale_q inside a group differs by x4 with the LARGER scale on the group's first head: a row of an odd head that reads the scale of the
+    head its tile begins with gets scores 4 x too large and collapses.  V is the plain one.  gains = False: e = 0 (the sparse / dense codes stay)."""
+    rng = np.random.default_rng(7001 * D + 19 * Sq + Skv)
+    qc, kc = _codes(rng, (B, HQ, Sq, D)), _codes(rng, (B, HKV, Skv, D))
+    rank = rng.random((B, HQ, Sq, D)).argsort(-1).argsort(-1)
+    sparse = (np.arange(HQ) % (HQ // HKV) == 0)[None, :, None, None]
+    qc = np.where(sparse, qc * SPARSE_GAIN * (rank < D // SPARSE_SHARE), qc)
+    nch = (Skv + 63) // 64
+    vc = per_key(_codes(rng, (B, HKV, D, nch)), Skv).transpose(0, 1, 3, 2) * rng.integers(0, 2, (B, HKV, Skv, D))
+    e = E_HEAD if gains else np.zeros_like(E_HEAD)
+    eq = -e[:, kv_of()] + np.where(sparse[0, :, 0, 0], int(np.log2(SPARSE_GAIN)), 0)[None, :]        # log2 of scale_q / the plain scale
+    return Ladder(qc * np.exp2(-e[:, kv_of()])[..., None, None], kc * np.exp2(e)[..., None, None], vc, e_k=e, e_q=eq, g=np.zeros((B, HKV, nch), np.int64),
+                  e_v=np.zeros_like(E_VHEAD), sparse=sparse[0, :, 0, 0])
+
+
+def used_mask(Sq, Skv, used, causal, sq=None, top_left=False):
+    """bool [B, 1, Sq, Skv]: batch entry b has sq[b] <= Sq query rows (default Sq; the rows behind them attend nothing) and attends its first
+    used[b] keys, causal bottom-right: position p attends the keys j <= p + used[b] - sq[b] (the split-KV, cache, paged and window entries);
+    top_left: the keys j <= p (the packed entries' is_causal, include/qattn_varlen.h)"""
+    sq = [Sq] * len(used) if sq is None else sq
+    p, j = np.arange(Sq)[:, None], np.arange(Skv)[None, :]
+    m = [(p < n) & (j < L) & ((j <= p + (0 if top_left else L - n)) if causal else True) for L, n in zip(used, sq)]
+    return np.stack(m)[:, None]
+
+
+class UsedScores(Scores):
+    """Scores with one mask per batch entry (used_mask): the reference of the split-KV / cache / paged entries and of seqused_k"""
+
+    def __init__(self, qz, mask):
+        assert mask.ndim == 4 and mask.shape[0] == B
+        Scores.__init__(self, qz, mask)
+
+    def _scaled(self, b, rs, cs):
+        return (self.raw[b] * (rs[b][..., None] * (1.0 / math.sqrt(self.D))) * cs[b][:, None, :]).masked_fill(~self.mask[b], -math.inf)
+
+    def softmax(self, rs=None, cs=None, v=None, sm_scale=None):
+        assert sm_scale is None
+        qz = self.qz
+        rs = torch.from_numpy(np.array(qz.row_scale() if rs is None else rs))
+        cs = torch.from_numpy(np.array(qz.col_scale() if cs is None else cs))
+        vv = torch.from_numpy(np.ascontiguousarray(qz.v_fp8 if v is None else v, np.float64)).repeat_interleave(HQ // HKV, dim=1)
+        out, lse = [], []
+        for b in range(B):
+            s = self._scaled(b, rs, cs)
+            l = torch.logsumexp(s, dim=-1)
+            out.append(torch.exp(s - l.clamp_min(-1e300)[..., None]) @ vv[b])
+            lse.append(l)
+        return torch.stack(out).numpy(), torch.stack(lse).numpy()
+
+    def weights_summary(self):
+        """(largest weight, effective key count) per row [B, HQ, Sq]; rows without a key: (0, 0)"""
+        qz = self.qz
+        rs, cs = torch.from_numpy(np.array(qz.row_scale())), torch.from_numpy(np.array(qz.col_scale()))
+        top, eff = [], []
+        for b in range(B):
+            s = self._scaled(b, rs, cs)
+            p = torch.exp(s - torch.logsumexp(s, dim=-1).clamp_min(-1e300)[..., None])
+            top.append(p.amax(-1))
+            eff.append(torch.where(p.sum(-1) > 0, 1.0 / (p * p).sum(-1).clamp_min(1e-300), torch.zeros(())))
+        return torch.stack(top).numpy(), torch.stack(eff).numpy()
+
+
+def tile_mutants(qz, sq_per_sequence):
+    """{name: (rs, None)}: the two ways the per-lane `g` of the split-KV kernels invites.  Batch entry b has sq_per_sequence[b] query rows;
+    row p of head h = h_kv G + g is packed row r = g Sq_b + p of its kv head, in tile r // 128.
+    1. every row of a tile reads the scale_q of the head of the tile's FIRST row (g taken from the workgroup-uniform r_first);
+    2. g computed with max_seqlen_q in place of the sequence's own Sq (packed queries: sequences shorter than the longest)."""
+    sq = qz.sq.astype(np.float64)
+    Sq, G, mx = qz.q8.shape[2], HQ // HKV, max(sq_per_sequence)
+    first, by_max = qz.row_scale().copy(), qz.row_scale().copy()
+    for b, n in enumerate(sq_per_sequence):
+        for h in range(HQ):
+            hkv, g = h // G, h % G
+            r = g * n + np.arange(n)
+            first[b, h, :n] = sq[b, hkv * G + np.minimum((r // TILE) * TILE // n, G - 1)]
+            by_max[b, h, :n] = sq[b, hkv * G + np.minimum(r // mx, G - 1)]
+    return {"scale_q of the tile's first row": (first, None), "g computed with max_seqlen_q": (by_max, None)}
