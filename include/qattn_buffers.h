@@ -1,6 +1,7 @@
 /*
  * qattn_buffers.h -- the BUFFER CONTRACT of every entry of qattn.h, qattn_strided.h, qattn_smooth.h, qattn_varlen.h, qattn_window.h and
- * qattn_block_sparse.h, and of qattn_rope.h, qattn_splitkv.h, qattn_kvcache.h, qattn_paged.h and qattn_paged_varlen.h (documentation only: no declaration).  Held by
+ * qattn_block_sparse.h, and of qattn_rope.h, qattn_splitkv.h, qattn_kvcache.h, qattn_paged.h, qattn_paged_varlen.h and qattn_splitkv_window.h
+ * (documentation only: no declaration).  Held by
  * tests/test_gpu_buffer_contract.py (qattn_rope.h: tests/test_gpu_rope_buffer_contract.py; qattn_splitkv.h:
  * tests/test_gpu_splitkv_buffer_contract.py; qattn_kvcache.h: tests/test_gpu_kvcache_buffer_contract.py; qattn_paged.h:
  * tests/test_gpu_paged_buffer_contract.py) on guarded buffers of exactly these sizes at exactly these alignments.
@@ -121,6 +122,18 @@
  *              it for the most splits), 16-byte aligned, needed whenever total_q > 0 (total_q = 0: nothing is launched or written, the
  *              workspace's size is not looked at); it holds whatever optional output is NULL, the pre-pass's abs-max words and, for ns > 8, the merge's fp32 accumulator; no
  *              result depends on what it held.
+ *
+ * qattn_fp8_attention_splitkv_window_forward, qattn_fp8_attention_paged_splitkv_window_forward and
+ * qattn_fp8_attention_paged_varlen_window_forward (qattn_splitkv_window.h; held by tests/test_gpu_splitkv_window_buffer_contract.py): every
+ * line of the sibling without a window -- qattn_fp8_attention_splitkv_forward, qattn_fp8_attention_paged_splitkv_forward,
+ * qattn_fp8_attention_paged_varlen_forward -- with window_left, window_right (two ints, no buffer) in is_causal's place, the same
+ * sizes, alignments and written elements, and the sibling's own workspace size function.  What is READ shrinks: with
+ * lo_i = window_left < 0 ? 0 : clamp(L_i - Sq_i - window_left, 0, L_i),
+ *   k8 / v8, k_pool / v_pool  the 64-key chunks lo_i / 64 .. ceil(L_i / 64) - 1 of sequence i at the most (a tile: the chunks of the keys its
+ *              rows attend), no other byte; the bytes of the keys below lo_i in lo_i's chunk and behind L_i in L_i's chunk are fetched and
+ *              influence no result (NaN patterns included).
+ *   block_table  the entries lo_i / page_size .. ceil(L_i / page_size) - 1 of row i at the most, each clamped before it forms an address;
+ *              the leading entries may hold anything (their pages may have been handed to another sequence).
  */
 #ifndef QATTN_BUFFERS_H_
 #define QATTN_BUFFERS_H_

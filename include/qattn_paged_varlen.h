@@ -52,7 +52,8 @@
  * Buffers: include/qattn_buffers.h.
  *
  * Not offered: a packed [total, Hkv, D] append (qattn_paged_kv_cache_append_fp8 with new_lens serves a mixed step: pad the new keys to the
- * longest chunk), sliding windows, a per-call table whose batch differs from the scales' and lengths', the contiguous KVCacheFP8.
+ * longest chunk), a per-call table whose batch differs from the scales' and lengths', the contiguous KVCacheFP8.  Sliding windows:
+ * qattn_fp8_attention_paged_varlen_window_forward, include/qattn_splitkv_window.h.
  */
 #ifndef QATTN_PAGED_VARLEN_H_
 #define QATTN_PAGED_VARLEN_H_

@@ -55,6 +55,8 @@ EXPORTS = (
     "qattn_kv_cache_append_fp8",
     "qattn_paged_kv_cache_append_fp8", "qattn_fp8_attention_paged_splitkv_workspace_bytes", "qattn_fp8_attention_paged_splitkv_forward",
     "qattn_fp8_attention_paged_varlen_workspace_bytes", "qattn_paged_varlen_auto_splits", "qattn_fp8_attention_paged_varlen_forward",
+    "qattn_splitkv_window_auto_splits", "qattn_paged_varlen_window_auto_splits", "qattn_fp8_attention_splitkv_window_forward",
+    "qattn_fp8_attention_paged_splitkv_window_forward", "qattn_fp8_attention_paged_varlen_window_forward",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -261,6 +263,21 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_attention_paged_varlen_forward.restype = i
     L.qattn_fp8_attention_paged_varlen_forward.argtypes = [vp, vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i,
                                                            f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    # the three split-KV entries under a sliding window (include/qattn_splitkv_window.h): the sibling's arguments with is_causal replaced by
+    # window_left, window_right; the auto-split rules take window_left before num_cus
+    L.qattn_splitkv_window_auto_splits.restype = i
+    L.qattn_splitkv_window_auto_splits.argtypes = [i, i, i, i, i, i, i, i]
+    L.qattn_paged_varlen_window_auto_splits.restype = i
+    L.qattn_paged_varlen_window_auto_splits.argtypes = [i, i, i, i, i, i, i, i, i]
+    L.qattn_fp8_attention_splitkv_window_forward.restype = i
+    L.qattn_fp8_attention_splitkv_window_forward.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, f, i, i,
+                                                             vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.qattn_fp8_attention_paged_splitkv_window_forward.restype = i
+    L.qattn_fp8_attention_paged_splitkv_window_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i,
+                                                                   f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.qattn_fp8_attention_paged_varlen_window_forward.restype = i
+    L.qattn_fp8_attention_paged_varlen_window_forward.argtypes = [vp, vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i,
+                                                                  i, i, i, f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1139,6 +1156,24 @@ def fp8_rope_quant_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
     return (out,) + ((lse,) if return_lse else ()) + ((quant,) if return_quant else ())
 
 
+def splitkv_window_auto_splits(B: int, Hq: int, Hkv: int, Sq: int, Skv: int, D: int, window_left: int, num_cus: int) -> int:
+    """qattn_splitkv_window_auto_splits (include/qattn_splitkv_window.h): the num_splits = 0 rule of the dense window entries."""
+    return int(lib().qattn_splitkv_window_auto_splits(B, Hq, Hkv, Sq, Skv, D, window_left, num_cus))
+
+
+def paged_varlen_window_auto_splits(B: int, Hq: int, Hkv: int, total_q: int, max_seqlen_q: int, Skv: int, D: int, window_left: int,
+                                    num_cus: int) -> int:
+    """qattn_paged_varlen_window_auto_splits (include/qattn_splitkv_window.h): the num_splits = 0 rule of the packed window entry."""
+    return int(lib().qattn_paged_varlen_window_auto_splits(B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, window_left, num_cus))
+
+
+def _window_args(window):
+    """(window_left, window_right) of a window entry as C ints."""
+    _require(len(window) == 2 and all(isinstance(w, int) and not isinstance(w, bool) and w >= -1 for w in window),
+             f"window must be a pair of integers >= -1, got {window!r}")
+    return int(window[0]), int(window[1])
+
+
 def splitkv_auto_splits(B: int, Hq: int, Hkv: int, Sq: int, Skv: int, D: int, num_cus: int) -> int:
     """qattn_splitkv_auto_splits (include/qattn_splitkv.h): the num_splits = 0 rule, a pure host function of the shape and the CU count."""
     return int(lib().qattn_splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, num_cus))
@@ -1148,15 +1183,18 @@ def fp8_attention_splitkv(q: torch.Tensor, k_frag: torch.Tensor, v_frag: torch.T
                           Skv: int, fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled", is_causal: bool = False,
                           sm_scale: float = 0.0, precision: str = "accurate", num_splits: int = 0,
                           seqused_k: Optional[torch.Tensor] = None, return_lse: bool = False, return_partials: bool = False,
-                          return_quant: bool = False, return_path: bool = False):
+                          return_quant: bool = False, return_path: bool = False, window: Optional[Tuple[int, int]] = None):
     """Split-KV attention over prepared K / V (qattn_fp8_attention_splitkv_forward, include/qattn_splitkv.h).  q [B, Hq, Sq, D] bf16 / fp16;
     k_frag / v_frag: the KFRAG / VFRAG images (flat uint8) of [B, Hkv, Skv, D] in fp8_dtype with scale_k / scale_v fp32 [B, Hkv];
     seqused_k int32 [B] on the device or None.  num_splits 0: the auto rule on the device's CU count (resolved here, on the host).
     Returns out, or a tuple of out, [lse], [partial_o fp32 [ns, B, Hq, Sq, D], partial_lse [ns, B, Hq, Sq], partial_path uint8 -- three
-    empty tensors when the call ran one split], [q8, scale_q], [row_path uint8 [B, Hq, Sq]]."""
+    empty tensors when the call ran one split], [q8, scale_q], [row_path uint8 [B, Hq, Sq]].
+    window = (left, right): qattn_fp8_attention_splitkv_window_forward (include/qattn_splitkv_window.h) instead -- the window stands in
+    is_causal's place, which is then not read; the same for the two paged functions below."""
     _require(precision in ("fast", "accurate"), f"Unsupported precision for the split-KV entry: {precision!r} (expected 'fast' or 'accurate')")
     _require(q.is_cuda and q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16), "query must be a 4-D bf16 / fp16 device tensor")
     _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
+    mask_args = (int(bool(is_causal)),) if window is None else _window_args(window)
     q = q.contiguous()
     B, Hq, Sq, D = q.shape
     _require(scale_k.dim() == 2 and scale_k.shape[0] == B and scale_k.shape == scale_v.shape, "scale_k / scale_v must be fp32 [B, Hkv]")
@@ -1174,7 +1212,8 @@ def fp8_attention_splitkv(q: torch.Tensor, k_frag: torch.Tensor, v_frag: torch.T
                  f"seqused_k must be a dense int32 [B] tensor on {dev}")
     ns = int(num_splits)
     if ns == 0:
-        ns = splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, torch.cuda.get_device_properties(dev).multi_processor_count)
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        ns = splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, cus) if window is None else splitkv_window_auto_splits(B, Hq, Hkv, Sq, Skv, D, window[0], cus)
     with torch.cuda.device(dev):
         out = torch.empty((B, Hq, Sq, D), dtype=q.dtype, device=dev)
         lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev) if return_lse else None
@@ -1192,11 +1231,12 @@ def fp8_attention_splitkv(q: torch.Tensor, k_frag: torch.Tensor, v_frag: torch.T
         ws_bytes = L.qattn_fp8_attention_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, ns)
         ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
         live = lambda t: _ptr(t) if t is not None and t.numel() else None
-        rc = L.qattn_fp8_attention_splitkv_forward(
+        fwd = L.qattn_fp8_attention_splitkv_forward if window is None else L.qattn_fp8_attention_splitkv_window_forward
+        rc = fwd(
             q.data_ptr(), fmt_of(q.dtype), k_frag.data_ptr(), v_frag.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(),
-            _ptr(lse), _ptr(seqused_k), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), int(bool(is_causal)), float(sm_scale),
+            _ptr(lse), _ptr(seqused_k), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), *mask_args, float(sm_scale),
             _precision(precision), ns, _ptr(q8), _ptr(sq), _ptr(path), live(po), live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_attention_splitkv_forward")
+    _check(rc, "qattn_fp8_attention_splitkv_forward" if window is None else "qattn_fp8_attention_splitkv_window_forward")
     if not (return_lse or return_partials or return_quant or return_path):
         return out
     return ((out,) + ((lse,) if return_lse else ()) + ((po, plse, ppath) if return_partials else ()) + ((q8, sq) if return_quant else ())
@@ -1287,7 +1327,7 @@ def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: t
                                 block_table: torch.Tensor, seqused_k: torch.Tensor, *, Skv: int, num_pages: int, page_size: int,
                                 fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled", is_causal: bool = False, sm_scale: float = 0.0,
                                 precision: str = "accurate", num_splits: int = 0, return_lse: bool = False, return_partials: bool = False,
-                                return_quant: bool = False, return_path: bool = False):
+                                return_quant: bool = False, return_path: bool = False, window: Optional[Tuple[int, int]] = None):
     """Split-KV attention over a paged cache (qattn_fp8_attention_paged_splitkv_forward, include/qattn_paged.h): fp8_attention_splitkv with
     the pools (flat uint8: the KFRAG / VFRAG images of [num_pages, Hkv, page_size, D]) and block_table int32 [B, max_pages] in place of the
     contiguous images; Skv <= max_pages page_size is the logical bound, seqused_k int32 [B] is required.  Returns what
@@ -1295,6 +1335,7 @@ def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: t
     _require(precision in ("fast", "accurate"), f"Unsupported precision for the split-KV entry: {precision!r} (expected 'fast' or 'accurate')")
     _require(q.is_cuda and q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16), "query must be a 4-D bf16 / fp16 device tensor")
     _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
+    mask_args = (int(bool(is_causal)),) if window is None else _window_args(window)
     q = q.contiguous()
     B, Hq, Sq, D = q.shape
     _require(scale_k.dim() == 2 and scale_k.shape[0] == B, "scale_k / scale_v must be fp32 [B, Hkv]")
@@ -1308,7 +1349,8 @@ def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: t
              and seqused_k.is_contiguous(), f"seqused_k must be a dense int32 [B] tensor on {dev}")
     ns = int(num_splits)
     if ns == 0:
-        ns = splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, torch.cuda.get_device_properties(dev).multi_processor_count)
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        ns = splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, cus) if window is None else splitkv_window_auto_splits(B, Hq, Hkv, Sq, Skv, D, window[0], cus)
     with torch.cuda.device(dev):
         out = torch.empty((B, Hq, Sq, D), dtype=q.dtype, device=dev)
         lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev) if return_lse else None
@@ -1326,12 +1368,13 @@ def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: t
         ws_bytes = L.qattn_fp8_attention_paged_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, ns)
         ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
         live = lambda t: _ptr(t) if t is not None and t.numel() else None
-        rc = L.qattn_fp8_attention_paged_splitkv_forward(
+        fwd = L.qattn_fp8_attention_paged_splitkv_forward if window is None else L.qattn_fp8_attention_paged_splitkv_window_forward
+        rc = fwd(
             q.data_ptr(), fmt_of(q.dtype), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), tstride, num_pages, page_size, max_pages,
             scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(), _ptr(lse), seqused_k.data_ptr(), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype),
-            _numerics(numerics), int(bool(is_causal)), float(sm_scale), _precision(precision), ns, _ptr(q8), _ptr(sq), _ptr(path), live(po),
+            _numerics(numerics), *mask_args, float(sm_scale), _precision(precision), ns, _ptr(q8), _ptr(sq), _ptr(path), live(po),
             live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_attention_paged_splitkv_forward")
+    _check(rc, "qattn_fp8_attention_paged_splitkv_forward" if window is None else "qattn_fp8_attention_paged_splitkv_window_forward")
     if not (return_lse or return_partials or return_quant or return_path):
         return out
     return ((out,) + ((lse,) if return_lse else ()) + ((po, plse, ppath) if return_partials else ()) + ((q8, sq) if return_quant else ())
@@ -1354,7 +1397,8 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
                                block_table: torch.Tensor, seqused_k: torch.Tensor, cu_seqlens_q: torch.Tensor, *, max_seqlen_q: int, Skv: int,
                                num_pages: int, page_size: int, fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled",
                                is_causal: bool = False, sm_scale: float = 0.0, precision: str = "accurate", num_splits: int = 0,
-                               return_lse: bool = False, return_partials: bool = False, return_quant: bool = False, return_path: bool = False):
+                               return_lse: bool = False, return_partials: bool = False, return_quant: bool = False, return_path: bool = False,
+                               window: Optional[Tuple[int, int]] = None):
     """Split-KV attention of PACKED queries over a paged cache (qattn_fp8_attention_paged_varlen_forward, include/qattn_paged_varlen.h).
     q [total_q, Hq, D] bf16 / fp16, dense or a view `paged_varlen_q_addressable` accepts (read in place); cu_seqlens_q int32 [B + 1] and
     seqused_k int32 [B] on the device; the pools, the table and the scales as fp8_attention_paged_splitkv.  num_splits 0: the auto rule on
@@ -1364,6 +1408,7 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
     _require(precision in ("fast", "accurate"), f"Unsupported precision for the split-KV entry: {precision!r} (expected 'fast' or 'accurate')")
     _require(q.is_cuda and q.dim() == 3 and q.dtype in (torch.bfloat16, torch.float16), "query must be a 3-D bf16 / fp16 device tensor [total_q, Hq, D]")
     _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
+    mask_args = (int(bool(is_causal)),) if window is None else _window_args(window)
     total_q, Hq, D = q.shape
     if total_q and not paged_varlen_q_addressable(q):
         q = q.contiguous()
@@ -1381,7 +1426,9 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
              and cu_seqlens_q.is_contiguous(), f"cu_seqlens_q must be a dense int32 [B + 1] tensor on {dev}")
     ns = int(num_splits)
     if ns == 0:
-        ns = paged_varlen_auto_splits(B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, torch.cuda.get_device_properties(dev).multi_processor_count)
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        ns = (paged_varlen_auto_splits(B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, cus) if window is None
+              else paged_varlen_window_auto_splits(B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, window[0], cus))
     with torch.cuda.device(dev):
         out = torch.empty((total_q, Hq, D), dtype=q.dtype, device=dev)
         lse = torch.empty((Hq, total_q), dtype=torch.float32, device=dev) if return_lse else None
@@ -1403,12 +1450,13 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
             live = lambda t: _ptr(t) if t is not None and t.numel() else None
             dense = (Hq * D, D)     # (a dimension of size 1 has no stride of its own)
             s2 = (ctypes.c_longlong * 2)(*[q.stride(i) if q.shape[i] > 1 else dense[i] for i in (0, 1)])
-            rc = L.qattn_fp8_attention_paged_varlen_forward(
+            fwd = L.qattn_fp8_attention_paged_varlen_forward if window is None else L.qattn_fp8_attention_paged_varlen_window_forward
+            rc = fwd(
                 q.data_ptr(), s2, fmt_of(q.dtype), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), tstride, num_pages, page_size,
                 max_pages, scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), seqused_k.data_ptr(), B, Hq,
-                Hkv, total_q, max_seqlen_q, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), int(bool(is_causal)), float(sm_scale),
+                Hkv, total_q, max_seqlen_q, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), *mask_args, float(sm_scale),
                 _precision(precision), ns, live(q8), _ptr(sq), live(path), live(po), live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_attention_paged_varlen_forward")
+    _check(rc, "qattn_fp8_attention_paged_varlen_forward" if window is None else "qattn_fp8_attention_paged_varlen_window_forward")
     if not (return_lse or return_partials or return_quant or return_path):
         return out
     return ((out,) + ((lse,) if return_lse else ()) + ((po, plse, ppath) if return_partials else ()) + ((q8, sq) if return_quant else ())

@@ -21,7 +21,8 @@ LIB = os.path.join(HERE, "libqattn_hip.so")
 # A/B baselines and tuning variants (`--variant=`) live in tools/ab_libs/, not beside the product library
 AB_LIBS = os.path.join(os.path.dirname(HERE), "tools", "ab_libs")
 SOURCES = ["qattn_quant.hip", "qattn_attn_v2.hip", "qattn_attn_v4.hip", "qattn_attn16.hip", "qattn_api.hip", "qattn_probe.hip", "qattn_attn_pv16.hip", "qattn_varlen.hip",
-           "qattn_block_sparse.hip", "qattn_block_sparse_fp8.hip", "qattn_smooth_k.hip", "qattn_varlen_smooth.hip", "qattn_varlen_window.hip", "qattn_varlen_fp8.hip", "qattn_varlen_window_fp8.hip", "qattn_merge.hip", "qattn_rope_quant.hip", "qattn_splitkv_fp8.hip", "qattn_kvcache_append.hip", "qattn_paged_splitkv_fp8.hip", "qattn_paged_append.hip", "qattn_paged_varlen_splitkv_fp8.hip"]
+           "qattn_block_sparse.hip", "qattn_block_sparse_fp8.hip", "qattn_smooth_k.hip", "qattn_varlen_smooth.hip", "qattn_varlen_window.hip", "qattn_varlen_fp8.hip", "qattn_varlen_window_fp8.hip", "qattn_merge.hip", "qattn_rope_quant.hip", "qattn_splitkv_fp8.hip", "qattn_kvcache_append.hip", "qattn_paged_splitkv_fp8.hip", "qattn_paged_append.hip", "qattn_paged_varlen_splitkv_fp8.hip",
+           "qattn_splitkv_window_fp8.hip", "qattn_paged_splitkv_window_fp8.hip", "qattn_paged_varlen_splitkv_window_fp8.hip"]
 # (source, extra flags, object name): the two big kernel files are compiled once per operand format / head dimension so that
 # the build runs in parallel (the longest single translation unit sets the wall time)
 # (a unit with a define is compiled through a two-line wrapper file named after the unit, so that -save-temps leaves one .s
@@ -61,6 +62,10 @@ UNITS = [
     ("qattn_paged_splitkv_fp8.hip", [], "qattn_paged_splitkv_fp8"),   # the split-KV sweep over a pool of pages behind a block table (include/qattn_paged.h)
     ("qattn_paged_append.hip", [], "qattn_paged_append"),   # ... and the append into it: csrc/qattn_splitkv_attn.h / qattn_kvcache_append.h with PAGED = true
     ("qattn_paged_varlen_splitkv_fp8.hip", [], "qattn_paged_varlen_splitkv_fp8"),   # the paged sweep under packed queries, a count per sequence (include/qattn_paged_varlen.h)
+    # the three split-KV sweeps under a sliding window (include/qattn_splitkv_window.h): a unit each, so that they compile in parallel
+    ("qattn_splitkv_window_fp8.hip", [], "qattn_splitkv_window_fp8"),
+    ("qattn_paged_splitkv_window_fp8.hip", [], "qattn_paged_splitkv_window_fp8"),
+    ("qattn_paged_varlen_splitkv_window_fp8.hip", [], "qattn_paged_varlen_splitkv_window_fp8"),
 ]
 # (Until round 5 `--dev` built a second library with -DQATTN_DEV: timing-only ablation instantiations, per-segment cycle stamps, work logs and
 # QATTN_* environment switches.  Round 6 took that scaffolding out of the sources -- identical product ISA, profiles/r06/isa_identity_*.log;
@@ -105,7 +110,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = False, 
     os.makedirs(build_dir, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("qattn.h", "qattn_measure.h", "qattn_varlen.h", "qattn_block_sparse.h", "qattn_smooth.h", "qattn_window.h", "qattn_merge.h", "qattn_rope.h", "qattn_splitkv.h", "qattn_kvcache.h", "qattn_paged.h", "qattn_paged_varlen.h")]
+    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("qattn.h", "qattn_measure.h", "qattn_varlen.h", "qattn_block_sparse.h", "qattn_smooth.h", "qattn_window.h", "qattn_merge.h", "qattn_rope.h", "qattn_splitkv.h", "qattn_kvcache.h", "qattn_paged.h", "qattn_paged_varlen.h", "qattn_splitkv_window.h")]
     objs, jobs = [], []
     for src, defines, name in UNITS:
         s = os.path.join(CSRC, src)

@@ -6,6 +6,9 @@
 // A third compilation of the body, paged K / V under PACKED queries of a different count per sequence, belongs to
 // qattn_fp8_attention_paged_varlen_forward (qattn_paged_varlen_splitkv_fp8.hip, include/qattn_paged_varlen.h); that entry has a driver of
 // its own and shares the launch ladder, the merge chain (skv_merge_chain) and the path launch with skv_forward.
+// Three more compilations put a sliding window where `causal` stands (QATTN_SKV_WINDOW; include/qattn_splitkv_window.h): the kernels of
+// qattn_splitkv_window_fp8.hip, qattn_paged_splitkv_window_fp8.hip and qattn_paged_varlen_splitkv_window_fp8.hip, launched through the same
+// ladder and the same drivers.  The window travels as a kernel argument of its own (SkvWindow): SkvAttn is what it was, field for field.
 #pragma once
 #include <limits.h>
 
@@ -48,6 +51,12 @@ struct SkvPages {
 struct SkvVarq {
     const int* cu;   // cu_seqlens_q [B + 1]
     int B, total_q, Hq;
+};
+
+// WINDOW: window_size = (left, right) of include/qattn_window.h, each >= -1 (-1: unbounded on that side).  A kernel argument of its own,
+// so that SkvAttn -- and with it every kernarg offset of the kernels without a window -- stays what it was.
+struct SkvWindow {
+    int left, right;
 };
 
 // Physical chunk of chunk `ch` of kv head hkv of the page a RAW table entry names.  The clamp is what keeps every address inside the
@@ -93,13 +102,34 @@ __device__ __forceinline__ void skv_zero_v_tail(unsigned char* vst, int nvalid) 
     lds_barrier();
 }
 
+// The mirror of skv_zero_v_tail for the chunk that holds the first key of a sliding window's interval: the bytes of its keys < nfirst
+// (0 < nfirst < 64) set to zero.  Same callers' duties: all four waves, after the stage has landed, before anyone reads it.
+template <int D>
+__device__ __forceinline__ void skv_zero_v_head(unsigned char* vst, int nfirst) {
+    constexpr int CH = 64 * D;
+    for (int o = (int)threadIdx.x * 16; o < CH; o += kFpvWaves * 64 * 16) {
+        v4i x = *reinterpret_cast<v4i*>(vst + o);
+        const int key0 = 32 * ((o >> 9) & 1) + 4 * ((o >> 10) & 1);
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const int dead = nfirst - (key0 + 8 * w);   // keys of this word below the interval: bytes 0 .. dead - 1
+            const unsigned keep = dead >= 4 ? 0u : dead <= 0 ? 0xffffffffu : ~((1u << (8 * dead)) - 1u);
+            x[w] = (int)((unsigned)x[w] & keep);
+        }
+        *reinterpret_cast<v4i*>(vst + o) = x;
+    }
+    lds_barrier();
+}
+
 // The two kernels: one body (qattn_splitkv_body.h), compiled once per chunk addressing.  BYTE / two / sel: as attn_vfp8_window_kernel.
 template <int D, int FMT, bool BYTE>
 __global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
 void attn_splitkv_fp8_kernel(const SkvAttn a, const int two, const int sel) {
 #define QATTN_SKV_PAGED 0
 #define QATTN_SKV_VARQ 0
+#define QATTN_SKV_WINDOW 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
 }
@@ -109,7 +139,9 @@ __global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
 void attn_paged_splitkv_fp8_kernel(const SkvAttn a, const SkvPages pg, const int two, const int sel) {
 #define QATTN_SKV_PAGED 1
 #define QATTN_SKV_VARQ 0
+#define QATTN_SKV_WINDOW 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
 }
@@ -119,19 +151,66 @@ __global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
 void attn_paged_varlen_splitkv_fp8_kernel(const SkvAttn a, const SkvPages pg, const SkvVarq vq, const int two, const int sel) {
 #define QATTN_SKV_PAGED 1
 #define QATTN_SKV_VARQ 1
+#define QATTN_SKV_WINDOW 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
 }
 
-// which of the three kernels a launch runs
-constexpr int kSkvContig = 0, kSkvPaged = 1, kSkvPagedVarq = 2;
+// ... and the same three under a sliding window `wn` in a.causal's place (QATTN_SKV_WINDOW)
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_splitkv_window_fp8_kernel(const SkvAttn a, const SkvWindow wn, const int two, const int sel) {
+#define QATTN_SKV_PAGED 0
+#define QATTN_SKV_VARQ 0
+#define QATTN_SKV_WINDOW 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_paged_splitkv_window_fp8_kernel(const SkvAttn a, const SkvPages pg, const SkvWindow wn, const int two, const int sel) {
+#define QATTN_SKV_PAGED 1
+#define QATTN_SKV_VARQ 0
+#define QATTN_SKV_WINDOW 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_paged_varlen_splitkv_window_fp8_kernel(const SkvAttn a, const SkvPages pg, const SkvVarq vq, const SkvWindow wn, const int two,
+                                                 const int sel) {
+#define QATTN_SKV_PAGED 1
+#define QATTN_SKV_VARQ 1
+#define QATTN_SKV_WINDOW 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+// which of the six kernels a launch runs (kSkvWindow + one of the first three: that kernel under a window)
+constexpr int kSkvContig = 0, kSkvPaged = 1, kSkvPagedVarq = 2, kSkvWindow = 4;
 
 template <int D, int FMT, int MODE>
-static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, unsigned grid, int max_keys, int precision, bool want_lse,
-                          hipStream_t st) {
+static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys,
+                          int precision, bool want_lse, hipStream_t st) {
     return fpv_precision_ladder(precision, max_keys, a.two_term_keys, want_lse, [&](auto byte, int two, int sel) {
-        if constexpr (MODE == kSkvPagedVarq)
+        if constexpr (MODE == kSkvWindow + kSkvPagedVarq)
+            return fpv_launch(attn_paged_varlen_splitkv_window_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg, vq, wn,
+                              two, sel);
+        else if constexpr (MODE == kSkvWindow + kSkvPaged)
+            return fpv_launch(attn_paged_splitkv_window_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg, wn, two, sel);
+        else if constexpr (MODE == kSkvWindow + kSkvContig)
+            return fpv_launch(attn_splitkv_window_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, wn, two, sel);
+        else if constexpr (MODE == kSkvPagedVarq)
             return fpv_launch(attn_paged_varlen_splitkv_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg, vq, two, sel);
         else if constexpr (MODE == kSkvPaged)
             return fpv_launch(attn_paged_splitkv_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg, two, sel);
@@ -140,19 +219,38 @@ static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, const SkvVarq& v
 }
 
 template <int D, int MODE>
-static int launch_skv_d(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, unsigned grid, int max_keys, int fp8_fmt, int precision,
-                        bool want_lse, hipStream_t st) {
-    return fp8_fmt == QATTN_FMT_E4M3 ? launch_skv_fmt<D, QATTN_FMT_E4M3, MODE>(a, pg, vq, grid, max_keys, precision, want_lse, st)
-                                     : launch_skv_fmt<D, QATTN_FMT_E5M2, MODE>(a, pg, vq, grid, max_keys, precision, want_lse, st);
+static int launch_skv_d(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys, int fp8_fmt,
+                        int precision, bool want_lse, hipStream_t st) {
+    return fp8_fmt == QATTN_FMT_E4M3 ? launch_skv_fmt<D, QATTN_FMT_E4M3, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st)
+                                     : launch_skv_fmt<D, QATTN_FMT_E5M2, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st);
 }
 
 // every head dimension of one entry
 template <int MODE>
-static int launch_skv(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, unsigned grid, int max_keys, int D, int fp8_fmt, int precision,
-                      bool want_lse, hipStream_t st) {
-    if (D == 64) return launch_skv_d<64, MODE>(a, pg, vq, grid, max_keys, fp8_fmt, precision, want_lse, st);
-    if (D == 128) return launch_skv_d<128, MODE>(a, pg, vq, grid, max_keys, fp8_fmt, precision, want_lse, st);
-    return launch_skv_d<256, MODE>(a, pg, vq, grid, max_keys, fp8_fmt, precision, want_lse, st);
+static int launch_skv(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys, int D,
+                      int fp8_fmt, int precision, bool want_lse, hipStream_t st) {
+    if (D == 64) return launch_skv_d<64, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st);
+    if (D == 128) return launch_skv_d<128, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st);
+    return launch_skv_d<256, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st);
+}
+
+// Host side of a window (include/qattn_splitkv_window.h).  Under left >= 0 a sequence's interval [lo_i, L) holds at most left + Sq keys,
+// which touch at most ceil((left + Sq) / 128) + 1 key blocks.
+// skv_window_keys: the key count the num_splits = 0 rule sees, min(Skv, left + Sq + 127).
+inline int skv_window_keys(int Skv, int Sq, int left) {
+    const long long k = (long long)left + Sq + 127;
+    return (left < 0 || k >= Skv) ? Skv : (int)k;
+}
+// skv_max_keys: an upper bound on the keys any workgroup sweeps with ns splits -- what fpv_precision_ladder needs to launch the one-term
+// kernel whenever a workgroup can reach two_term_keys.  Sq: the most queries of a sequence.  left = -1: the most keys a split can own.
+inline int skv_max_keys(int Skv, int Sq, int left, int ns) {
+    long long nkb = ceil_div(Skv, 128);
+    if (left >= 0) {
+        const long long in_window = ((long long)left + Sq + 127) / 128 + 1;
+        if (in_window < nkb) nkb = in_window;
+    }
+    const long long span = 128 * ((nkb + ns - 1) / ns);
+    return span < Skv ? (int)span : Skv;
 }
 
 inline bool skv_dims_ok(int B, int Hq, int Hkv, int Sq, int Skv) { return B > 0 && Hq > 0 && Hkv > 0 && Sq > 0 && Skv > 0; }
@@ -222,11 +320,14 @@ inline int skv_merge_chain(const float* po, const float* plse, int ns, long rows
 
 // Both entries, from their common arguments on: k8 / v8 are the contiguous images of [B, Hkv, Skv, D] or -- PAGED, with pg filled in and
 // checked by the caller -- the pools.
-template <bool PAGED>
+// WINDOW: the window kernels under (window_left, window_right) in is_causal's place -- also for (-1, 0) and (-1, -1).
+template <bool PAGED, bool WINDOW = false>
 int skv_forward(const void* q16, int in_fmt, const void* k8, const void* v8, const SkvPages& pg, const float* scale_k, const float* scale_v,
                 void* out, float* lse, const int* seqused_k, int B, int Hq, int Hkv, int Sq, int Skv, int D, int fp8_fmt, int numerics,
                 int is_causal, float sm_scale, int precision, int num_splits, void* q8, float* scale_q, unsigned char* row_path,
-                float* partial_o, float* partial_lse, unsigned char* partial_path, void* workspace, size_t workspace_bytes, void* stream) {
+                float* partial_o, float* partial_lse, unsigned char* partial_path, void* workspace, size_t workspace_bytes, void* stream,
+                int window_left = -1, int window_right = -1) {
+    if (WINDOW && (window_left < -1 || window_right < -1)) return QATTN_ERR_INVALID_ARG;
     if (!q16 || !k8 || !v8 || !scale_k || !scale_v || !out) return QATTN_ERR_INVALID_ARG;
     if (!skv_dims_ok(B, Hq, Hkv, Sq, Skv)) return QATTN_ERR_INVALID_ARG;
     if (!skv_d_ok(D) || Hq % Hkv != 0) return QATTN_ERR_UNSUPPORTED_DIM;
@@ -249,7 +350,8 @@ int skv_forward(const void* q16, int in_fmt, const void* k8, const void* v8, con
     const int ns_most = num_splits > 0 ? num_splits : (nkb_all < QATTN_SPLITKV_MAX_SPLITS ? nkb_all : QATTN_SPLITKV_MAX_SPLITS);
     if ((long long)B * Hkv * ntile * ns_most > 0x7fffffffLL) return QATTN_ERR_INVALID_ARG;   // (one workgroup per work item: a 32-bit grid)
     if (!workspace || workspace_bytes < skv_ws(B, Hq, Sq, D, ns_most).total()) return QATTN_ERR_WORKSPACE;
-    const int ns = num_splits > 0 ? num_splits : qattn_splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, cu_count());
+    const int ns = num_splits > 0 ? num_splits
+                                  : qattn_splitkv_auto_splits(B, Hq, Hkv, Sq, WINDOW ? skv_window_keys(Skv, Sq, window_left) : Skv, D, cu_count());
     const SkvWs ws = skv_ws(B, Hq, Sq, D, ns);
     hipStream_t st = (hipStream_t)stream;
     unsigned char* w = (unsigned char*)workspace;
@@ -287,12 +389,11 @@ int skv_forward(const void* q16, int in_fmt, const void* k8, const void* v8, con
     a.two_term_keys = kTwoTermKeys;
     a.sm_log2e = (sm_scale > 0.0f ? sm_scale : 1.0f / sqrtf((float)D)) * 1.4426950408889634f;
     // the most keys a split can own; the sweep asks for the LSE whenever it feeds the merge
-    const int nkb = ceil_div(Skv, 128);
-    const long long span = 128LL * ceil_div(nkb, ns);
-    const int max_keys = span < Skv ? (int)span : Skv;
+    const int max_keys = skv_max_keys(Skv, Sq, WINDOW ? window_left : -1, ns);
     const bool want_lse = lse != nullptr || ns > 1;
     const unsigned grid = (unsigned)((long long)B * Hkv * ntile * ns);
-    rc = launch_skv<PAGED ? kSkvPaged : kSkvContig>(a, pg, SkvVarq{}, grid, max_keys, D, fp8_fmt, precision, want_lse, st);
+    rc = launch_skv<(WINDOW ? kSkvWindow : 0) + (PAGED ? kSkvPaged : kSkvContig)>(a, pg, SkvVarq{}, SkvWindow{window_left, window_right}, grid,
+                                                                                 max_keys, D, fp8_fmt, precision, want_lse, st);
     if (rc != QATTN_OK) return rc;
     if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
     if (ns == 1) return QATTN_OK;

@@ -10,7 +10,14 @@
 // own Sq_i stands wherever the dense kernels read a.Sq.  The names that differ are macros (SKV_SQ, SKV_ROWS, SKV_QROW, SKV_QROW0, SKV_OROW,
 // SKV_LROW), so that with the switch off the text the compiler sees is token for token what it was
 // (profiles/paged_varlen/code_objects_vs_parent.log).
-// In scope: template parameters D, FMT, BYTE; arguments a (SkvAttn), two, sel, -- paged -- pg (SkvPages) and -- packed queries -- vq.
+// QATTN_SKV_WINDOW (include/qattn_splitkv_window.h) puts a sliding window (wn, SkvWindow: left / right, -1 = unbounded) where a.causal
+// stands: 0, the text above, token for token (profiles/splitkv_window/code_objects_vs_parent.log); 1, the split plan cuts the sequence's
+// interval [lo_i, L) instead of [0, L), the tile's trip range gets a lower end klo, the token mask a lower edge, and the V bytes of the
+// keys below lo_i that share its 64-key chunk are zeroed in LDS (skv_zero_v_head).  a.causal is then not read.  The edge offsets win_lo /
+// win_hi are attn_vfp8_window_kernel's, clamped exactly so that every sum below stays in 32 bits, and padding rows get that kernel's
+// masks: with one split, G = 1 and contiguous K / V the wave-mates, chunks and masks are its own.
+// In scope: template parameters D, FMT, BYTE; arguments a (SkvAttn), two, sel, -- paged -- pg (SkvPages), -- packed queries -- vq and
+// -- window -- wn.
 #if QATTN_SKV_VARQ
 #define SKV_SQ Sq_i
 #define SKV_ROWS rows_i
@@ -60,15 +67,35 @@
     int L = a.Skv;
     if (a.used) L = clampi(__builtin_amdgcn_readfirstlane(a.used[kvh / a.Hkv]), 0, a.Skv);
     // the split plan (workgroup-uniform, as everything down to the row numbers)
+#if QATTN_SKV_WINDOW
+    // position p attends the keys j with win_lo <= j - p <= win_hi.  j - p lies in (-Sq, L): an offset clamped to [-Sq, L] masks the same
+    // keys as the exact one.  The plan cuts the key blocks of the sequence's interval [lo_i, L): a function of (L, Sq, left, ns) alone
+    const long delta = (long)L - SKV_SQ;
+    auto clampl = [](long x, long lo, long hi) -> int { return (int)(x < lo ? lo : x > hi ? hi : x); };
+    const int win_lo = wn.left < 0 ? -SKV_SQ : clampl(delta - wn.left, -(long)SKV_SQ, L);
+    const int win_hi = wn.right < 0 ? L : clampl(delta + wn.right, -(long)SKV_SQ - 1, L);
+    const int lo_i = wn.left < 0 ? 0 : max(win_lo, 0);
+    const int kb0 = lo_i >> 7;
+    const int nkb = ((L + 127) >> 7) - kb0, per = (nkb + a.ns - 1) / a.ns;
+    const int k_begin = 128 * (kb0 + s * per), k_end = min(128 * (kb0 + (s + 1) * per), L);
+#else
     const int nkb = (L + 127) >> 7, per = (nkb + a.ns - 1) / a.ns;
     const int k_begin = 128 * s * per, k_end = min(128 * (s + 1) * per, L);
+#endif
     const int r_first = tile * kFpvTile, r_last = min(r_first + kFpvTile, SKV_ROWS) - 1;
     // positions of the tile's valid rows: [smin, smax] (a tile that crosses a head boundary holds a last and a first position)
     const int g_first = r_first / SKV_SQ, g_last = r_last / SKV_SQ;
     const int smin = g_first != g_last ? 0 : r_first - g_first * SKV_SQ, smax = g_first != g_last ? SKV_SQ - 1 : r_last - g_first * SKV_SQ;
+#if QATTN_SKV_WINDOW
+    // [klo, khi]: the keys of the split that the tile's valid rows attend
+    const int klo = max(k_begin, wn.left < 0 ? 0 : clampl((long)smin + win_lo, 0, L));
+    const int khi = min(k_end - 1, clampl((long)smax + win_hi, -1, L - 1));
+    const int keys = max(khi - klo + 1, 0);       // the keys this workgroup sweeps
+#else
     const int delta = L - SKV_SQ;   // causal: position p attends the keys j <= p + delta
     const int khi = a.causal ? min(k_end - 1, smax + delta) : k_end - 1;
     const int keys = max(khi - k_begin + 1, 0);   // the keys this workgroup sweeps
+#endif
     if (sel == kFpvSelMany && keys < a.two_term_keys) return;
     if (sel == kFpvSelFew && keys >= a.two_term_keys) return;
 
@@ -100,7 +127,11 @@
         }
         return;
     }
+#if QATTN_SKV_WINDOW
+    const int c_first = klo >> 6;                   // chunks c_first .. khi / 64 <= (L - 1) / 64 < nchunks: no other chunk is fetched
+#else
     const int c_first = k_begin >> 6;               // chunks c_first .. khi / 64 <= (L - 1) / 64 < nchunks
+#endif
     const int n_wg = (khi >> 6) - c_first + 1;
 
 #if QATTN_SKV_PAGED
@@ -129,9 +160,26 @@
     constexpr float kNoKeyYet = -1.0e20f;   // (attn_vfp8_window_kernel's header comment)
     sw.init_state(a.sm_log2e * a.sq[(long)kvh * a.G + g] * a.sk[kvh], kNoKeyYet);
     const int one = fpv_ones_word(lane);
+#if QATTN_SKV_WINDOW
+    // the first and the last key this lane's row attends (a padding row: position >= Sq, masked as attn_vfp8_window_kernel masks it), and
+    // where a chunk crosses an edge of some valid row: its end above `edge`, its start below `edge_lo`
+    const long pos = (long)r - (long)g * SKV_SQ;
+    const int lo_l = wn.left < 0 ? 0 : clampl(pos + win_lo, 0, L);
+    const int hi_l = clampl(pos + win_hi, -1, L - 1);
+    const int edge = clampl((long)smin + win_hi, -1, L);
+    const int edge_lo = wn.left < 0 ? 0 : clampl((long)smax + win_lo, 0, L);
+    // The keys below lo_i that share its chunk: no row attends them, so their P is exactly 0 -- and 0 x NaN is NaN in the matrix pipe.
+    // The workgroup whose first chunk holds lo_i zeroes their V bytes once the stage has landed, before anyone reads it (the mirror of
+    // skv_zero_v_tail; K needs nothing).
+    if ((c_first << 6) < lo_i) {
+        sw.wait_stage();
+        skv_zero_v_head<D>(smem + CH, lo_i - (c_first << 6));
+    }
+#else
     // the last key this lane's row attends, and the first chunk end that crosses the causal edge of some valid row
     const int hi_l = (a.causal && rvalid) ? min(L - 1, r - g * SKV_SQ + delta) : L - 1;
     const int edge = a.causal ? smin + delta : INT_MAX;
+#endif
 
     for (int t = 0; t < n_wg; t++) {   // step t sweeps chunk c_first + t
         const int k0 = (c_first + t) * 64;
@@ -157,6 +205,18 @@
         v16f s0, s1;
         v8i vf0, vf1;
         sw.qk(t, qf, s0, s1, vf0, vf1);
+#if QATTN_SKV_WINDOW
+        // ---- the ragged tail at L and the window's two edges by token, under a workgroup-uniform condition
+        if (__builtin_expect(k0 + 64 > L || k0 + 63 > edge || k0 < edge_lo, 0)) {
+            const int base = k0 + 4 * hh;
+#pragma unroll
+            for (int e = 0; e < 32; e++) {
+                const int key = base + 32 * (e >> 4) + (e & 3) + 8 * ((e & 15) >> 2);
+                v16f& sx = (e >> 4) ? s1 : s0;
+                sx[e & 15] = (key < lo_l || key > hi_l) ? -INFINITY : sx[e & 15];
+            }
+        }
+#else
         // ---- the ragged tail at L and the causal edge by token, under a workgroup-uniform condition
         if (__builtin_expect(k0 + 64 > L || k0 + 63 > edge, 0)) {
             const int base = k0 + 4 * hh;
@@ -167,6 +227,7 @@
                 sx[e & 15] = key > hi_l ? -INFINITY : sx[e & 15];
             }
         }
+#endif
         sw.softmax_pv(s0, s1, vf0, vf1, two, [&] { return fpv_spread_ones(one); });
     }
 

@@ -687,3 +687,146 @@ def _(query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, cu_seqlen
                 query.new_empty((n, Hq, total_q), dtype=torch.uint8))
     return (out, lse, query.new_empty((0,), dtype=torch.float32), query.new_empty((0,), dtype=torch.float32),
             query.new_empty((0,), dtype=torch.uint8))
+
+
+# ---- the three split-KV ops under a sliding window (include/qattn_splitkv_window.h): the sibling's arguments with is_causal replaced by
+# window_left, window_right (each >= -1).  They always run the window kernels, also for (-1, 0) and (-1, -1).
+
+def _skv_pack(res, query, return_lse, return_partials):
+    """(out, lse, partial_o, partial_lse, partial_path) of a _native split-KV result: what was not asked for is an empty tensor."""
+    res = res if isinstance(res, tuple) else (res,)
+    none_f = lambda: torch.empty((0,), dtype=torch.float32, device=query.device)
+    lse = res[1] if return_lse else none_f()
+    parts = res[-3:] if return_partials else (none_f(), none_f(), torch.empty((0,), dtype=torch.uint8, device=query.device))
+    return (res[0], lse) + tuple(parts)
+
+
+def _skv_fake(query, rows_o, rows_l, num_splits, return_lse, return_partials):
+    """The fake result of a split-KV op: rows_o / rows_l are the shapes of out without D / of lse."""
+    D = query.shape[-1]
+    out = query.new_empty(tuple(rows_o) + (D,))
+    lse = query.new_empty(tuple(rows_l) if return_lse else (0,), dtype=torch.float32)
+    n = num_splits if num_splits > 1 else 0
+    if return_partials:
+        return (out, lse, query.new_empty((n,) + tuple(rows_o) + (D,), dtype=torch.float32),
+                query.new_empty((n,) + tuple(rows_l), dtype=torch.float32), query.new_empty((n,) + tuple(rows_l), dtype=torch.uint8))
+    return (out, lse, query.new_empty((0,), dtype=torch.float32), query.new_empty((0,), dtype=torch.float32),
+            query.new_empty((0,), dtype=torch.uint8))
+
+
+@_custom_op("quantumattention_amd::fp8_splitkv_window_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_splitkv_window_attention_forward(
+    query: torch.Tensor,
+    k_frag: torch.Tensor,
+    v_frag: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    seqused_k: Optional[torch.Tensor],
+    seqlen_k: int,
+    num_splits: int,
+    window_left: int,
+    window_right: int,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    precision: str = "accurate",
+    return_lse: bool = False,
+    return_partials: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp8_splitkv_attention_forward under a sliding window (include/qattn_splitkv_window.h).  Reference implementation:
+    splitkv._splitkv_eager with window=.  Arguments are validated by splitkv_window.fp8_attn_splitkv_window_func."""
+    res = _native.fp8_attention_splitkv(
+        query, k_frag, v_frag, scale_k, scale_v, Skv=seqlen_k, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics,
+        sm_scale=0.0 if scale is None else float(scale), precision=precision, num_splits=num_splits, seqused_k=seqused_k,
+        return_lse=return_lse, return_partials=return_partials, window=(window_left, window_right))
+    return _skv_pack(res, query, return_lse, return_partials)
+
+
+@_register_fake("quantumattention_amd::fp8_splitkv_window_attention_forward")
+def _(query, k_frag, v_frag, scale_k, scale_v, seqused_k, seqlen_k, num_splits, window_left, window_right, fp8_format="e4m3",
+      numerics="compiled", precision="accurate", return_lse=False, return_partials=False, *, scale=None):
+    B, Hq, Sq, _ = query.shape
+    return _skv_fake(query, (B, Hq, Sq), (B, Hq, Sq), num_splits, return_lse, return_partials)
+
+
+@_custom_op("quantumattention_amd::fp8_paged_splitkv_window_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_paged_splitkv_window_attention_forward(
+    query: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    seqlen_k: int,
+    num_pages: int,
+    page_size: int,
+    num_splits: int,
+    window_left: int,
+    window_right: int,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    precision: str = "accurate",
+    return_lse: bool = False,
+    return_partials: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp8_paged_splitkv_attention_forward under a sliding window (include/qattn_splitkv_window.h).  Reference implementation:
+    paged._attend_eager with window=.  Arguments are validated by splitkv_window.fp8_attn_paged_window_func."""
+    res = _native.fp8_attention_paged_splitkv(
+        query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, Skv=seqlen_k, num_pages=num_pages, page_size=page_size,
+        fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics, sm_scale=0.0 if scale is None else float(scale), precision=precision,
+        num_splits=num_splits, return_lse=return_lse, return_partials=return_partials, window=(window_left, window_right))
+    return _skv_pack(res, query, return_lse, return_partials)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_splitkv_window_attention_forward")
+def _(query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, seqlen_k, num_pages, page_size, num_splits, window_left, window_right,
+      fp8_format="e4m3", numerics="compiled", precision="accurate", return_lse=False, return_partials=False, *, scale=None):
+    B, Hq, Sq, _ = query.shape
+    return _skv_fake(query, (B, Hq, Sq), (B, Hq, Sq), num_splits, return_lse, return_partials)
+
+
+@_custom_op("quantumattention_amd::fp8_paged_varlen_splitkv_window_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_paged_varlen_splitkv_window_attention_forward(
+    query: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    max_seqlen_q: int,
+    seqlen_k: int,
+    num_pages: int,
+    page_size: int,
+    num_splits: int,
+    window_left: int,
+    window_right: int,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    precision: str = "accurate",
+    return_lse: bool = False,
+    return_partials: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp8_paged_varlen_splitkv_attention_forward under a sliding window per sequence (include/qattn_splitkv_window.h).  Reference
+    implementation: paged._attend_varlen_eager with window=.  Arguments are validated by splitkv_window.fp8_attn_paged_varlen_window_func."""
+    res = _native.fp8_attention_paged_varlen(
+        query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, cu_seqlens_q, max_seqlen_q=max_seqlen_q, Skv=seqlen_k,
+        num_pages=num_pages, page_size=page_size, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics,
+        sm_scale=0.0 if scale is None else float(scale), precision=precision, num_splits=num_splits, return_lse=return_lse,
+        return_partials=return_partials, window=(window_left, window_right))
+    return _skv_pack(res, query, return_lse, return_partials)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_varlen_splitkv_window_attention_forward")
+def _(query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, cu_seqlens_q, max_seqlen_q, seqlen_k, num_pages, page_size, num_splits,
+      window_left, window_right, fp8_format="e4m3", numerics="compiled", precision="accurate", return_lse=False, return_partials=False, *,
+      scale=None):
+    total_q, Hq, _ = query.shape
+    return _skv_fake(query, (total_q, Hq), (Hq, total_q), num_splits, return_lse, return_partials)

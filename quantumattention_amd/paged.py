@@ -20,7 +20,7 @@ hold anything.  A page shared by several sequences (a common prefix) needs equal
 sequences that append into the same page in one call have two writers: undefined.
 
 Package attributes, not names of `__all__` (that list mirrors the reference).  Not offered: page allocation, copy-on-write, re-scaling,
-a per-call table whose batch differs from the cache's slots, sliding windows.  Queries of a different count per sequence slot (packed
+a per-call table whose batch differs from the cache's slots.  Sliding windows: splitkv_window.fp8_attn_paged_window_func.  Queries of a different count per sequence slot (packed
 [total_q, Hq, D] under cu_seqlens_q): `fp8_attn_paged_varlen_func`, paged_varlen.py."""
 import math
 from typing import Optional, Tuple
@@ -263,9 +263,9 @@ def gather_paged_eager(cache: PagedKVCacheFP8, Skv: Optional[int] = None) -> Pre
                       cache.numerics, "rowmajor")
 
 
-def _attend_eager(q, cache, causal, scale, seqused_k, Skv, ns, precision):
+def _attend_eager(q, cache, causal, scale, seqused_k, Skv, ns, precision, window=None):
     """CPU tensors and config.attention.force_eager_fallback: splitkv._splitkv_eager on the cache gathered through the table."""
-    return _splitkv_eager(q, gather_paged_eager(cache, Skv), causal, scale, seqused_k, ns, precision)
+    return _splitkv_eager(q, gather_paged_eager(cache, Skv), causal, scale, seqused_k, ns, precision, window)
 
 
 def paged_kv_cache_append_fp8(cache: PagedKVCacheFP8, k_new: Tensor, v_new: Tensor, *, new_lens: Optional[Tensor] = None,

@@ -12,8 +12,8 @@ in chunked prefill with hundreds of queries, many decode one token (or a few spe
 The rule: for every slot with queries, the rows of every output are, bit for bit, those of `fp8_attn_paged_func` on that slot alone.
 
 A package attribute, not a name of `__all__`.  Not offered: a packed [total, Hkv, D] append (the padded
-`paged_kv_cache_append_fp8(..., new_lens=)` serves a mixed step), sliding windows, a per-call table whose batch differs from the cache's
-slots, the contiguous `KVCacheFP8`."""
+`paged_kv_cache_append_fp8(..., new_lens=)` serves a mixed step), a per-call table whose batch differs from the cache's
+slots, the contiguous `KVCacheFP8`.  Sliding windows: splitkv_window.fp8_attn_paged_varlen_window_func."""
 import math
 from typing import Optional, Tuple
 
@@ -98,7 +98,7 @@ def _resolve_varlen_splits(num_splits: int, B: int, Hq: int, Hkv: int, total_q: 
     return _native.paged_varlen_auto_splits(B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, cus)
 
 
-def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, ns, precision):
+def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, ns, precision, window=None):
     """CPU tensors and config.attention.force_eager_fallback: per sequence slot, splitkv._splitkv_eager on the slot's queries and on its
     keys gathered through the table, scattered into the packed outputs.  Rows of tokens that belong to no sequence: zeros.  (This path
     reads cu_seqlens_q, seqused_k and the table on the host.)"""
@@ -121,7 +121,8 @@ def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, 
             continue
         one = PreparedKV(kv.k[b:b + 1], kv.v[b:b + 1], kv.scale_k[b:b + 1], kv.scale_v[b:b + 1], (1,) + tuple(kv.shape[1:]), kv.fp8_format,
                          kv.dtype, kv.numerics, "rowmajor")
-        o, l, p_o, p_l, p_p = _splitkv_eager(q[start:end].transpose(0, 1)[None], one, causal, scale, seqused_k[b:b + 1], ns, precision)
+        o, l, p_o, p_l, p_p = _splitkv_eager(q[start:end].transpose(0, 1)[None], one, causal, scale, seqused_k[b:b + 1], ns, precision,
+                                             window)
         out[start:end] = o[0].transpose(0, 1)
         lse[:, start:end] = l[0]
         if n:

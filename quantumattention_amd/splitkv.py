@@ -15,7 +15,7 @@ attends; both products run on the FP8 matrix pipe.  Package attributes, not name
 An appendable cache with FIXED scales is kvcache.KVCacheFP8 (kv_cache_append_fp8): a PreparedKV this entry attends
 unchanged.  A PAGED cache (a pool of pages behind a block table) is paged.PagedKVCacheFP8 with its own entry, fp8_attn_paged_func
 (DESIGN.md section 4.19): the bits of this entry on the gathered cache.  Not offered: scales that grow with the
-tensor, key smoothing on prepared keys, precision="auto", the 16-bit-P.V numerics, sliding windows, strided views."""
+tensor, key smoothing on prepared keys, precision="auto", the 16-bit-P.V numerics, strided views.  Sliding windows: splitkv_window.py."""
 import math
 from typing import Optional, Tuple
 
@@ -175,12 +175,29 @@ def split_plan(L: int, num_splits: int):
     return [(min(BLOCK_N * s * per, L), min(BLOCK_N * (s + 1) * per, L)) for s in range(num_splits)]
 
 
-def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision):
+def window_interval_lo(L: int, Sq: int, window_left: int) -> int:
+    """lo_i of include/qattn_splitkv_window.h: the first key any of Sq queries over L keys attends under window_left (-1: 0)."""
+    return 0 if window_left < 0 else min(max(L - Sq - window_left, 0), L)
+
+
+def split_plan_window(L: int, Sq: int, window_left: int, num_splits: int):
+    """`split_plan` under a sliding window: the splits cut the key blocks of the interval [lo, L), lo = window_interval_lo(L, Sq,
+    window_left), not those of [0, L): kb0 = lo // 128, nkb = ceil(L / 128) - kb0, per = ceil(nkb / ns); split s owns
+    [128 (kb0 + s per), 128 (kb0 + (s + 1) per)) cut at L.  window_left = -1: `split_plan`."""
+    kb0 = window_interval_lo(L, Sq, window_left) // BLOCK_N
+    nkb = _cdiv(L, BLOCK_N) - kb0
+    per = _cdiv(nkb, num_splits)
+    return [(min(BLOCK_N * (kb0 + s * per), L), min(BLOCK_N * (kb0 + (s + 1) * per), L)) for s in range(num_splits)]
+
+
+def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, window=None):
     """CPU tensors and config.attention.force_eager_fallback: the torch definition.  The eager quantiser on q (head-wise), the prepared
     row-major bytes de-quantised; per split an fp32 softmax partial (o_s, lse_s) over the split's keys of every batch element's first L_b
     keys -- a row without a key there: a zero row, LSE -inf --, then merge.merge_attn_states_eager.  The path bytes restate the kernel's
     rule per (kv head, 128-row tile of packed rows, split).  Returns (out, lse, partial_o, partial_lse, partial_path); with one split the
-    partials are empty.  (This path reads seqused_k on the host.)"""
+    partials are empty.  (This path reads seqused_k on the host.)
+    window = (left, right): the definition of the window entries (include/qattn_splitkv_window.h) -- `causal` is not read; the splits are
+    split_plan_window's, position p keeps the keys p + delta - left .. p + delta + right, and the path byte counts the keys klo .. khi."""
     fp8_dtype = _native.fp8_dtype_of(kv.fp8_format)
     B, Hq, Sq, D = q.shape
     _, Hkv, Skv, _ = kv.shape
@@ -200,17 +217,28 @@ def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision):
     for s in range(ns):
         keep = torch.zeros((B, 1, Sq, Skv), dtype=torch.bool, device=q.device)
         for b, L in enumerate(used):
-            lo, hi = split_plan(L, ns)[s]
+            lo, hi = split_plan(L, ns)[s] if window is None else split_plan_window(L, Sq, window[0], ns)[s]
             m = (key >= lo) & (key < hi)
-            if causal:
+            if window is not None:
+                if window[0] >= 0:
+                    m = m & (key >= pos + (L - Sq - window[0]))
+                if window[1] >= 0:
+                    m = m & (key <= pos + (L - Sq + window[1]))
+            elif causal:
                 m = m & (key <= pos + (L - Sq))
             keep[b, 0] = m.expand(Sq, Skv)
             # the kernel's path byte: per tile of the kv head's packed rows, by the keys the workgroup sweeps
             for t in range(ntile):
                 r0, r1 = t * TILE_M, min((t + 1) * TILE_M, G * Sq) - 1
                 smax = Sq - 1 if r0 // Sq != r1 // Sq else r1 % Sq
-                khi = min(hi - 1, smax + L - Sq) if causal else hi - 1
-                keys = max(khi - lo + 1, 0)
+                if window is not None:
+                    smin = 0 if r0 // Sq != r1 // Sq else r0 % Sq
+                    klo = max(lo, 0 if window[0] < 0 else max(smin + L - Sq - window[0], 0))
+                    khi = min(hi - 1, L - 1 if window[1] < 0 else smax + L - Sq + window[1])
+                    keys = max(khi - klo + 1, 0)
+                else:
+                    khi = min(hi - 1, smax + L - Sq) if causal else hi - 1
+                    keys = max(khi - lo + 1, 0)
                 code = _native.PATH_ONE_TERM if (keys == 0 or (precision == "fast" and keys >= TWO_TERM_KEYS)) else _native.PATH_TWO_TERM
                 path[s, b].view(Hkv, G * Sq)[:, r0:r1 + 1] = code
         sc = s_all.masked_fill(~keep, -math.inf)
