@@ -244,7 +244,9 @@ def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, window=None):
         sc = s_all.masked_fill(~keep, -math.inf)
         lse = torch.logsumexp(sc, dim=-1)
         p = torch.exp(sc - lse.clamp_min(torch.finfo(torch.float32).min)[..., None])   # (a row without keys: exp(-inf) = 0)
-        outs.append(p @ dv)
+        # a key no row of the split attends enters with V = 0, not with its bytes: 0 * NaN would make the row NaN, and bytes behind
+        # seqused_k or below a window influence no output bit (the kernels never load them)
+        outs.append(p @ dv.masked_fill(~keep.any(2)[..., None], 0))
         lses.append(lse)
     if ns == 1:
         e = lambda dt: torch.empty((0,), dtype=dt, device=q.device)
