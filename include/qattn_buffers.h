@@ -123,6 +123,15 @@
  *              workspace's size is not looked at); it holds whatever optional output is NULL, the pre-pass's abs-max words and, for ns > 8, the merge's fp32 accumulator; no
  *              result depends on what it held.
  *
+ * qattn_paged_kv_cache_append_varlen_fp8 (qattn_paged_varlen_append.h; held by tests/test_gpu_paged_varlen_append_buffer_contract.py): k_pool,
+ * v_pool, block_table, scale_k, scale_v and seqlens as qattn_paged_kv_cache_append_fp8 above (per sequence i), and
+ *   k16, v16   [total, Hkv, D] 16-bit through the element strides {token, head} of k_strides2 / v_strides2, head_dim innermost and dense;
+ *              base 16-byte aligned, both strides NON-NEGATIVE multiples of 8 elements.  Exactly `total` rows: the last row's last element
+ *              ends the buffer.  Read: the D elements of each (token, head) row of the tokens that are appended, no other byte -- not
+ *              the pads between rows or heads, not the rows behind cu_seqlens[B], not a dropped token's.
+ *   cu_seqlens  int32 [B + 1], 4-byte aligned; read, every extent clamped into [0, total].
+ *   No workspace.
+ *
  * qattn_fp8_attention_splitkv_window_forward, qattn_fp8_attention_paged_splitkv_window_forward and
  * qattn_fp8_attention_paged_varlen_window_forward (qattn_splitkv_window.h; held by tests/test_gpu_splitkv_window_buffer_contract.py): every
  * line of the sibling without a window -- qattn_fp8_attention_splitkv_forward, qattn_fp8_attention_paged_splitkv_forward,

@@ -51,8 +51,9 @@
  * total_q = 0 (after these checks, before the workspace's: none is needed): QATTN_OK, nothing launched, nothing written.
  * Buffers: include/qattn_buffers.h.
  *
- * Not offered: a packed [total, Hkv, D] append (qattn_paged_kv_cache_append_fp8 with new_lens serves a mixed step: pad the new keys to the
- * longest chunk), a per-call table whose batch differs from the scales' and lengths', the contiguous KVCacheFP8.  Sliding windows:
+ * The append half of the same step, on packed [total, Hkv, D] tokens under the same cu_seqlens: qattn_paged_kv_cache_append_varlen_fp8,
+ * include/qattn_paged_varlen_append.h (the padded qattn_paged_kv_cache_append_fp8 with new_lens leaves the same bytes).
+ * Not offered: a per-call table whose batch differs from the scales' and lengths', the contiguous KVCacheFP8.  Sliding windows:
  * qattn_fp8_attention_paged_varlen_window_forward, include/qattn_splitkv_window.h.
  */
 #ifndef QATTN_PAGED_VARLEN_H_

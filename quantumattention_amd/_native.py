@@ -57,6 +57,7 @@ EXPORTS = (
     "qattn_fp8_attention_paged_varlen_workspace_bytes", "qattn_paged_varlen_auto_splits", "qattn_fp8_attention_paged_varlen_forward",
     "qattn_splitkv_window_auto_splits", "qattn_paged_varlen_window_auto_splits", "qattn_fp8_attention_splitkv_window_forward",
     "qattn_fp8_attention_paged_splitkv_window_forward", "qattn_fp8_attention_paged_varlen_window_forward",
+    "qattn_paged_kv_cache_append_varlen_fp8",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -278,6 +279,10 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_attention_paged_varlen_window_forward.restype = i
     L.qattn_fp8_attention_paged_varlen_window_forward.argtypes = [vp, vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i,
                                                                   i, i, i, f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    # the paged append on packed tokens (include/qattn_paged_varlen_append.h): k16, v16, in_fmt, k_strides2, v_strides2, k_pool, v_pool, scale_k,
+    # scale_v, block_table, table_stride, seqlens, cu_seqlens, advance, B, Hkv, total, num_pages, page_size, max_pages, D, fp8_fmt, stream
+    L.qattn_paged_kv_cache_append_varlen_fp8.restype = i
+    L.qattn_paged_kv_cache_append_varlen_fp8.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, ll, vp, vp, i, i, i, i, i, i, i, i, i, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1321,6 +1326,38 @@ def paged_kv_cache_append_fp8(k_pool: torch.Tensor, v_pool: torch.Tensor, scale_
                                                seqlens.data_ptr(), _ptr(new_lens), int(bool(advance)), B, Hkv, T, num_pages, page_size, max_pages,
                                                D, fmt_of(fp8_dtype), _stream(k_new))
     _check(rc, "qattn_paged_kv_cache_append_fp8")
+
+
+def paged_kv_cache_append_varlen_fp8(k_pool: torch.Tensor, v_pool: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor,
+                                     block_table: torch.Tensor, seqlens: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
+                                     cu_seqlens: torch.Tensor, *, num_pages: int, page_size: int, fp8_dtype=torch.float8_e4m3fn,
+                                     advance: bool = True) -> None:
+    """qattn_paged_kv_cache_append_varlen_fp8 (include/qattn_paged_varlen_append.h): paged_kv_cache_append_fp8 on PACKED tokens k_new / v_new
+    [total, Hkv, D] (dense or views `paged_varlen_q_addressable` accepts, read in place), slot b owning the rows cu_seqlens[b] ..
+    cu_seqlens[b + 1] (int32 [B + 1]).  The table, seqlens and cu_seqlens are read on the device.  Mutates k_pool, v_pool and seqlens."""
+    _require(k_new.is_cuda and k_new.dim() == 3 and k_new.dtype in (torch.bfloat16, torch.float16), "k_new must be a 3-D bf16 / fp16 device tensor")
+    _require(v_new.shape == k_new.shape and v_new.dtype == k_new.dtype and v_new.device == k_new.device, "k_new and v_new must agree in shape, dtype and device")
+    total, Hkv, D = k_new.shape
+    if total == 0:
+        return
+    _require(paged_varlen_q_addressable(k_new) and paged_varlen_q_addressable(v_new), "k_new / v_new need head_dim innermost and 16-byte-aligned rows")
+    B = block_table.shape[0] if block_table.dim() == 2 else 0
+    L = lib()
+    dev = k_new.device
+    max_pages, tstride = _paged_pool_checks(L, k_pool, v_pool, block_table, scale_k, scale_v, dev, B, Hkv, num_pages, page_size, D)
+    _require(seqlens.dtype == torch.int32 and seqlens.device == dev and tuple(seqlens.shape) == (B,) and seqlens.is_contiguous(),
+             f"seqlens must be a dense int32 [B] tensor on {dev}")
+    _require(cu_seqlens.dtype == torch.int32 and cu_seqlens.device == dev and tuple(cu_seqlens.shape) == (B + 1,) and cu_seqlens.is_contiguous(),
+             f"cu_seqlens must be a dense int32 [B + 1] tensor on {dev}")
+    dense = (Hkv * D, D)     # (a dimension of size 1 has no stride of its own)
+    s2 = lambda t: (ctypes.c_longlong * 2)(*[t.stride(i) if t.shape[i] > 1 else dense[i] for i in (0, 1)])
+    with torch.cuda.device(dev):
+        rc = L.qattn_paged_kv_cache_append_varlen_fp8(k_new.data_ptr(), v_new.data_ptr(), fmt_of(k_new.dtype), s2(k_new), s2(v_new),
+                                                      k_pool.data_ptr(), v_pool.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(),
+                                                      block_table.data_ptr(), tstride, seqlens.data_ptr(), cu_seqlens.data_ptr(),
+                                                      int(bool(advance)), B, Hkv, total, num_pages, page_size, max_pages, D, fmt_of(fp8_dtype),
+                                                      _stream(k_new))
+    _check(rc, "qattn_paged_kv_cache_append_varlen_fp8")
 
 
 def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor,

@@ -29,6 +29,15 @@ struct KvPages {
     int num_pages, pc;  // pages of the pool; 64-key chunks per page
 };
 
+// PACKED tokens (include/qattn_paged_varlen_append.h): sequence i owns the rows clamp(cu[i], 0, total) .. clamp(cu[i + 1], that, total) of
+// x [total, Hkv, D]; NS = 2 B + total / 64 chunk slots per kv head (the kernel of qattn_paged_varlen_append.hip)
+struct KvVarq {
+    const int* cu;   // [B + 1]
+    int B, total, NS;
+};
+
+__device__ __forceinline__ int kv_clampi(int x, int lo, int hi) { return x < lo ? lo : x > hi ? hi : x; }
+
 // the appended keys of batch element b: [p, p + n) cut at the capacity
 __device__ __forceinline__ void kv_append_range(const int* seqlens, const int* new_lens, int b, int T, int capacity, int& p, int& end) {
     p = seqlens[b];
@@ -55,14 +64,18 @@ __device__ __forceinline__ bool has_nonfinite16(const uint4& raw) {
 template <int D, int IN_FMT, int OUT_FMT>
 __global__ __launch_bounds__(256) void kv_append_kernel(const KvAppendArgs a) {
 #define QATTN_KVA_PAGED 0
+#define QATTN_KVA_VARQ 0
 #include "qattn_kvcache_append_body.h"
+#undef QATTN_KVA_VARQ
 #undef QATTN_KVA_PAGED
 }
 
 template <int D, int IN_FMT, int OUT_FMT>
 __global__ __launch_bounds__(256) void kv_paged_append_kernel(const KvAppendArgs a, const KvPages pg) {
 #define QATTN_KVA_PAGED 1
+#define QATTN_KVA_VARQ 0
 #include "qattn_kvcache_append_body.h"
+#undef QATTN_KVA_VARQ
 #undef QATTN_KVA_PAGED
 }
 

@@ -3,7 +3,12 @@
 // statement for statement the kernel qattn_kvcache_append.hip held before the paged entry existed, so that its device code stays what it
 // was; 1, the pool through the block table `pg` (include/qattn_paged.h).  Shared as text, not as an inlined function, for the reason
 // qattn_splitkv_body.h gives.
-// In scope: template parameters D, IN_FMT, OUT_FMT; arguments a (KvAppendArgs) and -- paged -- pg (KvPages).
+// QATTN_KVA_VARQ (with QATTN_KVA_PAGED; include/qattn_paged_varlen_append.h) selects where the workgroup's TOKENS live: 0, the padded
+// [B, Hkv, T, D] tensors, new_lens[b] of sequence b's T rows used; 1, packed tensors [total, Hkv, D] cut by cu_seqlens (`vq`, KvVarq): the
+// workgroup finds its (sequence, chunk) by a binary search on the chunk-slot bases 2 i + start_i / 64 -- the search QATTN_SKV_VARQ runs on
+// its tile slots (qattn_splitkv_body.h) -- and the sequence's count end_i - start_i stands where the padded kernels clamp new_lens[b].
+// With the switch off the text the compiler sees is what it was.
+// In scope: template parameters D, IN_FMT, OUT_FMT; arguments a (KvAppendArgs), -- paged -- pg (KvPages) and -- packed -- vq (KvVarq).
     constexpr int VPR = D / 8;             // 16-byte input vectors per row
     constexpr int ITERS = 64 * VPR / 256;  // vectors per thread
     constexpr int KPAD = 64 * D + (64 * D / 512) * 16;  // KFRAG image + 16 B per 512 B     (the staging images of quant_multi_kernel)
@@ -11,17 +16,43 @@
     constexpr int LDS_BYTES = KPAD > 64 * VSTRIDE ? KPAD : 64 * VSTRIDE;
     __shared__ __attribute__((aligned(16))) unsigned char img[LDS_BYTES];
     const int tid = threadIdx.x, z = blockIdx.y;
+#if QATTN_KVA_VARQ
+    // blockIdx.x = h NS + j: chunk slot j of kv head h.  Slot j belongs to the largest sequence i with base_i = 2 i + start_i / 64 <= j, as
+    // the chunk j - base_i counted from the one that holds key p_i; base_{i+1} - base_i >= n_i / 64 + 2, the most chunks n_i keys touch
+    const int h = (int)(blockIdx.x / (unsigned)vq.NS), jt = (int)(blockIdx.x % (unsigned)vq.NS);
+    int b = 0, b_hi = vq.B - 1;
+    while (b < b_hi) {   // (workgroup-uniform)
+        const int mid = (b + b_hi + 1) >> 1;
+        const int sm = kv_clampi(__builtin_amdgcn_readfirstlane(vq.cu[mid]), 0, vq.total);
+        if (2 * mid + sm / 64 <= jt) b = mid;
+        else b_hi = mid - 1;
+    }
+    const int start = kv_clampi(__builtin_amdgcn_readfirstlane(vq.cu[b]), 0, vq.total);
+    const int n = kv_clampi(__builtin_amdgcn_readfirstlane(vq.cu[b + 1]), start, vq.total) - start;
+    const int ci = jt - (2 * b + start / 64);
+    if (ci < 0 || ci > n / 64 + 1) return;   // a slot that is no chunk of its sequence: before any other memory is touched
+    const int g = b * a.Hkv + h;
+    int p = a.seqlens[b];
+    p = p < 0 ? 0 : p > a.capacity ? a.capacity : p;
+    const int end = a.capacity - p >= n ? p + n : a.capacity;   // (kv_append_range on the sequence's own count)
+#else
     const int g = (int)(blockIdx.x / (unsigned)a.nchunk), ci = (int)(blockIdx.x % (unsigned)a.nchunk);
     const int b = g / a.Hkv, h = g % a.Hkv;
     int p, end;
     kv_append_range(a.seqlens, a.new_lens, b, a.T, a.capacity, p, end);
+#endif
     const long key0 = 64L * (p / 64 + ci);   // first key of this workgroup's chunk
     if (p >= end || key0 >= end) return;     // (workgroup-uniform: nothing is appended -- new_lens 0, a full cache -- or nothing of this chunk)
     // the chunk's keys [lo, hi) are the tokens [key0 + lo - p, key0 + hi - p) of the call
     const int lo = p > key0 ? (int)(p - key0) : 0, hi = end - key0 < 64 ? (int)(end - key0) : 64;
     const float scale = a.scale[z][g];
     const float rinv = 1.0f / scale;
+#if QATTN_KVA_VARQ
+    // key p + t is token start + t < start + n <= total: the rows [lo, hi) of the chunk are rows of the sequence's own tokens
+    const uint4* xg = a.x[z] + (long)h * a.sh[z] + ((long)start + key0 - p) * a.st[z];   // row of chunk key 0 (not touched below lo)
+#else
     const uint4* xg = a.x[z] + (long)b * a.sb[z] + (long)h * a.sh[z] + (key0 - p) * a.st[z];   // row of chunk key 0 (not touched below lo)
+#endif
     const long st = a.st[z];
     uint4 held[ITERS];
 #pragma unroll

@@ -633,6 +633,35 @@ def _(k_pool, v_pool, scale_k, scale_v, block_table, seqlens, k_new, v_new, new_
     return None
 
 
+@_custom_op("quantumattention_amd::fp8_paged_varlen_kv_cache_append_", mutates_args=("k_pool", "v_pool", "seqlens"), device_types=("cuda",))
+def fp8_paged_varlen_kv_cache_append_(
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens: torch.Tensor,
+    k_new: torch.Tensor,
+    v_new: torch.Tensor,
+    cu_seqlens: torch.Tensor,
+    num_pages: int,
+    page_size: int,
+    fp8_format: str = "e4m3",
+    advance: bool = True,
+) -> None:
+    """Append PACKED tokens to a paged FP8 K/V cache IN PLACE (include/qattn_paged_varlen_append.h): fp8_paged_kv_cache_append_ on k_new /
+    v_new [total, Hkv, D], slot b owning the rows cu_seqlens[b] .. cu_seqlens[b + 1] (int32 [B + 1], read on the device).
+    Reference implementation: paged_varlen._append_varlen_eager.  Arguments are validated by paged_varlen.paged_kv_cache_append_varlen_fp8."""
+    _native.paged_kv_cache_append_varlen_fp8(k_pool, v_pool, scale_k, scale_v, block_table, seqlens, k_new, v_new, cu_seqlens,
+                                             num_pages=num_pages, page_size=page_size, fp8_dtype=_native.fp8_dtype_of(fp8_format),
+                                             advance=advance)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_varlen_kv_cache_append_")
+def _(k_pool, v_pool, scale_k, scale_v, block_table, seqlens, k_new, v_new, cu_seqlens, num_pages, page_size, fp8_format="e4m3", advance=True):
+    return None
+
+
 @_custom_op("quantumattention_amd::fp8_paged_varlen_splitkv_attention_forward", mutates_args=(), device_types=("cuda",))
 def fp8_paged_varlen_splitkv_attention_forward(
     query: torch.Tensor,

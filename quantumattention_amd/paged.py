@@ -21,7 +21,8 @@ sequences that append into the same page in one call have two writers: undefined
 
 Package attributes, not names of `__all__` (that list mirrors the reference).  Not offered: page allocation, copy-on-write, re-scaling,
 a per-call table whose batch differs from the cache's slots.  Sliding windows: splitkv_window.fp8_attn_paged_window_func.  Queries of a different count per sequence slot (packed
-[total_q, Hq, D] under cu_seqlens_q): `fp8_attn_paged_varlen_func`, paged_varlen.py."""
+[total_q, Hq, D] under cu_seqlens_q): `fp8_attn_paged_varlen_func`, and the append of packed [total, Hkv, D] tokens under the same
+cu_seqlens: `paged_kv_cache_append_varlen_fp8`, both paged_varlen.py."""
 import math
 from typing import Optional, Tuple
 

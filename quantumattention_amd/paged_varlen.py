@@ -11,9 +11,17 @@ in chunked prefill with hundreds of queries, many decode one token (or a few spe
 
 The rule: for every slot with queries, the rows of every output are, bit for bit, those of `fp8_attn_paged_func` on that slot alone.
 
-A package attribute, not a name of `__all__`.  Not offered: a packed [total, Hkv, D] append (the padded
-`paged_kv_cache_append_fp8(..., new_lens=)` serves a mixed step), a per-call table whose batch differs from the cache's
-slots, the contiguous `KVCacheFP8`.  Sliding windows: splitkv_window.fp8_attn_paged_varlen_window_func."""
+The append half of the same step, on the same packed tensor and the same cu_seqlens: `paged_kv_cache_append_varlen_fp8`
+(include/qattn_paged_varlen_append.h) -- the K and V slices of the QKV projection go into the cache as they are,
+no padding to the longest chunk, no new_lens beside cu_seqlens.
+
+    qkv = proj(x).view(total, Hq + 2 * Hkv, D)
+    paged_kv_cache_append_varlen_fp8(cache, qkv[:, Hq:Hq + Hkv], qkv[:, Hq + Hkv:], cu)
+    out = fp8_attn_paged_varlen_func(qkv[:, :Hq], cache, cu, max_seqlen_q, causal=True, max_seqlen_k=longest_live_sequence)
+
+Package attributes, not names of `__all__`.  Not offered: rotary embedding of K inside the append, a per-token slot_mapping form, a
+per-call table whose batch differs from the cache's slots, the contiguous `KVCacheFP8`, page allocation.  Sliding windows:
+splitkv_window.fp8_attn_paged_varlen_window_func."""
 import math
 from typing import Optional, Tuple
 
@@ -22,7 +30,7 @@ from torch import Tensor
 
 from . import _native, nn
 from .kvcache import _is_int
-from .paged import PagedKVCacheFP8, _cache_reason, _lens_reason, gather_paged_eager
+from .paged import PagedKVCacheFP8, _append_eager, _cache_reason, _lens_reason, gather_paged_eager
 from .splitkv import _CPU_NUM_CUS, MAX_SPLITS, PreparedKV, _splitkv_eager
 from .utils import checks
 
@@ -184,3 +192,102 @@ def fp8_attn_paged_varlen_func(q, cache: PagedKVCacheFP8, cu_seqlens_q: Tensor, 
     if return_partials:
         res += (po, plse, ppath)
     return res if len(res) > 1 else out
+
+
+def paged_varlen_append_input_reason(cache, k_new, v_new, cu_seqlens) -> Optional[str]:
+    """The first rule the arguments of `paged_kv_cache_append_varlen_fp8` break, or None.  Shapes, dtypes, devices and strides only: the
+    CONTENTS of cu_seqlens, cache.seqlens and the block table are read on the device."""
+    reason = _cache_reason(cache)
+    if reason:
+        return reason
+    if not isinstance(k_new, Tensor) or not isinstance(v_new, Tensor) or k_new.dim() != 3 or v_new.dim() != 3:
+        return "NYI: k_new and v_new must be 3-D tensors [total, Hkv, head_dim]"
+    if k_new.requires_grad or v_new.requires_grad:
+        return "NYI: k_new and v_new must be leaf tensors (no backward)"
+    if k_new.dtype != cache.dtype or v_new.dtype != cache.dtype:
+        return f"Expected k_new and v_new to have the cache's dtype {cache.dtype}, but got {k_new.dtype} and {v_new.dtype} instead."
+    B = cache.batch_size
+    _, Hkv, _, D = cache.shape
+    if k_new.shape != v_new.shape:
+        return f"Expect k_new and v_new to have the same shape but got {tuple(k_new.shape)} and {tuple(v_new.shape)}."
+    if tuple(k_new.shape[1:]) != (Hkv, D):
+        return f"Expected k_new and v_new to have shape [total, {Hkv}, {D}], but got {list(k_new.shape)}."
+    if (2 * B + k_new.shape[0] // 64) * Hkv > 2 ** 31 - 1:
+        return f"(2 * batch_size + total // 64) * Hkv must stay below 2^31 (the grid), got {(2 * B + k_new.shape[0] // 64) * Hkv}"
+    if k_new.device != cache.device or v_new.device != cache.device:
+        return f"Expected k_new and v_new to be on the cache's device {cache.device}, but got {k_new.device} and {v_new.device} instead."
+    for name, t in (("k_new", k_new), ("v_new", v_new)):
+        if t.shape[0] > 0 and not _q_rows_addressable(t):
+            return (f"Expected {name} to have head_dim innermost and 16-byte-aligned rows (strides that are multiples of 8 elements), but got "
+                    f"strides {tuple(t.stride())} at storage offset {t.storage_offset()}; pass {name}.contiguous()")
+    if not isinstance(cu_seqlens, Tensor) or cu_seqlens.dtype != torch.int32:
+        return f"Expected cu_seqlens to be a torch.int32 tensor, but got {getattr(cu_seqlens, 'dtype', type(cu_seqlens))}"
+    if tuple(cu_seqlens.shape) != (B + 1,):
+        return f"Expected cu_seqlens to have shape [{B + 1}] (the cache's slots + 1), but got {list(cu_seqlens.shape)}."
+    if cu_seqlens.device != cache.device:
+        return f"Expected cu_seqlens to be on {cache.device}, but got {cu_seqlens.device} instead."
+    if not cu_seqlens.is_contiguous():
+        return "Expected cu_seqlens to be contiguous"
+    return _lens_reason("cache.seqlens", cache.seqlens, B, cache.device)
+
+
+def _append_varlen_eager(cache: PagedKVCacheFP8, k_new: Tensor, v_new: Tensor, cu_seqlens: Tensor, advance: bool) -> None:
+    """CPU tensors and config.attention.force_eager_fallback: the torch definition on row-major fp8 pools -- paged._append_eager on each
+    slot's own rows of the packed tokens, the counts taken from cu_seqlens.  (This path reads cu_seqlens, seqlens and the table on the
+    host.)"""
+    total, Hkv, D = k_new.shape
+    B = cache.batch_size
+    cu = cu_seqlens.tolist()
+    start = [min(max(int(cu[b]), 0), total) for b in range(B)]
+    cnt = [min(max(int(cu[b + 1]), start[b]), total) - start[b] for b in range(B)]
+    T = max(max(cnt), 1)
+    # the padded tokens of the rule: slot b's rows, then zeros that new_lens keeps out of the cache
+    pad = lambda x: torch.stack([torch.cat([x[start[b]:start[b] + cnt[b]], x.new_zeros((T - cnt[b], Hkv, D))]).transpose(0, 1)
+                                 for b in range(B)])
+    _append_eager(cache, pad(k_new), pad(v_new), torch.tensor(cnt, dtype=torch.int32), advance)
+
+
+def paged_kv_cache_append_varlen_fp8(cache: PagedKVCacheFP8, k_new: Tensor, v_new: Tensor, cu_seqlens: Tensor, *,
+                                     advance: bool = True) -> PagedKVCacheFP8:
+    """`paged_kv_cache_append_fp8` for PACKED tokens, a different count per sequence slot; in place, returns `cache`.
+
+    k_new, v_new [total, Hkv, D] in cache.dtype, read through their strides: head_dim innermost, token and head strides non-negative
+    multiples of 8 elements, the base 16-byte aligned -- the K and V slices of a packed QKV projection go in as they are.  cu_seqlens:
+    int32 [cache.batch_size + 1] on the device, the tensor `fp8_attn_paged_varlen_func` takes as cu_seqlens_q; slot b owns the tokens
+    start_b = clamp(cu[b], 0, total) .. clamp(cu[b + 1], start_b, total), n_b of them (0: an idle slot).  With p_b = clamp(seqlens[b], 0,
+    capacity), token start_b + t becomes key p_b + t of slot b; tokens at or beyond the capacity are dropped; seqlens[b] becomes
+    min(p_b + n_b, capacity) unless advance=False.
+    The rule: pools and seqlens end, byte for byte, as `paged_kv_cache_append_fp8(cache, pad(k_new), pad(v_new), new_lens=n)` leaves
+    them (the same quantiser bytes, saturation, NaN handling, store schemes, table entries read and clamped); exactly the bytes of the
+    appended keys change.  Rows behind cu[B] (a padded token bucket) are not read.  A cu_seqlens that is not non-decreasing gives
+    unspecified pool contents in the slots concerned, and nothing worse.  Two slots that append into one page: undefined.
+    Everything is read on the device: no host synchronisation, no allocation, graph-capture safe, and a captured call follows the later
+    contents of cu_seqlens, seqlens and the table.  total = 0 returns at once.  CPU tensors and config.attention.force_eager_fallback run
+    the eager definition (`_append_varlen_eager`); on the device there is no fallback.  Invalid input raises ValueError(reason)."""
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = paged_varlen_append_input_reason(cache, k_new, v_new, cu_seqlens)
+        if reason:
+            raise ValueError(reason)
+    if k_new.shape[0] == 0:
+        return cache
+    eager = (not k_new.is_cuda or checks.config_value("attention.force_eager_fallback")) and not torch.compiler.is_dynamo_compiling()
+    if eager:
+        if cache.layout != "rowmajor":
+            raise ValueError("the eager definition needs a cache made on a CPU device or under config.attention.force_eager_fallback")
+        _append_varlen_eager(cache, k_new, v_new, cu_seqlens, bool(advance))
+        return cache
+    if cache.layout != "frag":
+        raise ValueError("this cache holds row-major bytes for the eager definition; make it on the device without "
+                         "config.attention.force_eager_fallback")
+    ok, why = nn._pre_check_can_use_hip_attention(device=k_new.device)
+    if not ok:
+        raise ValueError(why)
+    if torch.compiler.is_compiling():
+        nn._ops().fp8_paged_varlen_kv_cache_append_(cache.k, cache.v, cache.scale_k, cache.scale_v, cache.block_table, cache.seqlens, k_new, v_new,
+                                                    cu_seqlens, cache.num_pages, cache.page_size, cache.fp8_format, bool(advance))
+    else:
+        # outside a trace: the op's own body, without the dispatcher's bookkeeping for a mutating op (as paged_kv_cache_append_fp8)
+        _native.paged_kv_cache_append_varlen_fp8(cache.k, cache.v, cache.scale_k, cache.scale_v, cache.block_table, cache.seqlens, k_new, v_new,
+                                                 cu_seqlens, num_pages=cache.num_pages, page_size=cache.page_size,
+                                                 fp8_dtype=_native.fp8_dtype_of(cache.fp8_format), advance=bool(advance))
+    return cache
