@@ -132,6 +132,17 @@
  *   cu_seqlens  int32 [B + 1], 4-byte aligned; read, every extent clamped into [0, total].
  *   No workspace.
  *
+ * qattn_paged_kv_cache_append_varlen_rope_fp8 and qattn_rope_paged_varlen (qattn_paged_varlen_rope.h; held by
+ * tests/test_gpu_paged_varlen_rope_buffer_contract.py): no workspace.  The append: every line of qattn_paged_kv_cache_append_varlen_fp8
+ * above -- the same bytes of k_pool and v_pool are written, those of the appended keys and no other, and seqlens with advance -- and
+ *   cos, sin   fp32 [T, D/2] through table_row_stride floats (a non-negative multiple of 4), both bases 16-byte aligned.  Exactly T rows: the
+ *              last row's last float ends the buffer.  Read: the D/2 floats of the rows min(p_i + t, T - 1) of the appended keys, no other
+ *              byte -- not the pads between rows of a sliced table, not a row no appended key uses.
+ * The rotation: x16 [total, H, D] as k16 above (exactly `total` rows; read: the rows a sequence owns, not those behind cu_seqlens[B]);
+ * cos, sin as above (read: the rows min(max(base_i, 0) + t, T - 1)); cu_seqlens int32 [B + 1] and seqlens int32 [B], 4-byte aligned, read;
+ *   out16      dense [total, H, D] in x16's dtype, 2 total H D bytes, 16-byte aligned.  Written: every element of the rows a sequence
+ *              owns; the rows behind cu_seqlens[B] are not written.
+ *
  * qattn_fp8_attention_splitkv_window_forward, qattn_fp8_attention_paged_splitkv_window_forward and
  * qattn_fp8_attention_paged_varlen_window_forward (qattn_splitkv_window.h; held by tests/test_gpu_splitkv_window_buffer_contract.py): every
  * line of the sibling without a window -- qattn_fp8_attention_splitkv_forward, qattn_fp8_attention_paged_splitkv_forward,

@@ -51,8 +51,9 @@
  * NULL or not 4-byte aligned; total < 0; the grid Hkv NS above 2^31 - 1.  total = 0 (after these checks): QATTN_OK, nothing launched,
  * nothing written.  Buffers: as listed above; no workspace.
  *
- * Not offered: rotary embedding of K inside the append (the kernel knows each key's position p_i + t: the obvious follow-up), a
- * per-token slot_mapping form, the contiguous KVCacheFP8, page allocation.
+ * Rotary embedding of K inside the append: the sibling qattn_paged_kv_cache_append_varlen_rope_fp8 (include/qattn_paged_varlen_rope.h), this
+ * entry's body compiled once more with the rotation between its load and its quantiser.
+ * Not offered: a per-token slot_mapping form, the contiguous KVCacheFP8, page allocation.
  */
 #ifndef QATTN_PAGED_VARLEN_APPEND_H_
 #define QATTN_PAGED_VARLEN_APPEND_H_

@@ -51,6 +51,9 @@ from .paged import PagedKVCacheFP8, alloc_paged_kv_cache_fp8, fp8_attn_paged_fun
 from .paged_varlen import fp8_attn_paged_varlen_func  # noqa: E402
 # ... and the append of PACKED tokens under the same cu_seqlens (include/qattn_paged_varlen_append.h): a package attribute, not in __all__
 from .paged_varlen import paged_kv_cache_append_varlen_fp8  # noqa: E402
+# ... and the same with the rotary embedding of K inside the append, and q's packed rotation at the same positions
+# (include/qattn_paged_varlen_rope.h): package attributes, not in __all__
+from .paged_varlen import apply_rope_paged_varlen, paged_kv_cache_append_varlen_rope_fp8  # noqa: E402
 # sliding windows for the split-KV, paged and packed-paged entries (include/qattn_splitkv_window.h): package attributes, not in __all__
 from .splitkv_window import (  # noqa: E402
     fp8_attn_paged_varlen_window_func,

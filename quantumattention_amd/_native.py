@@ -58,6 +58,7 @@ EXPORTS = (
     "qattn_splitkv_window_auto_splits", "qattn_paged_varlen_window_auto_splits", "qattn_fp8_attention_splitkv_window_forward",
     "qattn_fp8_attention_paged_splitkv_window_forward", "qattn_fp8_attention_paged_varlen_window_forward",
     "qattn_paged_kv_cache_append_varlen_fp8",
+    "qattn_paged_kv_cache_append_varlen_rope_fp8", "qattn_rope_paged_varlen",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -283,6 +284,14 @@ def lib() -> ctypes.CDLL:
     # scale_v, block_table, table_stride, seqlens, cu_seqlens, advance, B, Hkv, total, num_pages, page_size, max_pages, D, fp8_fmt, stream
     L.qattn_paged_kv_cache_append_varlen_fp8.restype = i
     L.qattn_paged_kv_cache_append_varlen_fp8.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, ll, vp, vp, i, i, i, i, i, i, i, i, i, vp]
+    # the same with K rotated inside it (include/qattn_paged_varlen_rope.h): ..., fp8_fmt, cos, sin, table_row_stride, T, interleaved, stream
+    L.qattn_paged_kv_cache_append_varlen_rope_fp8.restype = i
+    L.qattn_paged_kv_cache_append_varlen_rope_fp8.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, ll, vp, vp, i, i, i, i, i, i, i, i, i, vp, vp,
+                                                              ll, i, i, vp]
+    # packed rows rotated at the cache's positions: x16, in_fmt, x_strides2, out16, cu_seqlens, seqlens, appended, B, H, total, capacity, D, cos,
+    # sin, table_row_stride, T, interleaved, stream
+    L.qattn_rope_paged_varlen.restype = i
+    L.qattn_rope_paged_varlen.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, i, ll, i, vp, vp, ll, i, i, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1358,6 +1367,83 @@ def paged_kv_cache_append_varlen_fp8(k_pool: torch.Tensor, v_pool: torch.Tensor,
                                                       int(bool(advance)), B, Hkv, total, num_pages, page_size, max_pages, D, fmt_of(fp8_dtype),
                                                       _stream(k_new))
     _check(rc, "qattn_paged_kv_cache_append_varlen_fp8")
+
+
+def _paged_rope_tables(cos: torch.Tensor, sin: torch.Tensor, dev, D: int):
+    """cos / sin fp32 [T, D/2] as include/qattn_paged_varlen_rope.h takes them: (T, row stride in floats).  Read in place: no copy is made."""
+    for name, t in (("cos", cos), ("sin", sin)):
+        _require(t.dtype == torch.float32 and t.device == dev and t.dim() == 2 and t.shape[0] >= 1 and t.shape[1] == D // 2,
+                 f"{name} must be a float32 [T, D/2 = {D // 2}] tensor on {dev}")
+        _require(t.stride(1) == 1 and t.data_ptr() % 16 == 0 and (t.shape[0] == 1 or (t.stride(0) >= 0 and t.stride(0) % 4 == 0)),
+                 f"{name} needs dense rows, a 16-byte-aligned base and a row stride that is a non-negative multiple of 4 floats")
+    _require(cos.shape == sin.shape and (cos.shape[0] == 1 or cos.stride(0) == sin.stride(0)), "cos and sin must share shape and row stride")
+    return cos.shape[0], (cos.stride(0) if cos.shape[0] > 1 else D // 2)
+
+
+def paged_kv_cache_append_varlen_rope_fp8(k_pool: torch.Tensor, v_pool: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor,
+                                          block_table: torch.Tensor, seqlens: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
+                                          cu_seqlens: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, *, num_pages: int, page_size: int,
+                                          fp8_dtype=torch.float8_e4m3fn, interleaved: bool = False, advance: bool = True) -> None:
+    """qattn_paged_kv_cache_append_varlen_rope_fp8 (include/qattn_paged_varlen_rope.h): paged_kv_cache_append_varlen_fp8 with key p + t of a
+    slot rotated with row min(p + t, T - 1) of cos / sin (fp32 [T, D/2], read in place) before it is quantised.  Any T >= 1 is taken: the
+    capacity rule is the Python entry's.  Mutates k_pool, v_pool and seqlens."""
+    _require(k_new.is_cuda and k_new.dim() == 3 and k_new.dtype in (torch.bfloat16, torch.float16), "k_new must be a 3-D bf16 / fp16 device tensor")
+    _require(v_new.shape == k_new.shape and v_new.dtype == k_new.dtype and v_new.device == k_new.device, "k_new and v_new must agree in shape, dtype and device")
+    total, Hkv, D = k_new.shape
+    if total == 0:
+        return
+    _require(paged_varlen_q_addressable(k_new) and paged_varlen_q_addressable(v_new), "k_new / v_new need head_dim innermost and 16-byte-aligned rows")
+    B = block_table.shape[0] if block_table.dim() == 2 else 0
+    L = lib()
+    dev = k_new.device
+    max_pages, tstride = _paged_pool_checks(L, k_pool, v_pool, block_table, scale_k, scale_v, dev, B, Hkv, num_pages, page_size, D)
+    _require(seqlens.dtype == torch.int32 and seqlens.device == dev and tuple(seqlens.shape) == (B,) and seqlens.is_contiguous(),
+             f"seqlens must be a dense int32 [B] tensor on {dev}")
+    _require(cu_seqlens.dtype == torch.int32 and cu_seqlens.device == dev and tuple(cu_seqlens.shape) == (B + 1,) and cu_seqlens.is_contiguous(),
+             f"cu_seqlens must be a dense int32 [B + 1] tensor on {dev}")
+    T, tr = _paged_rope_tables(cos, sin, dev, D)
+    dense = (Hkv * D, D)     # (a dimension of size 1 has no stride of its own)
+    s2 = lambda t: (ctypes.c_longlong * 2)(*[t.stride(i) if t.shape[i] > 1 else dense[i] for i in (0, 1)])
+    with torch.cuda.device(dev):
+        rc = L.qattn_paged_kv_cache_append_varlen_rope_fp8(k_new.data_ptr(), v_new.data_ptr(), fmt_of(k_new.dtype), s2(k_new), s2(v_new),
+                                                           k_pool.data_ptr(), v_pool.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(),
+                                                           block_table.data_ptr(), tstride, seqlens.data_ptr(), cu_seqlens.data_ptr(),
+                                                           int(bool(advance)), B, Hkv, total, num_pages, page_size, max_pages, D,
+                                                           fmt_of(fp8_dtype), cos.data_ptr(), sin.data_ptr(), tr, T, int(bool(interleaved)),
+                                                           _stream(k_new))
+    _check(rc, "qattn_paged_kv_cache_append_varlen_rope_fp8")
+
+
+def rope_paged_varlen(x: torch.Tensor, seqlens: torch.Tensor, cu_seqlens: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, *, capacity: int,
+                      interleaved: bool = False, appended: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qattn_rope_paged_varlen (include/qattn_paged_varlen_rope.h): packed rows x [total, H, D] (dense or a view `paged_varlen_q_addressable`
+    accepts, read in place) rotated at the positions of a paged cache's slots -> dense [total, H, D] (`out`, or a new tensor).  seqlens
+    int32 [B], cu_seqlens int32 [B + 1] and the tables are read on the device."""
+    _require(x.is_cuda and x.dim() == 3 and x.dtype in (torch.bfloat16, torch.float16), "x must be a 3-D bf16 / fp16 device tensor")
+    total, H, D = x.shape
+    dev = x.device
+    if out is None:
+        with torch.cuda.device(dev):
+            out = torch.empty((total, H, D), dtype=x.dtype, device=dev)
+    _require(out.shape == x.shape and out.dtype == x.dtype and out.device == dev and out.is_contiguous() and out.data_ptr() % 16 == 0,
+             "out must be a dense, 16-byte-aligned tensor of x's shape, dtype and device")
+    if total == 0:
+        return out
+    _require(H > 0 and paged_varlen_q_addressable(x), "x needs head_dim innermost and 16-byte-aligned rows")
+    B = seqlens.shape[0] if seqlens.dim() == 1 else 0
+    _require(B > 0 and seqlens.dtype == torch.int32 and seqlens.device == dev and seqlens.is_contiguous(), f"seqlens must be a dense int32 [B] tensor on {dev}")
+    _require(cu_seqlens.dtype == torch.int32 and cu_seqlens.device == dev and tuple(cu_seqlens.shape) == (B + 1,) and cu_seqlens.is_contiguous(),
+             f"cu_seqlens must be a dense int32 [B + 1] tensor on {dev}")
+    _require(isinstance(capacity, int) and capacity >= 1, f"capacity must be a positive integer, got {capacity!r}")
+    T, tr = _paged_rope_tables(cos, sin, dev, D)
+    dense = (H * D, D)     # (a dimension of size 1 has no stride of its own)
+    s2 = (ctypes.c_longlong * 2)(*[x.stride(i) if x.shape[i] > 1 else dense[i] for i in (0, 1)])
+    with torch.cuda.device(dev):
+        rc = lib().qattn_rope_paged_varlen(x.data_ptr(), fmt_of(x.dtype), s2, out.data_ptr(), cu_seqlens.data_ptr(), seqlens.data_ptr(),
+                                           int(bool(appended)), B, H, total, capacity, D, cos.data_ptr(), sin.data_ptr(), tr, T,
+                                           int(bool(interleaved)), _stream(x))
+    _check(rc, "qattn_rope_paged_varlen")
+    return out
 
 
 def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor,

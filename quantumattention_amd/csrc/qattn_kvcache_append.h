@@ -36,6 +36,14 @@ struct KvVarq {
     int B, total, NS;
 };
 
+// ROTATED keys (include/qattn_paged_varlen_rope.h): key j of every slot rotates with row min(j, T - 1) of cos / sin [T, D/2] fp32
+struct KvRope {
+    const float* cs;
+    const float* sn;
+    long tr;   // floats between table rows (a multiple of 4)
+    int T;
+};
+
 __device__ __forceinline__ int kv_clampi(int x, int lo, int hi) { return x < lo ? lo : x > hi ? hi : x; }
 
 // the appended keys of batch element b: [p, p + n) cut at the capacity
@@ -65,7 +73,9 @@ template <int D, int IN_FMT, int OUT_FMT>
 __global__ __launch_bounds__(256) void kv_append_kernel(const KvAppendArgs a) {
 #define QATTN_KVA_PAGED 0
 #define QATTN_KVA_VARQ 0
+#define QATTN_KVA_ROPE 0
 #include "qattn_kvcache_append_body.h"
+#undef QATTN_KVA_ROPE
 #undef QATTN_KVA_VARQ
 #undef QATTN_KVA_PAGED
 }
@@ -74,13 +84,60 @@ template <int D, int IN_FMT, int OUT_FMT>
 __global__ __launch_bounds__(256) void kv_paged_append_kernel(const KvAppendArgs a, const KvPages pg) {
 #define QATTN_KVA_PAGED 1
 #define QATTN_KVA_VARQ 0
+#define QATTN_KVA_ROPE 0
 #include "qattn_kvcache_append_body.h"
+#undef QATTN_KVA_ROPE
 #undef QATTN_KVA_VARQ
 #undef QATTN_KVA_PAGED
 }
 
 // kv_advance_kernel's launch (qattn_kvcache_append.hip): the second launch of an advancing call
 void kv_launch_advance(int* seqlens, const int* new_lens, int B, int T, int capacity, hipStream_t st);
+
+// kv_varlen_advance_kernel's launch (qattn_paged_varlen_append.hip): the second launch of an advancing packed call
+void kv_launch_varlen_advance(int* seqlens, const int* cu, int B, int total, int capacity, hipStream_t st);
+
+// The argument checks of the packed append (include/qattn_paged_varlen_append.h) and its argument structs, shared by its entries
+// (qattn_paged_varlen_append.hip, qattn_paged_varlen_rope_append.hip).  QATTN_OK with total = 0: nothing is to be launched.
+inline int kv_varlen_append_args(const void* k16, const void* v16, int in_fmt, const long long* k_strides2, const long long* v_strides2,
+                                 void* k_pool, void* v_pool, const float* scale_k, const float* scale_v, const int* block_table,
+                                 long long table_stride, int* seqlens, const int* cu_seqlens, int B, int Hkv, int total, int num_pages,
+                                 int page_size, int max_pages, int D, int fp8_fmt, KvAppendArgs& a, KvPages& pg, KvVarq& vq) {
+    // the paging arguments, as qattn_paged_kv_cache_append_fp8 checks them
+    if (!block_table || (size_t)block_table % 4 != 0) return QATTN_ERR_INVALID_ARG;
+    if (num_pages <= 0 || max_pages <= 0 || Hkv <= 0 || page_size < 64 || page_size % 64 != 0) return QATTN_ERR_INVALID_ARG;
+    if (table_stride < max_pages) return QATTN_ERR_INVALID_ARG;
+    const int pc = page_size / 64;
+    if ((long long)num_pages * Hkv * pc > 0x7fffffffLL) return QATTN_ERR_INVALID_ARG;   // (the physical chunk index is an int)
+    const long long capacity = (long long)max_pages * page_size;
+    if (capacity > 0x7fffffffLL - 64) return QATTN_ERR_INVALID_ARG;   // (p_i + n_i stays in 32 bits)
+    // the packed arguments
+    if (!cu_seqlens || (size_t)cu_seqlens % 4 != 0) return QATTN_ERR_INVALID_ARG;
+    if (total < 0) return QATTN_ERR_INVALID_ARG;
+    // kv_append's checks (qattn_kvcache_append.h), T > 0 excepted
+    if (!k16 || !v16 || !k_strides2 || !v_strides2 || !k_pool || !v_pool || !scale_k || !scale_v || !seqlens) return QATTN_ERR_INVALID_ARG;
+    if (B <= 0 || D <= 0) return QATTN_ERR_INVALID_ARG;
+    if (D != 64 && D != 128 && D != 256) return QATTN_ERR_UNSUPPORTED_DIM;
+    if (in_fmt != QATTN_FMT_BF16 && in_fmt != QATTN_FMT_FP16) return QATTN_ERR_UNSUPPORTED_FMT;
+    if (fp8_fmt != QATTN_FMT_E4M3 && fp8_fmt != QATTN_FMT_E5M2) return QATTN_ERR_UNSUPPORTED_FMT;
+    if (((size_t)k_pool | (size_t)v_pool) % 16 != 0) return QATTN_ERR_INVALID_ARG;
+    if (((size_t)k16 | (size_t)v16) % 16 != 0) return QATTN_ERR_INVALID_ARG;   // rows: 16-byte loads
+    for (int i = 0; i < 2; i++)   // (a negative stride would read in front of the base pointer)
+        if (k_strides2[i] < 0 || v_strides2[i] < 0 || k_strides2[i] % 8 != 0 || v_strides2[i] % 8 != 0) return QATTN_ERR_INVALID_ARG;
+    const long long NS = 2LL * B + total / 64;   // chunk slots per kv head
+    if (NS * Hkv > 0x7fffffffLL) return QATTN_ERR_INVALID_ARG;   // (one workgroup per (kv head, slot): a 32-bit grid; NS itself an int)
+    a.x[0] = (const uint4*)k16; a.x[1] = (const uint4*)v16;
+    a.img[0] = (unsigned char*)k_pool; a.img[1] = (unsigned char*)v_pool;
+    a.scale[0] = scale_k; a.scale[1] = scale_v;
+    a.sb[0] = a.sb[1] = 0;   // (no batch axis: the sequence's rows start at start_i)
+    a.st[0] = (long)(k_strides2[0] / 8); a.sh[0] = (long)(k_strides2[1] / 8);
+    a.st[1] = (long)(v_strides2[0] / 8); a.sh[1] = (long)(v_strides2[1] / 8);
+    a.seqlens = seqlens; a.new_lens = nullptr;
+    a.Hkv = Hkv; a.T = total; a.capacity = (int)capacity; a.nchunk = (int)NS;
+    pg.table = block_table; pg.stride = (long)table_stride; pg.num_pages = num_pages; pg.pc = pc;
+    vq.cu = cu_seqlens; vq.B = B; vq.total = total; vq.NS = (int)NS;
+    return QATTN_OK;
+}
 
 template <int D, bool PAGED>
 static int launch_kv_append(const KvAppendArgs& a, const KvPages& pg, int in_fmt, int fp8_fmt, dim3 grid, hipStream_t st) {

@@ -8,7 +8,14 @@
 // workgroup finds its (sequence, chunk) by a binary search on the chunk-slot bases 2 i + start_i / 64 -- the search QATTN_SKV_VARQ runs on
 // its tile slots (qattn_splitkv_body.h) -- and the sequence's count end_i - start_i stands where the padded kernels clamp new_lens[b].
 // With the switch off the text the compiler sees is what it was.
-// In scope: template parameters D, IN_FMT, OUT_FMT; arguments a (KvAppendArgs), -- paged -- pg (KvPages) and -- packed -- vq (KvVarq).
+// QATTN_KVA_ROPE (with QATTN_KVA_PAGED and QATTN_KVA_VARQ; include/qattn_paged_varlen_rope.h) rotates K between the load and the quantiser:
+// the K half (blockIdx.y = 0) holds the work units of qattn_rope_dev.h -- the 16-byte pieces dvh and dvh + D/16 of one row in one thread,
+// ITERS / 2 units in the same ITERS registers -- so that no value crosses lanes; a unit of chunk row r in [lo, hi) is key key0 + r of its
+// sequence and rotates with table row min(key0 + r, T - 1) (`rp`, KvRope; template flag IL = interleaved pairs).  The rotated vector is
+// rounded to the input dtype (rope_unit) before has_nonfinite16 and quant8 see it, and lands at the LDS offsets the plain mapping uses;
+// everything behind the barrier, and the V half, is the shared text.  With the switch off the text the compiler sees is what it was.
+// In scope: template parameters D, IN_FMT, OUT_FMT (rope: IL); arguments a (KvAppendArgs), -- paged -- pg (KvPages), -- packed -- vq
+// (KvVarq) and -- rope -- rp (KvRope).
     constexpr int VPR = D / 8;             // 16-byte input vectors per row
     constexpr int ITERS = 64 * VPR / 256;  // vectors per thread
     constexpr int KPAD = 64 * D + (64 * D / 512) * 16;  // KFRAG image + 16 B per 512 B     (the staging images of quant_multi_kernel)
@@ -55,6 +62,45 @@
 #endif
     const long st = a.st[z];
     uint4 held[ITERS];
+#if QATTN_KVA_ROPE
+    if (z == 0) {   // (workgroup-uniform)
+        constexpr int HV = D / 16;   // units per row; 64 HV / 256 = ITERS / 2 units per thread
+        const float4* cg = reinterpret_cast<const float4*>(rp.cs);
+        const float4* sg = reinterpret_cast<const float4*>(rp.sn);
+        const long tr4 = rp.tr >> 2;
+        float4 c[ITERS / 2][2], s[ITERS / 2][2];
+#pragma unroll
+        for (int u = 0; u < ITERS / 2; u++) {
+            const int unit = u * 256 + tid;
+            const int r = unit / HV, dvh = unit % HV;
+            held[2 * u] = held[2 * u + 1] = make_uint4(0, 0, 0, 0);
+            c[u][0] = c[u][1] = s[u][0] = s[u][1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (r >= lo && r < hi) {   // (rows outside: zero vectors, no table row read)
+                const uint4* px = xg + (long)r * st + dvh;
+                held[2 * u] = load_nt(px);
+                held[2 * u + 1] = load_nt(px + HV);
+                // key0 + r < end <= capacity: an int; the clamp keeps the row inside the tables whatever seqlens holds
+                const int pos = (int)key0 + r < rp.T ? (int)key0 + r : rp.T - 1;
+                const int t0 = IL ? dvh : 2 * dvh, t1 = IL ? dvh + HV : 2 * dvh + 1;
+                c[u][0] = cg[pos * tr4 + t0]; c[u][1] = cg[pos * tr4 + t1];
+                s[u][0] = sg[pos * tr4 + t0]; s[u][1] = sg[pos * tr4 + t1];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < ITERS / 2; u++) {
+            const int unit = u * 256 + tid;
+            const int r = unit / HV, dvh = unit % HV;
+            if (r >= lo && r < hi) rope_unit<IN_FMT, IL>(held[2 * u], held[2 * u + 1], c[u], s[u]);
+#pragma unroll
+            for (int half = 0; half < 2; half++) {
+                const uint4& y = held[2 * u + half];
+                const int2 lohi = quant8<IN_FMT, OUT_FMT>(y, scale, rinv, has_nonfinite16<IN_FMT>(y));   // (on the ROTATED vector)
+                const int o = kfrag_offset<D>(r, (dvh + half * HV) * 8);
+                *reinterpret_cast<int2*>(img + o + ((o >> 9) << 4)) = lohi;
+            }
+        }
+    } else {
+#endif
 #pragma unroll
     for (int it = 0; it < ITERS; it++) {
         const int vec = it * 256 + tid;
@@ -75,6 +121,9 @@
             *reinterpret_cast<int*>(img + r * VSTRIDE + d0 + 4) = lohi.y;
         }
     }
+#if QATTN_KVA_ROPE
+    }
+#endif
     __syncthreads();
 #if QATTN_KVA_PAGED
     // key0 < end <= capacity = max_pages page_size: the entry read is one of the pages that cover [p, end); its clamp keeps the chunk inside

@@ -12,6 +12,7 @@
 // Either way a unit reads 32 bytes of data and 64 bytes of tables, and no value crosses lanes.  The tables are shared by every head of a
 // batch element: blockIdx.x is the head, so that the workgroups in flight together read the same table rows (L2 / Infinity Cache).
 #include "qattn_common.h"
+#include "qattn_rope_dev.h"
 #include "../../include/qattn_rope.h"
 
 namespace qattn {
@@ -32,54 +33,6 @@ struct RopeJobs {
     int nsplit;            // abs-max blocks per head = valid words of amax_part per head
     int token;
 };
-
-// the rotation of one pair, as the contract states it: three separately rounded fp32 operations (no contraction)
-__device__ __forceinline__ void rot(float a, float b, float c, float s, float& y0, float& y1) {
-    y0 = __fsub_rn(__fmul_rn(a, c), __fmul_rn(b, s));
-    y1 = __fadd_rn(__fmul_rn(b, c), __fmul_rn(a, s));
-}
-
-// 8 floats -> 8 values of the input dtype, round to nearest even (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32)
-template <int IN_FMT>
-__device__ __forceinline__ uint4 pack16x8(const float (&f)[8]) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const f2 v = {f[2 * i], f[2 * i + 1]};
-        if (IN_FMT == QATTN_FMT_BF16) {
-            const b2 h = __builtin_convertvector(v, b2);
-            __builtin_memcpy(&w[i], &h, 4);
-        } else {
-            const h2 h = __builtin_convertvector(v, h2);
-            __builtin_memcpy(&w[i], &h, 4);
-        }
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// one unit in place: A = piece dvh, B = piece dvh + D/16; c / s: the unit's two float4 of cos / sin (see the head of the file)
-template <int IN_FMT, bool IL>
-__device__ __forceinline__ void rope_unit(uint4& A, uint4& B, const float4 (&c)[2], const float4 (&s)[2]) {
-    unsigned short ea[8], eb[8];
-    float cc[8], sv[8], fa[8], fb[8];
-    __builtin_memcpy(ea, &A, 16); __builtin_memcpy(eb, &B, 16);
-    __builtin_memcpy(cc, c, 32); __builtin_memcpy(sv, s, 32);
-    if (!IL) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) rot(load16f<IN_FMT>(ea[j]), load16f<IN_FMT>(eb[j]), cc[j], sv[j], fa[j], fb[j]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            rot(load16f<IN_FMT>(ea[2 * i]), load16f<IN_FMT>(ea[2 * i + 1]), cc[i], sv[i], fa[2 * i], fa[2 * i + 1]);
-            rot(load16f<IN_FMT>(eb[2 * i]), load16f<IN_FMT>(eb[2 * i + 1]), cc[4 + i], sv[4 + i], fb[2 * i], fb[2 * i + 1]);
-        }
-    }
-    A = pack16x8<IN_FMT>(fa);
-    B = pack16x8<IN_FMT>(fb);
-}
 
 __device__ __forceinline__ const uint4* rope_head(const RopeJob& jb, int g) { return jb.x + (long)(g / jb.H) * jb.sb + (long)(g % jb.H) * jb.sh; }
 

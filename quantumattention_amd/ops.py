@@ -662,6 +662,62 @@ def _(k_pool, v_pool, scale_k, scale_v, block_table, seqlens, k_new, v_new, cu_s
     return None
 
 
+@_custom_op("quantumattention_amd::fp8_paged_varlen_rope_kv_cache_append_", mutates_args=("k_pool", "v_pool", "seqlens"), device_types=("cuda",))
+def fp8_paged_varlen_rope_kv_cache_append_(
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens: torch.Tensor,
+    k_new: torch.Tensor,
+    v_new: torch.Tensor,
+    cu_seqlens: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    num_pages: int,
+    page_size: int,
+    fp8_format: str = "e4m3",
+    interleaved: bool = False,
+    advance: bool = True,
+) -> None:
+    """fp8_paged_varlen_kv_cache_append_ with K rotated inside the append (include/qattn_paged_varlen_rope.h): key p + t of a slot rotates
+    with row min(p + t, T - 1) of cos / sin (fp32 [T, D/2], read in place) before it is quantised.
+    Reference implementation: paged_varlen._append_varlen_rope_eager.  Arguments are validated by
+    paged_varlen.paged_kv_cache_append_varlen_rope_fp8."""
+    _native.paged_kv_cache_append_varlen_rope_fp8(k_pool, v_pool, scale_k, scale_v, block_table, seqlens, k_new, v_new, cu_seqlens, cos, sin,
+                                                  num_pages=num_pages, page_size=page_size, fp8_dtype=_native.fp8_dtype_of(fp8_format),
+                                                  interleaved=interleaved, advance=advance)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_varlen_rope_kv_cache_append_")
+def _(k_pool, v_pool, scale_k, scale_v, block_table, seqlens, k_new, v_new, cu_seqlens, cos, sin, num_pages, page_size, fp8_format="e4m3",
+      interleaved=False, advance=True):
+    return None
+
+
+@_custom_op("quantumattention_amd::rope_paged_varlen", mutates_args=(), device_types=("cuda",))
+def rope_paged_varlen(
+    x: torch.Tensor,
+    seqlens: torch.Tensor,
+    cu_seqlens: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    capacity: int,
+    interleaved: bool = False,
+    appended: bool = False,
+) -> torch.Tensor:
+    """Packed rows x [total, H, D] rotated at the positions of a paged cache's slots (include/qattn_paged_varlen_rope.h) -> dense
+    [total, H, D]; rows behind cu_seqlens[B] have unspecified contents.  Reference implementation: paged_varlen._rope_paged_varlen_eager.
+    Arguments are validated by paged_varlen.apply_rope_paged_varlen."""
+    return _native.rope_paged_varlen(x, seqlens, cu_seqlens, cos, sin, capacity=capacity, interleaved=interleaved, appended=appended)
+
+
+@_register_fake("quantumattention_amd::rope_paged_varlen")
+def _(x, seqlens, cu_seqlens, cos, sin, capacity, interleaved=False, appended=False):
+    return x.new_empty(x.shape)
+
+
 @_custom_op("quantumattention_amd::fp8_paged_varlen_splitkv_attention_forward", mutates_args=(), device_types=("cuda",))
 def fp8_paged_varlen_splitkv_attention_forward(
     query: torch.Tensor,

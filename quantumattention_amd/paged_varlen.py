@@ -19,9 +19,19 @@ no padding to the longest chunk, no new_lens beside cu_seqlens.
     paged_kv_cache_append_varlen_fp8(cache, qkv[:, Hq:Hq + Hkv], qkv[:, Hq + Hkv:], cu)
     out = fp8_attn_paged_varlen_func(qkv[:, :Hq], cache, cu, max_seqlen_q, causal=True, max_seqlen_k=longest_live_sequence)
 
-Package attributes, not names of `__all__`.  Not offered: rotary embedding of K inside the append, a per-token slot_mapping form, a
-per-call table whose batch differs from the cache's slots, the contiguous `KVCacheFP8`, page allocation.  Sliding windows:
-splitkv_window.fp8_attn_paged_varlen_window_func."""
+With the rotary embedding (include/qattn_paged_varlen_rope.h): `paged_kv_cache_append_varlen_rope_fp8` rotates K
+inside the append -- key p_b + t of slot b with row p_b + t of one cos / sin table pair, a key's index in its sequence being its position
+-- and `apply_rope_paged_varlen` rotates q at the positions of the keys the same tokens become.  No positions tensor, no rotated K in
+memory:
+
+    q = apply_rope_paged_varlen(qkv[:, :Hq], cache, cu, cos, sin)                      # before the append: the default appended=False
+    paged_kv_cache_append_varlen_rope_fp8(cache, qkv[:, Hq:Hq + Hkv], qkv[:, Hq + Hkv:], cu, cos, sin)
+    out = fp8_attn_paged_varlen_func(q, cache, cu, max_seqlen_q, causal=True, max_seqlen_k=longest_live_sequence)
+
+Package attributes, not names of `__all__`.  Not offered: RoPE fused into the attention's q pre-pass, per-slot position offsets or a
+positions tensor, a partial rotary_dim, scaled / YaRN tables beyond what the caller puts into cos / sin, RoPE in the padded and the
+contiguous appends, a per-token slot_mapping form, a per-call table whose batch differs from the cache's slots, the contiguous
+`KVCacheFP8`, page allocation.  Sliding windows: splitkv_window.fp8_attn_paged_varlen_window_func."""
 import math
 from typing import Optional, Tuple
 
@@ -31,6 +41,7 @@ from torch import Tensor
 from . import _native, nn
 from .kvcache import _is_int
 from .paged import PagedKVCacheFP8, _append_eager, _cache_reason, _lens_reason, gather_paged_eager
+from .rope import _TABLE_DTYPES, apply_rope_eager
 from .splitkv import _CPU_NUM_CUS, MAX_SPLITS, PreparedKV, _splitkv_eager
 from .utils import checks
 
@@ -291,3 +302,215 @@ def paged_kv_cache_append_varlen_fp8(cache: PagedKVCacheFP8, k_new: Tensor, v_ne
                                                  cu_seqlens, num_pages=cache.num_pages, page_size=cache.page_size,
                                                  fp8_dtype=_native.fp8_dtype_of(cache.fp8_format), advance=bool(advance))
     return cache
+
+
+# ---- the rotary embedding at the cache's positions (include/qattn_paged_varlen_rope.h) ----------------------------------------------------
+def _rope_tables_reason(cos, sin, D: int, capacity: int, device) -> Optional[str]:
+    """The first rule a cos / sin pair breaks for a cache of head_dim D and `capacity` keys per slot, or None.  Host ints only."""
+    if not isinstance(cos, Tensor) or not isinstance(sin, Tensor):
+        return "cos / sin must be tensors"
+    if cos.shape != sin.shape:
+        return f"cos / sin must have the same shape, got {tuple(cos.shape)} and {tuple(sin.shape)}"
+    if cos.dtype != sin.dtype or cos.dtype not in _TABLE_DTYPES:
+        return f"cos / sin must share a dtype out of float32, bfloat16, float16, got {cos.dtype} and {sin.dtype}"
+    if cos.device != device or sin.device != device:
+        return f"cos / sin must be on the cache's device {device}, got {cos.device} and {sin.device}"
+    if cos.dim() != 2:
+        return (f"cos / sin must be [T, D/2], one table pair for every slot, got {cos.dim()} dimension(s): the [B, T, D/2] form (a table per "
+                "slot) is not offered here, nor are per-slot position offsets")
+    if cos.shape[1] != D // 2:
+        return (f"cos / sin must hold D/2 = {D // 2} entries per row, one per rotated pair, got {cos.shape[1]}: a partial rotary_dim is not "
+                "supported (only the full head dim is rotated), nor is the duplicated [T, D] table layout")
+    if cos.shape[0] < capacity:
+        return (f"cos / sin hold T = {cos.shape[0]} positions, fewer than the cache's capacity max_pages_per_seq * page_size = {capacity}: "
+                "a key's index in its sequence is its position")
+    if cos.dtype == torch.float32:   # read in place (16-bit tables are up-cast into dense ones)
+        for name, t in (("cos", cos), ("sin", sin)):
+            aligned = torch.compiler.is_dynamo_compiling() or t.storage_offset() % 4 == 0
+            if not (t.stride(1) == 1 and aligned and (t.shape[0] == 1 or (t.stride(0) >= 0 and t.stride(0) % 4 == 0))):
+                return (f"Expected {name} to have dense rows, a 16-byte-aligned base and a row stride that is a non-negative multiple of 4 "
+                        f"floats (rows are read 16 bytes at a time), but got strides {tuple(t.stride())} at storage offset "
+                        f"{t.storage_offset()}; pass {name}.contiguous()")
+        if cos.shape[0] > 1 and cos.stride(0) != sin.stride(0):
+            return f"Expected cos and sin to have the same row stride, but got {cos.stride(0)} and {sin.stride(0)}"
+    return None
+
+
+def paged_varlen_rope_append_input_reason(cache, k_new, v_new, cu_seqlens, cos, sin) -> Optional[str]:
+    """The first rule the arguments of `paged_kv_cache_append_varlen_rope_fp8` break, or None: `paged_varlen_append_input_reason`, then
+    the table rules -- cos / sin [T, D/2] of one dtype out of float32 / bfloat16 / float16 on the cache's device, T >= cache.capacity,
+    float32 tables addressable as rows of float4.  Shapes, dtypes, devices and strides only: nothing is read on the device."""
+    reason = paged_varlen_append_input_reason(cache, k_new, v_new, cu_seqlens)
+    if reason:
+        return reason
+    return _rope_tables_reason(cos, sin, cache.shape[3], cache.capacity, cache.device)
+
+
+def _fp32_tables(cos: Tensor, sin: Tensor) -> Tuple[Tensor, Tensor]:
+    """16-bit tables are up-cast (exact), as rope._check_tables does; float32 tables go as they are"""
+    if cos.dtype == torch.float32:
+        return cos, sin
+    return cos.to(torch.float32).contiguous(), sin.to(torch.float32).contiguous()
+
+
+def _rope_positions_host(cache: PagedKVCacheFP8, cu_seqlens: Tensor, total: int, T: int, appended: bool):
+    """(rows, positions): the rows of the packed tokens that a slot owns and the table row each is rotated with, as host lists.  (Reads
+    cu_seqlens and seqlens on the host: the eager definitions only.)"""
+    cu, lens, cap = cu_seqlens.tolist(), cache.seqlens.tolist(), cache.capacity
+    rows, pos = [], []
+    for b in range(cache.batch_size):
+        start = min(max(int(cu[b]), 0), total)
+        n = min(max(int(cu[b + 1]), start), total) - start
+        base = max(min(max(int(lens[b]), 0), cap) - (n if appended else 0), 0)
+        rows += range(start, start + n)
+        pos += [min(base + t, T - 1) for t in range(n)]
+    return rows, pos
+
+
+def _rope_rows_eager(x: Tensor, rows, pos, cos: Tensor, sin: Tensor, interleaved: bool) -> Tensor:
+    """apply_rope_eager on the rows `rows` of x [total, H, D], row rows[j] with table row pos[j] -> [len(rows), H, D]"""
+    at = torch.tensor(pos, dtype=torch.long, device=cos.device)
+    return apply_rope_eager(x[rows].transpose(0, 1)[None], cos[at], sin[at], interleaved=interleaved)[0].transpose(0, 1)
+
+
+def _append_varlen_rope_eager(cache: PagedKVCacheFP8, k_new: Tensor, v_new: Tensor, cu_seqlens: Tensor, cos: Tensor, sin: Tensor,
+                              interleaved: bool, advance: bool) -> None:
+    """CPU tensors and config.attention.force_eager_fallback: the rule's composition -- `apply_rope_eager` on the owned rows of k_new at
+    their keys' positions, then `_append_varlen_eager`.  (This path reads cu_seqlens and seqlens on the host.)"""
+    rows, pos = _rope_positions_host(cache, cu_seqlens, k_new.shape[0], cos.shape[0], False)
+    k_rot = torch.zeros(k_new.shape, dtype=k_new.dtype, device=k_new.device)      # (rows nobody owns are not read by the append)
+    if rows:
+        k_rot[rows] = _rope_rows_eager(k_new, rows, pos, cos, sin, interleaved)
+    _append_varlen_eager(cache, k_rot, v_new, cu_seqlens, advance)
+
+
+def paged_kv_cache_append_varlen_rope_fp8(cache: PagedKVCacheFP8, k_new: Tensor, v_new: Tensor, cu_seqlens: Tensor, cos: Tensor, sin: Tensor, *,
+                                          interleaved: bool = False, advance: bool = True) -> PagedKVCacheFP8:
+    """`paged_kv_cache_append_varlen_fp8` with the rotary embedding of K inside the append; in place, returns `cache`.
+
+    cache, k_new, v_new, cu_seqlens, advance: exactly those of `paged_kv_cache_append_varlen_fp8` (strided slices of the packed
+    projection, clamps, dropped tail, idle slots, rows behind cu[B] not read).  k_new is the UNROTATED K.  cos, sin: [T, D/2], one table
+    pair for every slot, T >= cache.capacity; float32 tables are read in place as rows of float4 (base 16-byte aligned, row stride a
+    non-negative multiple of 4 floats: a slice cos[:, :D/2] of a wider table is fine), bfloat16 / float16 tables are up-cast.
+    `interleaved` as `fp8_attn_rope_func`: False pairs (i, i + D/2), True pairs (2i, 2i + 1).  Key p_b + t of slot b,
+    p_b = clamp(seqlens[b], 0, capacity), is rotated with table row p_b + t: a key's index in its sequence is its position.  V is not
+    rotated.
+    The rule: pools and seqlens end, byte for byte, as `paged_kv_cache_append_varlen_fp8(cache, k_rot, v_new, cu_seqlens)` leaves them
+    with k_rot = `apply_rope_eager` of every token at its key's position -- the rotated value rounded to the input dtype before the
+    quantiser, non-finite values handled as the composition handles them; exactly the bytes of the appended keys change.
+    Everything is read on the device: no host synchronisation, no allocation (16-bit tables excepted), graph-capture safe, and a
+    captured call follows the later contents of cu_seqlens, seqlens, the table and cos / sin.  total = 0 returns at once.  CPU tensors
+    and config.attention.force_eager_fallback run the eager definition (`_append_varlen_rope_eager`); on the device there is no
+    fallback.  Invalid input raises ValueError(reason)."""
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = paged_varlen_rope_append_input_reason(cache, k_new, v_new, cu_seqlens, cos, sin)
+        if reason:
+            raise ValueError(reason)
+    if k_new.shape[0] == 0:
+        return cache
+    cos, sin = _fp32_tables(cos, sin)
+    il = bool(interleaved)
+    eager = (not k_new.is_cuda or checks.config_value("attention.force_eager_fallback")) and not torch.compiler.is_dynamo_compiling()
+    if eager:
+        if cache.layout != "rowmajor":
+            raise ValueError("the eager definition needs a cache made on a CPU device or under config.attention.force_eager_fallback")
+        _append_varlen_rope_eager(cache, k_new, v_new, cu_seqlens, cos, sin, il, bool(advance))
+        return cache
+    if cache.layout != "frag":
+        raise ValueError("this cache holds row-major bytes for the eager definition; make it on the device without "
+                         "config.attention.force_eager_fallback")
+    ok, why = nn._pre_check_can_use_hip_attention(device=k_new.device)
+    if not ok:
+        raise ValueError(why)
+    if torch.compiler.is_compiling():
+        nn._ops().fp8_paged_varlen_rope_kv_cache_append_(cache.k, cache.v, cache.scale_k, cache.scale_v, cache.block_table, cache.seqlens, k_new,
+                                                         v_new, cu_seqlens, cos, sin, cache.num_pages, cache.page_size, cache.fp8_format, il,
+                                                         bool(advance))
+    else:
+        # outside a trace: the op's own body, without the dispatcher's bookkeeping for a mutating op (as paged_kv_cache_append_varlen_fp8)
+        _native.paged_kv_cache_append_varlen_rope_fp8(cache.k, cache.v, cache.scale_k, cache.scale_v, cache.block_table, cache.seqlens, k_new,
+                                                      v_new, cu_seqlens, cos, sin, num_pages=cache.num_pages, page_size=cache.page_size,
+                                                      fp8_dtype=_native.fp8_dtype_of(cache.fp8_format), interleaved=il, advance=bool(advance))
+    return cache
+
+
+def paged_varlen_rope_input_reason(x, cache, cu_seqlens, cos, sin, out=None) -> Optional[str]:
+    """The first rule the arguments of `apply_rope_paged_varlen` break, or None.  Shapes, dtypes, devices and strides only."""
+    reason = _cache_reason(cache)
+    if reason:
+        return reason
+    if not isinstance(x, Tensor) or x.dim() != 3:
+        return "NYI: x must be a 3-D tensor [total, H, head_dim]"
+    if x.requires_grad:
+        return "NYI: x must be a leaf tensor (no backward)"
+    if x.dtype != cache.dtype:
+        return f"Expected x to have the cache's dtype {cache.dtype}, but got {x.dtype} instead."
+    B, D = cache.batch_size, cache.shape[3]
+    if x.shape[2] != D:
+        return f"Expect x to have the cache's head dimension but got {x.shape[2]} and {D}."
+    if x.shape[1] == 0:
+        return "Expected a non-empty head count"
+    if x.device != cache.device:
+        return f"Expected x to be on the cache's device {cache.device}, but got {x.device} instead."
+    if x.shape[0] > 0 and not _q_rows_addressable(x):
+        return (f"Expected x to have head_dim innermost and 16-byte-aligned rows (strides that are multiples of 8 elements), but got "
+                f"strides {tuple(x.stride())} at storage offset {x.storage_offset()}; pass x.contiguous()")
+    if not isinstance(cu_seqlens, Tensor) or cu_seqlens.dtype != torch.int32:
+        return f"Expected cu_seqlens to be a torch.int32 tensor, but got {getattr(cu_seqlens, 'dtype', type(cu_seqlens))}"
+    if tuple(cu_seqlens.shape) != (B + 1,):
+        return f"Expected cu_seqlens to have shape [{B + 1}] (the cache's slots + 1), but got {list(cu_seqlens.shape)}."
+    if cu_seqlens.device != cache.device:
+        return f"Expected cu_seqlens to be on {cache.device}, but got {cu_seqlens.device} instead."
+    if not cu_seqlens.is_contiguous():
+        return "Expected cu_seqlens to be contiguous"
+    reason = _lens_reason("cache.seqlens", cache.seqlens, B, cache.device)
+    if reason:
+        return reason
+    if out is not None:
+        if not isinstance(out, Tensor) or out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+            return f"Expected out to have x's shape {list(x.shape)}, dtype and device"
+        if not out.is_contiguous() or (not torch.compiler.is_dynamo_compiling() and out.storage_offset() % 8 != 0):
+            return "Expected out to be contiguous and 16-byte aligned"
+    return _rope_tables_reason(cos, sin, D, cache.capacity, cache.device)
+
+
+def _rope_paged_varlen_eager(x: Tensor, cache: PagedKVCacheFP8, cu_seqlens: Tensor, cos: Tensor, sin: Tensor, interleaved: bool,
+                             appended: bool, out: Tensor) -> None:
+    """CPU tensors and config.attention.force_eager_fallback: `apply_rope_eager` on the owned rows at host-computed positions, written
+    into `out`; other rows of `out` are left alone.  (Reads cu_seqlens and seqlens on the host.)"""
+    rows, pos = _rope_positions_host(cache, cu_seqlens, x.shape[0], cos.shape[0], appended)
+    if rows:
+        out[rows] = _rope_rows_eager(x, rows, pos, cos, sin, interleaved)
+
+
+def apply_rope_paged_varlen(x: Tensor, cache: PagedKVCacheFP8, cu_seqlens: Tensor, cos: Tensor, sin: Tensor, *, interleaved: bool = False,
+                            appended: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """Rotate packed rows -- q, or anything packed under cu_seqlens -- at the positions of the paged cache's slots.
+
+    x [total, H, D] in cache.dtype, read through its {token, head} strides under the packed append's stride rules: the q slice of the
+    projection goes in as it is.  Returns dense [total, H, D] in x.dtype (`out`, if given: contiguous, 16-byte aligned).  cu_seqlens, cos,
+    sin, interleaved: as `paged_kv_cache_append_varlen_rope_fp8`.  Row start_b + t is rotated with table row max(base_b, 0) + t,
+    base_b = clamp(seqlens[b], 0, capacity) - (n_b if appended else 0): appended=False for a call made BEFORE the step's append -- a
+    query then gets the position of the key the same token becomes -- appended=True for one made after an advancing append.
+    Bit for bit `apply_rope_eager` at these positions.  Rows behind cu[B] are neither read nor written (unspecified in a new tensor).
+    One launch; everything is read on the device: no host synchronisation, no allocation beyond the result (16-bit tables excepted),
+    graph-capture safe.  CPU tensors and config.attention.force_eager_fallback run the eager definition; on the device there is no
+    fallback.  Invalid input raises ValueError(reason)."""
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = paged_varlen_rope_input_reason(x, cache, cu_seqlens, cos, sin, out)
+        if reason:
+            raise ValueError(reason)
+    cos, sin = _fp32_tables(cos, sin)
+    il, ap = bool(interleaved), bool(appended)
+    eager = (not x.is_cuda or checks.config_value("attention.force_eager_fallback")) and not torch.compiler.is_dynamo_compiling()
+    if eager:
+        res = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+        _rope_paged_varlen_eager(x, cache, cu_seqlens, cos, sin, il, ap, res)
+        return res
+    ok, why = nn._pre_check_can_use_hip_attention(device=x.device)
+    if not ok:
+        raise ValueError(why)
+    if torch.compiler.is_compiling():
+        res = nn._ops().rope_paged_varlen(x, cache.seqlens, cu_seqlens, cos, sin, cache.capacity, il, ap)
+        return res if out is None else out.copy_(res)
+    return _native.rope_paged_varlen(x, cache.seqlens, cu_seqlens, cos, sin, capacity=cache.capacity, interleaved=il, appended=ap, out=out)
