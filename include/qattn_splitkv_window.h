@@ -60,8 +60,8 @@
  * block-table entries of the slot are dead: the caller's allocator may hand their pages to someone else and leave the entries as they
  * are (or overwrite them with anything).  The library neither allocates nor frees pages.
  *
- * Not offered: learned attention sinks; "sink tokens + window" in one call (two calls and a state merge); windows on the 16-bit P.V
- * numerics.
+ * Learned attention sinks (gpt-oss): the sibling entries of include/qattn_sinks.h.  Not offered: "sink tokens + window" in one call (two
+ * calls and a state merge); windows on the 16-bit P.V numerics.
  */
 #ifndef QATTN_SPLITKV_WINDOW_H_
 #define QATTN_SPLITKV_WINDOW_H_

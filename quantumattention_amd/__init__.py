@@ -61,6 +61,13 @@ from .splitkv_window import (  # noqa: E402
     fp8_attn_splitkv_window_func,
     paged_window_dead_pages,
 )
+# learned attention sinks for the three window entries and the state merge (include/qattn_sinks.h): package attributes, not in __all__
+from .sinks import (  # noqa: E402
+    fp8_attn_paged_sink_func,
+    fp8_attn_paged_varlen_sink_func,
+    fp8_attn_splitkv_sink_func,
+    merge_attn_states_with_sinks,
+)
 
 __version__ = "0.1.0"
 

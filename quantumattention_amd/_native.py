@@ -59,6 +59,8 @@ EXPORTS = (
     "qattn_fp8_attention_paged_splitkv_window_forward", "qattn_fp8_attention_paged_varlen_window_forward",
     "qattn_paged_kv_cache_append_varlen_fp8",
     "qattn_paged_kv_cache_append_varlen_rope_fp8", "qattn_rope_paged_varlen",
+    "qattn_attention_state_merge_sink", "qattn_fp8_attention_splitkv_sink_forward", "qattn_fp8_attention_paged_splitkv_sink_forward",
+    "qattn_fp8_attention_paged_varlen_sink_forward",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -292,6 +294,18 @@ def lib() -> ctypes.CDLL:
     # sin, table_row_stride, T, interleaved, stream
     L.qattn_rope_paged_varlen.restype = i
     L.qattn_rope_paged_varlen.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, i, ll, i, vp, vp, ll, i, i, vp]
+    # learned attention sinks (include/qattn_sinks.h): the merge's arguments + sink; the window entries' arguments with sinks after window_right
+    L.qattn_attention_state_merge_sink.restype = i
+    L.qattn_attention_state_merge_sink.argtypes = [i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, i, i, i, i, vp, vp]
+    L.qattn_fp8_attention_splitkv_sink_forward.restype = i
+    L.qattn_fp8_attention_splitkv_sink_forward.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, vp, f, i, i,
+                                                           vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.qattn_fp8_attention_paged_splitkv_sink_forward.restype = i
+    L.qattn_fp8_attention_paged_splitkv_sink_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i,
+                                                                 vp, f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.qattn_fp8_attention_paged_varlen_sink_forward.restype = i
+    L.qattn_fp8_attention_paged_varlen_sink_forward.argtypes = [vp, vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i,
+                                                                i, i, i, vp, f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1033,15 +1047,27 @@ def _merge_strides(o: torch.Tensor, lse: torch.Tensor):
 
 def attention_state_merge(outs, lses, *, out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None,
                           out_dtype: Optional[torch.dtype] = None, return_lse: bool = True):
+    return _attention_state_merge(outs, lses, None, out, lse_out, out_dtype, return_lse)
+
+
+def attention_state_merge_sink(outs, lses, sinks: torch.Tensor, *, out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None,
+                               out_dtype: Optional[torch.dtype] = None, return_lse: bool = True):
+    """qattn_attention_state_merge_sink (include/qattn_sinks.h): `attention_state_merge` of 1 .. 8 states with sinks, fp32 [H] on the
+    device -- the learned sink of every head as one more state without an O row."""
+    return _attention_state_merge(outs, lses, sinks, out, lse_out, out_dtype, return_lse)
+
+
+def _attention_state_merge(outs, lses, sinks, out, lse_out, out_dtype, return_lse):
     """qattn_attention_state_merge (include/qattn_merge.h) in one launch: 2 .. 8 partial states (outs[i], lses[i]) of the same queries over
     disjoint key sets -> the state over the union.  outs[i]: [B,H,S,D] with lses[i] fp32 [B,H,S], or packed [total,H,D] with [H,total];
     bf16 / fp16 / fp32, each its own; any strides with head_dim innermost and 16-byte rows go to the kernel as they are (the stride table
     is built from the tensors; anything else is copied).  out / lse_out: caller's buffers (never copied: they must be addressable), e.g.
     outs[0] / lses[0] themselves for the in-place accumulate; else fresh dense tensors of out_dtype (default: outs[0]'s).  The caller has
     validated shapes and dtypes (merge.merge_attn_states).  Returns (out, lse_out), or out without return_lse (no LSE is written then,
-    unless lse_out is given)."""
+    unless lse_out is given).  (sinks: the entry of `attention_state_merge_sink` instead.)"""
     n = len(outs)
-    _require(2 <= n <= MERGE_MAX_PARTIALS and len(lses) == n, f"attention_state_merge takes 2 .. {MERGE_MAX_PARTIALS} states per launch, got {n}")
+    _require((2 if sinks is None else 1) <= n <= MERGE_MAX_PARTIALS and len(lses) == n,
+             f"attention_state_merge takes {2 if sinks is None else 1} .. {MERGE_MAX_PARTIALS} states per launch, got {n}")
     o0 = outs[0]
     _require(o0.is_cuda and o0.dim() in (3, 4) and lses[0].dim() == o0.dim() - 1, "states must be device tensors [B,H,S,D] / [B,H,S] or [total,H,D] / [H,total]")
     outs = [o if merge_addressable(o) else o.contiguous() for o in outs]
@@ -1063,12 +1089,17 @@ def attention_state_merge(outs, lses, *, out: Optional[torch.Tensor] = None, lse
         o_str, l_str = zip(*(_merge_strides(o, l) for o, l in zip(outs, lses)))
         out_str, lout_str = _merge_strides(out, lse_out if lse_out is not None else lses[0])
         ll = ctypes.c_longlong
-        rc = lib().qattn_attention_state_merge(
+        entry, sink_arg = lib().qattn_attention_state_merge, ()
+        if sinks is not None:
+            _require(sinks.dtype == torch.float32 and sinks.device == dev and tuple(sinks.shape) == (H,) and sinks.is_contiguous(),
+                     f"sinks must be a dense float32 [H={H}] tensor on {dev}")
+            entry, sink_arg = lib().qattn_attention_state_merge_sink, (sinks.data_ptr(),)
+        rc = entry(
             n, (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), (ctypes.c_int * n)(*[_MERGE_FMT[o.dtype] for o in outs]),
             (ll * (3 * n))(*[x for st in o_str for x in st]), (ctypes.c_void_p * n)(*[l.data_ptr() for l in lses]),
             (ll * (3 * n))(*[x for st in l_str for x in st]), out.data_ptr(), _MERGE_FMT[out.dtype], (ll * 3)(*out_str), _ptr(lse_out),
-            (ll * 3)(*lout_str), B, H, S, D, _stream(o0))
-    _check(rc, "qattn_attention_state_merge")
+            (ll * 3)(*lout_str), B, H, S, D, _stream(o0), *sink_arg)
+    _check(rc, "qattn_attention_state_merge" if sinks is None else "qattn_attention_state_merge_sink")
     return (out, lse_out) if return_lse else out
 
 
@@ -1188,6 +1219,16 @@ def _window_args(window):
     return int(window[0]), int(window[1])
 
 
+def _sink_args(sinks, window, Hq, dev):
+    """() without sinks, else (the pointer,): the sink entries (include/qattn_sinks.h) take it right after window_left, window_right."""
+    if sinks is None:
+        return ()
+    _require(window is not None, "sinks are offered by the window entries: pass window=(left, right)")
+    _require(sinks.dtype == torch.float32 and sinks.device == dev and tuple(sinks.shape) == (Hq,) and sinks.is_contiguous(),
+             f"sinks must be a dense float32 [Hq={Hq}] tensor on {dev}")
+    return (sinks.data_ptr(),)
+
+
 def splitkv_auto_splits(B: int, Hq: int, Hkv: int, Sq: int, Skv: int, D: int, num_cus: int) -> int:
     """qattn_splitkv_auto_splits (include/qattn_splitkv.h): the num_splits = 0 rule, a pure host function of the shape and the CU count."""
     return int(lib().qattn_splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, num_cus))
@@ -1197,20 +1238,24 @@ def fp8_attention_splitkv(q: torch.Tensor, k_frag: torch.Tensor, v_frag: torch.T
                           Skv: int, fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled", is_causal: bool = False,
                           sm_scale: float = 0.0, precision: str = "accurate", num_splits: int = 0,
                           seqused_k: Optional[torch.Tensor] = None, return_lse: bool = False, return_partials: bool = False,
-                          return_quant: bool = False, return_path: bool = False, window: Optional[Tuple[int, int]] = None):
+                          return_quant: bool = False, return_path: bool = False, window: Optional[Tuple[int, int]] = None,
+                          sinks: Optional[torch.Tensor] = None):
     """Split-KV attention over prepared K / V (qattn_fp8_attention_splitkv_forward, include/qattn_splitkv.h).  q [B, Hq, Sq, D] bf16 / fp16;
     k_frag / v_frag: the KFRAG / VFRAG images (flat uint8) of [B, Hkv, Skv, D] in fp8_dtype with scale_k / scale_v fp32 [B, Hkv];
     seqused_k int32 [B] on the device or None.  num_splits 0: the auto rule on the device's CU count (resolved here, on the host).
     Returns out, or a tuple of out, [lse], [partial_o fp32 [ns, B, Hq, Sq, D], partial_lse [ns, B, Hq, Sq], partial_path uint8 -- three
     empty tensors when the call ran one split], [q8, scale_q], [row_path uint8 [B, Hq, Sq]].
     window = (left, right): qattn_fp8_attention_splitkv_window_forward (include/qattn_splitkv_window.h) instead -- the window stands in
-    is_causal's place, which is then not read; the same for the two paged functions below."""
+    is_causal's place, which is then not read; the same for the two paged functions below.
+    sinks (with window; fp32 [Hq] on the device): qattn_fp8_attention_splitkv_sink_forward (include/qattn_sinks.h) -- a learned sink logit
+    per query head in the softmax denominator; the partials stay free of it.  Again the same for the two paged functions."""
     _require(precision in ("fast", "accurate"), f"Unsupported precision for the split-KV entry: {precision!r} (expected 'fast' or 'accurate')")
     _require(q.is_cuda and q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16), "query must be a 4-D bf16 / fp16 device tensor")
     _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
     mask_args = (int(bool(is_causal)),) if window is None else _window_args(window)
     q = q.contiguous()
     B, Hq, Sq, D = q.shape
+    mask_args += _sink_args(sinks, window, Hq, q.device)
     _require(scale_k.dim() == 2 and scale_k.shape[0] == B and scale_k.shape == scale_v.shape, "scale_k / scale_v must be fp32 [B, Hkv]")
     Hkv = scale_k.shape[1]
     _require(Hkv > 0 and Hq % Hkv == 0, f"Hq={Hq} is not a multiple of Hkv={Hkv}")
@@ -1245,12 +1290,14 @@ def fp8_attention_splitkv(q: torch.Tensor, k_frag: torch.Tensor, v_frag: torch.T
         ws_bytes = L.qattn_fp8_attention_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, ns)
         ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
         live = lambda t: _ptr(t) if t is not None and t.numel() else None
-        fwd = L.qattn_fp8_attention_splitkv_forward if window is None else L.qattn_fp8_attention_splitkv_window_forward
+        fwd = (L.qattn_fp8_attention_splitkv_forward if window is None else L.qattn_fp8_attention_splitkv_window_forward if sinks is None
+               else L.qattn_fp8_attention_splitkv_sink_forward)
         rc = fwd(
             q.data_ptr(), fmt_of(q.dtype), k_frag.data_ptr(), v_frag.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(),
             _ptr(lse), _ptr(seqused_k), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), *mask_args, float(sm_scale),
             _precision(precision), ns, _ptr(q8), _ptr(sq), _ptr(path), live(po), live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_attention_splitkv_forward" if window is None else "qattn_fp8_attention_splitkv_window_forward")
+    _check(rc, "qattn_fp8_attention_splitkv_forward" if window is None else "qattn_fp8_attention_splitkv_window_forward" if sinks is None
+           else "qattn_fp8_attention_splitkv_sink_forward")
     if not (return_lse or return_partials or return_quant or return_path):
         return out
     return ((out,) + ((lse,) if return_lse else ()) + ((po, plse, ppath) if return_partials else ()) + ((q8, sq) if return_quant else ())
@@ -1450,7 +1497,8 @@ def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: t
                                 block_table: torch.Tensor, seqused_k: torch.Tensor, *, Skv: int, num_pages: int, page_size: int,
                                 fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled", is_causal: bool = False, sm_scale: float = 0.0,
                                 precision: str = "accurate", num_splits: int = 0, return_lse: bool = False, return_partials: bool = False,
-                                return_quant: bool = False, return_path: bool = False, window: Optional[Tuple[int, int]] = None):
+                                return_quant: bool = False, return_path: bool = False, window: Optional[Tuple[int, int]] = None,
+                                sinks: Optional[torch.Tensor] = None):
     """Split-KV attention over a paged cache (qattn_fp8_attention_paged_splitkv_forward, include/qattn_paged.h): fp8_attention_splitkv with
     the pools (flat uint8: the KFRAG / VFRAG images of [num_pages, Hkv, page_size, D]) and block_table int32 [B, max_pages] in place of the
     contiguous images; Skv <= max_pages page_size is the logical bound, seqused_k int32 [B] is required.  Returns what
@@ -1461,6 +1509,7 @@ def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: t
     mask_args = (int(bool(is_causal)),) if window is None else _window_args(window)
     q = q.contiguous()
     B, Hq, Sq, D = q.shape
+    mask_args += _sink_args(sinks, window, Hq, q.device)
     _require(scale_k.dim() == 2 and scale_k.shape[0] == B, "scale_k / scale_v must be fp32 [B, Hkv]")
     Hkv = scale_k.shape[1]
     _require(Hkv > 0 and Hq % Hkv == 0, f"Hq={Hq} is not a multiple of Hkv={Hkv}")
@@ -1491,13 +1540,15 @@ def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: t
         ws_bytes = L.qattn_fp8_attention_paged_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, ns)
         ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
         live = lambda t: _ptr(t) if t is not None and t.numel() else None
-        fwd = L.qattn_fp8_attention_paged_splitkv_forward if window is None else L.qattn_fp8_attention_paged_splitkv_window_forward
+        fwd = (L.qattn_fp8_attention_paged_splitkv_forward if window is None else L.qattn_fp8_attention_paged_splitkv_window_forward
+               if sinks is None else L.qattn_fp8_attention_paged_splitkv_sink_forward)
         rc = fwd(
             q.data_ptr(), fmt_of(q.dtype), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), tstride, num_pages, page_size, max_pages,
             scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(), _ptr(lse), seqused_k.data_ptr(), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype),
             _numerics(numerics), *mask_args, float(sm_scale), _precision(precision), ns, _ptr(q8), _ptr(sq), _ptr(path), live(po),
             live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_attention_paged_splitkv_forward" if window is None else "qattn_fp8_attention_paged_splitkv_window_forward")
+    _check(rc, "qattn_fp8_attention_paged_splitkv_forward" if window is None else "qattn_fp8_attention_paged_splitkv_window_forward"
+           if sinks is None else "qattn_fp8_attention_paged_splitkv_sink_forward")
     if not (return_lse or return_partials or return_quant or return_path):
         return out
     return ((out,) + ((lse,) if return_lse else ()) + ((po, plse, ppath) if return_partials else ()) + ((q8, sq) if return_quant else ())
@@ -1521,7 +1572,7 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
                                num_pages: int, page_size: int, fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled",
                                is_causal: bool = False, sm_scale: float = 0.0, precision: str = "accurate", num_splits: int = 0,
                                return_lse: bool = False, return_partials: bool = False, return_quant: bool = False, return_path: bool = False,
-                               window: Optional[Tuple[int, int]] = None):
+                               window: Optional[Tuple[int, int]] = None, sinks: Optional[torch.Tensor] = None):
     """Split-KV attention of PACKED queries over a paged cache (qattn_fp8_attention_paged_varlen_forward, include/qattn_paged_varlen.h).
     q [total_q, Hq, D] bf16 / fp16, dense or a view `paged_varlen_q_addressable` accepts (read in place); cu_seqlens_q int32 [B + 1] and
     seqused_k int32 [B] on the device; the pools, the table and the scales as fp8_attention_paged_splitkv.  num_splits 0: the auto rule on
@@ -1533,6 +1584,7 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
     _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
     mask_args = (int(bool(is_causal)),) if window is None else _window_args(window)
     total_q, Hq, D = q.shape
+    mask_args += _sink_args(sinks, window, Hq, q.device)
     if total_q and not paged_varlen_q_addressable(q):
         q = q.contiguous()
     _require(scale_k.dim() == 2, "scale_k / scale_v must be fp32 [B, Hkv]")
@@ -1573,13 +1625,15 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
             live = lambda t: _ptr(t) if t is not None and t.numel() else None
             dense = (Hq * D, D)     # (a dimension of size 1 has no stride of its own)
             s2 = (ctypes.c_longlong * 2)(*[q.stride(i) if q.shape[i] > 1 else dense[i] for i in (0, 1)])
-            fwd = L.qattn_fp8_attention_paged_varlen_forward if window is None else L.qattn_fp8_attention_paged_varlen_window_forward
+            fwd = (L.qattn_fp8_attention_paged_varlen_forward if window is None else L.qattn_fp8_attention_paged_varlen_window_forward
+                   if sinks is None else L.qattn_fp8_attention_paged_varlen_sink_forward)
             rc = fwd(
                 q.data_ptr(), s2, fmt_of(q.dtype), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), tstride, num_pages, page_size,
                 max_pages, scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), seqused_k.data_ptr(), B, Hq,
                 Hkv, total_q, max_seqlen_q, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), *mask_args, float(sm_scale),
                 _precision(precision), ns, live(q8), _ptr(sq), live(path), live(po), live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_attention_paged_varlen_forward" if window is None else "qattn_fp8_attention_paged_varlen_window_forward")
+    _check(rc, "qattn_fp8_attention_paged_varlen_forward" if window is None else "qattn_fp8_attention_paged_varlen_window_forward"
+           if sinks is None else "qattn_fp8_attention_paged_varlen_sink_forward")
     if not (return_lse or return_partials or return_quant or return_path):
         return out
     return ((out,) + ((lse,) if return_lse else ()) + ((po, plse, ppath) if return_partials else ()) + ((q8, sq) if return_quant else ())

@@ -44,14 +44,17 @@ inline int pvq_most_splits(int Skv, int num_splits) {
 
 
 // WINDOW: the window kernel under (window_left, window_right) in is_causal's place -- also for (-1, 0) and (-1, -1).
-template <bool WINDOW>
+// SINK (with WINDOW; include/qattn_sinks.h): the sink kernel with `sinks` fp32 [Hq], as skv_forward.
+template <bool WINDOW, bool SINK = false>
 int pvq_forward(const void* q16, const long long* q_strides2, int in_fmt, const void* k_pool, const void* v_pool, const int* block_table,
                 long long table_stride, int num_pages, int page_size, int max_pages, const float* scale_k, const float* scale_v, void* out,
                 float* lse, const int* cu_seqlens_q, const int* seqused_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int Skv, int D,
                 int fp8_fmt, int numerics, int is_causal, int window_left, int window_right, float sm_scale, int precision, int num_splits,
                 void* q8, float* scale_q, unsigned char* row_path, float* partial_o, float* partial_lse, unsigned char* partial_path,
-                void* workspace, size_t workspace_bytes, void* stream) {
+                void* workspace, size_t workspace_bytes, void* stream, const float* sinks = nullptr) {
+    static_assert(WINDOW || !SINK, "the sink kernel is a window kernel");
     if (WINDOW && (window_left < -1 || window_right < -1)) return QATTN_ERR_INVALID_ARG;
+    if (SINK && (!sinks || (size_t)sinks % 4 != 0)) return QATTN_ERR_INVALID_ARG;
     // ---- the paging arguments, as qattn_fp8_attention_paged_splitkv_forward
     if (!block_table || !seqused_k || (size_t)block_table % 4 != 0) return QATTN_ERR_INVALID_ARG;
     if (num_pages <= 0 || max_pages <= 0 || Hkv <= 0 || page_size < 64 || page_size % 64 != 0) return QATTN_ERR_INVALID_ARG;
@@ -137,16 +140,17 @@ int pvq_forward(const void* q16, const long long* q_strides2, int in_fmt, const 
     // bound takes total_q for a sequence's query count: cu_seqlens_q is not read on the host, and no sequence holds more (the extents are
     // clamped), whatever max_seqlen_q says
     const int max_keys = skv_max_keys(Skv, total_q, WINDOW ? window_left : -1, ns);
-    const bool want_lse = lse != nullptr || ns > 1;
-    rc = launch_skv<(WINDOW ? kSkvWindow : 0) + kSkvPagedVarq>(a, pg, vq, SkvWindow{window_left, window_right},
-                                                               (unsigned)((long long)Hkv * nt * ns), max_keys, D, fp8_fmt, precision, want_lse, st);
+    const bool want_lse = SINK || lse != nullptr || ns > 1;
+    rc = launch_skv<(SINK ? kSkvSink : 0) + (WINDOW ? kSkvWindow : 0) + kSkvPagedVarq>(
+        a, pg, vq, SkvWindow{window_left, window_right}, (unsigned)((long long)Hkv * nt * ns), max_keys, D, fp8_fmt, precision, want_lse, st,
+        SkvSink{sinks});
     if (rc != QATTN_OK) return rc;
     if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
     if (ns == 1) return QATTN_OK;
 
     // ---- the merge on the packed conventions of include/qattn_merge.h: B = 1, S = total_q
     const long long os3[3] = {0, D, (long long)Hq * D}, ls3[3] = {0, total_q, 1};
-    rc = skv_merge_chain(po, plse, ns, rows, os3, ls3, 1, Hq, total_q, D, out, in_fmt, lse, acc, acc_lse, stream);
+    rc = skv_merge_chain_sink(po, plse, ns, rows, os3, ls3, 1, Hq, total_q, D, out, in_fmt, lse, acc, acc_lse, stream, SINK ? sinks : nullptr);
     if (rc != QATTN_OK) return rc;
     if (row_path) return skv_launch_path(plse, ppath, row_path, rows, ns, st);
     return QATTN_OK;

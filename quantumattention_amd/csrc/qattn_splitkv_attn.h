@@ -9,12 +9,16 @@
 // Three more compilations put a sliding window where `causal` stands (QATTN_SKV_WINDOW; include/qattn_splitkv_window.h): the kernels of
 // qattn_splitkv_window_fp8.hip, qattn_paged_splitkv_window_fp8.hip and qattn_paged_varlen_splitkv_window_fp8.hip, launched through the same
 // ladder and the same drivers.  The window travels as a kernel argument of its own (SkvWindow): SkvAttn is what it was, field for field.
+// And three more add a learned attention sink per query head to the window kernels (QATTN_SKV_SINK; include/qattn_sinks.h): the kernels of
+// qattn_splitkv_sink_fp8.hip, qattn_paged_splitkv_sink_fp8.hip and qattn_paged_varlen_splitkv_sink_fp8.hip, the sink again an argument of
+// its own (SkvSink).
 #pragma once
 #include <limits.h>
 
 #include "qattn_fp8pv_sweep.h"
 #include "qattn_varlen_tile.h"
 #include "../../include/qattn_merge.h"
+#include "../../include/qattn_sinks.h"
 #include "../../include/qattn_splitkv.h"
 
 namespace qattn {
@@ -59,7 +63,13 @@ struct SkvWindow {
     int left, right;
 };
 
-// Physical chunk of chunk `ch` of kv head hkv of the page a RAW table entry names.  The clamp is what keeps every address inside the
+// SINK: learned attention sinks (include/qattn_sinks.h): one logit per QUERY head, fp32 [Hq], in natural-log units of the scaled scores.
+// A kernel argument of its own, as the window: the kernels without a sink keep their kernarg layout.
+struct SkvSink {
+    const float* sink;
+};
+
+// Physical chunk of chunk `ch` of kv head hkv of the page a RAW table entry names. The clamp is what keeps every address inside the
 // pool, whatever the table holds; it is applied here, where the entry forms an address, so that the entry's load can be issued a step
 // ahead of its use without its wait following it.  (Everything is workgroup-uniform.)
 __device__ __forceinline__ int skv_phys(const SkvPages& pg, int entry, int Hkv, int hkv, int ch) {
@@ -128,7 +138,9 @@ void attn_splitkv_fp8_kernel(const SkvAttn a, const int two, const int sel) {
 #define QATTN_SKV_PAGED 0
 #define QATTN_SKV_VARQ 0
 #define QATTN_SKV_WINDOW 0
+#define QATTN_SKV_SINK 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
@@ -140,7 +152,9 @@ void attn_paged_splitkv_fp8_kernel(const SkvAttn a, const SkvPages pg, const int
 #define QATTN_SKV_PAGED 1
 #define QATTN_SKV_VARQ 0
 #define QATTN_SKV_WINDOW 0
+#define QATTN_SKV_SINK 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
@@ -152,7 +166,9 @@ void attn_paged_varlen_splitkv_fp8_kernel(const SkvAttn a, const SkvPages pg, co
 #define QATTN_SKV_PAGED 1
 #define QATTN_SKV_VARQ 1
 #define QATTN_SKV_WINDOW 0
+#define QATTN_SKV_SINK 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
@@ -165,7 +181,9 @@ void attn_splitkv_window_fp8_kernel(const SkvAttn a, const SkvWindow wn, const i
 #define QATTN_SKV_PAGED 0
 #define QATTN_SKV_VARQ 0
 #define QATTN_SKV_WINDOW 1
+#define QATTN_SKV_SINK 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
@@ -177,7 +195,9 @@ void attn_paged_splitkv_window_fp8_kernel(const SkvAttn a, const SkvPages pg, co
 #define QATTN_SKV_PAGED 1
 #define QATTN_SKV_VARQ 0
 #define QATTN_SKV_WINDOW 1
+#define QATTN_SKV_SINK 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
@@ -190,20 +210,77 @@ void attn_paged_varlen_splitkv_window_fp8_kernel(const SkvAttn a, const SkvPages
 #define QATTN_SKV_PAGED 1
 #define QATTN_SKV_VARQ 1
 #define QATTN_SKV_WINDOW 1
+#define QATTN_SKV_SINK 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
 }
 
-// which of the six kernels a launch runs (kSkvWindow + one of the first three: that kernel under a window)
-constexpr int kSkvContig = 0, kSkvPaged = 1, kSkvPagedVarq = 2, kSkvWindow = 4;
+// ... and the three window kernels with a learned sink per query head `sn` (QATTN_SKV_SINK; include/qattn_sinks.h).  Only the exact
+// instances (BYTE = false) are ever launched: the sink entries ask the ladder for the exact one-term sweep under FAST.
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_splitkv_window_sink_fp8_kernel(const SkvAttn a, const SkvWindow wn, const SkvSink sn, const int two, const int sel) {
+#define QATTN_SKV_PAGED 0
+#define QATTN_SKV_VARQ 0
+#define QATTN_SKV_WINDOW 1
+#define QATTN_SKV_SINK 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SINK
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_paged_splitkv_window_sink_fp8_kernel(const SkvAttn a, const SkvPages pg, const SkvWindow wn, const SkvSink sn, const int two,
+                                               const int sel) {
+#define QATTN_SKV_PAGED 1
+#define QATTN_SKV_VARQ 0
+#define QATTN_SKV_WINDOW 1
+#define QATTN_SKV_SINK 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SINK
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_paged_varlen_splitkv_window_sink_fp8_kernel(const SkvAttn a, const SkvPages pg, const SkvVarq vq, const SkvWindow wn,
+                                                      const SkvSink sn, const int two, const int sel) {
+#define QATTN_SKV_PAGED 1
+#define QATTN_SKV_VARQ 1
+#define QATTN_SKV_WINDOW 1
+#define QATTN_SKV_SINK 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SINK
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+// which of the nine kernels a launch runs (kSkvWindow + one of the first three: that kernel under a window; + kSkvSink: with a sink)
+constexpr int kSkvContig = 0, kSkvPaged = 1, kSkvPagedVarq = 2, kSkvWindow = 4, kSkvSink = 8;
 
 template <int D, int FMT, int MODE>
 static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys,
-                          int precision, bool want_lse, hipStream_t st) {
+                          int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}) {
     return fpv_precision_ladder(precision, max_keys, a.two_term_keys, want_lse, [&](auto byte, int two, int sel) {
-        if constexpr (MODE == kSkvWindow + kSkvPagedVarq)
+        if constexpr ((MODE & kSkvSink) != 0) {
+            // (the byte-exponential instances are not compiled for the sink kernels: their callers pass want_lse = true)
+            if constexpr (decltype(byte)::value) return (int)QATTN_ERR_LAUNCH;
+            else if constexpr (MODE == kSkvSink + kSkvWindow + kSkvPagedVarq)
+                return fpv_launch(attn_paged_varlen_splitkv_window_sink_fp8_kernel<D, FMT, false>, grid, fpv_lds_bytes(D), st, a, pg, vq, wn, sn, two,
+                                  sel);
+            else if constexpr (MODE == kSkvSink + kSkvWindow + kSkvPaged)
+                return fpv_launch(attn_paged_splitkv_window_sink_fp8_kernel<D, FMT, false>, grid, fpv_lds_bytes(D), st, a, pg, wn, sn, two, sel);
+            else return fpv_launch(attn_splitkv_window_sink_fp8_kernel<D, FMT, false>, grid, fpv_lds_bytes(D), st, a, wn, sn, two, sel);
+        } else if constexpr (MODE == kSkvWindow + kSkvPagedVarq)
             return fpv_launch(attn_paged_varlen_splitkv_window_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg, vq, wn,
                               two, sel);
         else if constexpr (MODE == kSkvWindow + kSkvPaged)
@@ -220,18 +297,18 @@ static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, const SkvVarq& v
 
 template <int D, int MODE>
 static int launch_skv_d(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys, int fp8_fmt,
-                        int precision, bool want_lse, hipStream_t st) {
-    return fp8_fmt == QATTN_FMT_E4M3 ? launch_skv_fmt<D, QATTN_FMT_E4M3, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st)
-                                     : launch_skv_fmt<D, QATTN_FMT_E5M2, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st);
+                        int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}) {
+    return fp8_fmt == QATTN_FMT_E4M3 ? launch_skv_fmt<D, QATTN_FMT_E4M3, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st, sn)
+                                     : launch_skv_fmt<D, QATTN_FMT_E5M2, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st, sn);
 }
 
 // every head dimension of one entry
 template <int MODE>
 static int launch_skv(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys, int D,
-                      int fp8_fmt, int precision, bool want_lse, hipStream_t st) {
-    if (D == 64) return launch_skv_d<64, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st);
-    if (D == 128) return launch_skv_d<128, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st);
-    return launch_skv_d<256, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st);
+                      int fp8_fmt, int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}) {
+    if (D == 64) return launch_skv_d<64, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn);
+    if (D == 128) return launch_skv_d<128, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn);
+    return launch_skv_d<256, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn);
 }
 
 // Host side of a window (include/qattn_splitkv_window.h).  Under left >= 0 a sequence's interval [lo_i, L) holds at most left + Sq keys,
@@ -290,10 +367,14 @@ int skv_auto_splits_of_tiles(long long tiles, int Skv, int D, int num_cus);
 // follow), then 7 more per launch in place, the last one into out.  os3 / ls3: the element strides (batch, head, query) every partial,
 // the accumulator and the destination share -- dense [B, Hq, Sq, D] / [B, Hq, Sq], or the packed conventions of include/qattn_merge.h with
 // B = 1, Sq = total_q.  acc / acc_lse are read only with ns > QATTN_MERGE_MAX_PARTIALS.
-inline int skv_merge_chain(const float* po, const float* plse, int ns, long rows, const long long (&os3)[3], const long long (&ls3)[3], int B,
-                           int Hq, int Sq, int D, void* out, int out_fmt, float* lse, float* acc, float* acc_lse, void* stream) {
+// skv_merge_chain_sink: the chain with a learned sink per head (include/qattn_sinks.h; nullptr: none, the chain as it always was).  The
+// sink is one more state of the row and may be counted once: it enters the LAST launch only (qattn_attention_state_merge_sink), the
+// launches before it are the plain merge.
+inline int skv_merge_chain_sink(const float* po, const float* plse, int ns, long rows, const long long (&os3)[3], const long long (&ls3)[3],
+                                int B, int Hq, int Sq, int D, void* out, int out_fmt, float* lse, float* acc, float* acc_lse, void* stream,
+                                const float* sink) {
     constexpr int top = QATTN_MERGE_MAX_PARTIALS;
-    auto merge = [&](const float* o0, const float* l0, int first, int n_more, void* dst, int dst_fmt, float* dst_lse) -> int {
+    auto merge = [&](const float* o0, const float* l0, int first, int n_more, void* dst, int dst_fmt, float* dst_lse, bool last) -> int {
         const void* o[top];
         const float* l[top];
         int fmt[top];
@@ -305,29 +386,39 @@ inline int skv_merge_chain(const float* po, const float* plse, int ns, long rows
             fmt[i] = QATTN_FMT_FP32;
             for (int j = 0; j < 3; j++) { ostr[3 * i + j] = os3[j]; lstr[3 * i + j] = ls3[j]; }
         }
+        if (last && sink) return qattn_attention_state_merge_sink(n, o, fmt, ostr, l, lstr, dst, dst_fmt, os3, dst_lse, ls3, B, Hq, Sq, D, stream, sink);
         return qattn_attention_state_merge(n, o, fmt, ostr, l, lstr, dst, dst_fmt, os3, dst_lse, ls3, B, Hq, Sq, D, stream);
     };
-    if (ns <= top) return merge(nullptr, nullptr, 0, ns, out, out_fmt, lse);
-    int rc = merge(nullptr, nullptr, 0, top, acc, QATTN_FMT_FP32, acc_lse);
+    if (ns <= top) return merge(nullptr, nullptr, 0, ns, out, out_fmt, lse, true);
+    int rc = merge(nullptr, nullptr, 0, top, acc, QATTN_FMT_FP32, acc_lse, false);
     int done = top;
     while (rc == QATTN_OK && ns - done > top - 1) {
-        rc = merge(acc, acc_lse, done, top - 1, acc, QATTN_FMT_FP32, acc_lse);
+        rc = merge(acc, acc_lse, done, top - 1, acc, QATTN_FMT_FP32, acc_lse, false);
         done += top - 1;
     }
-    if (rc == QATTN_OK) rc = merge(acc, acc_lse, done, ns - done, out, out_fmt, lse);
+    if (rc == QATTN_OK) rc = merge(acc, acc_lse, done, ns - done, out, out_fmt, lse, true);
     return rc;
+}
+
+inline int skv_merge_chain(const float* po, const float* plse, int ns, long rows, const long long (&os3)[3], const long long (&ls3)[3], int B,
+                           int Hq, int Sq, int D, void* out, int out_fmt, float* lse, float* acc, float* acc_lse, void* stream) {
+    return skv_merge_chain_sink(po, plse, ns, rows, os3, ls3, B, Hq, Sq, D, out, out_fmt, lse, acc, acc_lse, stream, nullptr);
 }
 
 // Both entries, from their common arguments on: k8 / v8 are the contiguous images of [B, Hkv, Skv, D] or -- PAGED, with pg filled in and
 // checked by the caller -- the pools.
 // WINDOW: the window kernels under (window_left, window_right) in is_causal's place -- also for (-1, 0) and (-1, -1).
-template <bool PAGED, bool WINDOW = false>
+// SINK (with WINDOW; include/qattn_sinks.h): the sink kernels with `sinks` fp32 [Hq] on the device -- folded into the sweep's epilogue with
+// one split, into the last launch of the merge chain with more.  Under FAST they take the exact one-term sweep, never the byte one.
+template <bool PAGED, bool WINDOW = false, bool SINK = false>
 int skv_forward(const void* q16, int in_fmt, const void* k8, const void* v8, const SkvPages& pg, const float* scale_k, const float* scale_v,
                 void* out, float* lse, const int* seqused_k, int B, int Hq, int Hkv, int Sq, int Skv, int D, int fp8_fmt, int numerics,
                 int is_causal, float sm_scale, int precision, int num_splits, void* q8, float* scale_q, unsigned char* row_path,
                 float* partial_o, float* partial_lse, unsigned char* partial_path, void* workspace, size_t workspace_bytes, void* stream,
-                int window_left = -1, int window_right = -1) {
+                int window_left = -1, int window_right = -1, const float* sinks = nullptr) {
+    static_assert(WINDOW || !SINK, "the sink kernels are window kernels");
     if (WINDOW && (window_left < -1 || window_right < -1)) return QATTN_ERR_INVALID_ARG;
+    if (SINK && (!sinks || (size_t)sinks % 4 != 0)) return QATTN_ERR_INVALID_ARG;
     if (!q16 || !k8 || !v8 || !scale_k || !scale_v || !out) return QATTN_ERR_INVALID_ARG;
     if (!skv_dims_ok(B, Hq, Hkv, Sq, Skv)) return QATTN_ERR_INVALID_ARG;
     if (!skv_d_ok(D) || Hq % Hkv != 0) return QATTN_ERR_UNSUPPORTED_DIM;
@@ -390,16 +481,16 @@ int skv_forward(const void* q16, int in_fmt, const void* k8, const void* v8, con
     a.sm_log2e = (sm_scale > 0.0f ? sm_scale : 1.0f / sqrtf((float)D)) * 1.4426950408889634f;
     // the most keys a split can own; the sweep asks for the LSE whenever it feeds the merge
     const int max_keys = skv_max_keys(Skv, Sq, WINDOW ? window_left : -1, ns);
-    const bool want_lse = lse != nullptr || ns > 1;
+    const bool want_lse = SINK || lse != nullptr || ns > 1;
     const unsigned grid = (unsigned)((long long)B * Hkv * ntile * ns);
-    rc = launch_skv<(WINDOW ? kSkvWindow : 0) + (PAGED ? kSkvPaged : kSkvContig)>(a, pg, SkvVarq{}, SkvWindow{window_left, window_right}, grid,
-                                                                                 max_keys, D, fp8_fmt, precision, want_lse, st);
+    rc = launch_skv<(SINK ? kSkvSink : 0) + (WINDOW ? kSkvWindow : 0) + (PAGED ? kSkvPaged : kSkvContig)>(
+        a, pg, SkvVarq{}, SkvWindow{window_left, window_right}, grid, max_keys, D, fp8_fmt, precision, want_lse, st, SkvSink{sinks});
     if (rc != QATTN_OK) return rc;
     if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
     if (ns == 1) return QATTN_OK;
 
     const long long os3[3] = {(long long)Hq * Sq * D, (long long)Sq * D, D}, ls3[3] = {(long long)Hq * Sq, Sq, 1};
-    rc = skv_merge_chain(po, plse, ns, rows, os3, ls3, B, Hq, Sq, D, out, in_fmt, lse, acc, acc_lse, stream);
+    rc = skv_merge_chain_sink(po, plse, ns, rows, os3, ls3, B, Hq, Sq, D, out, in_fmt, lse, acc, acc_lse, stream, SINK ? sinks : nullptr);
     if (rc != QATTN_OK) return rc;
     if (row_path) return skv_launch_path(plse, ppath, row_path, rows, ns, st);
     return QATTN_OK;

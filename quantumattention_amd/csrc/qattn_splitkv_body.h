@@ -16,8 +16,14 @@
 // keys below lo_i that share its 64-key chunk are zeroed in LDS (skv_zero_v_head).  a.causal is then not read.  The edge offsets win_lo /
 // win_hi are attn_vfp8_window_kernel's, clamped exactly so that every sum below stays in 32 bits, and padding rows get that kernel's
 // masks: with one split, G = 1 and contiguous K / V the wave-mates, chunks and masks are its own.
-// In scope: template parameters D, FMT, BYTE; arguments a (SkvAttn), two, sel, -- paged -- pg (SkvPages), -- packed queries -- vq and
-// -- window -- wn.
+// QATTN_SKV_SINK (with QATTN_SKV_WINDOW; include/qattn_sinks.h) adds a learned per-head logit `sn.sink[head]` (natural-log units of the
+// scaled scores) to the softmax denominator: 0, the text above, token for token (profiles/sinks/code_objects_vs_parent.log); 1, a call
+// with ONE split folds the sink into the epilogue -- l' = l + exp2(sink log2e - (m c - kPShift)), loaded after the sweep loop so that it
+// lives in no register across it -- and a tile without a key stores zero rows with LSE = sink.  With more splits the partials are written
+// WITHOUT the sink (the statements of the switch-off text): it enters the last launch of the merge chain.  sink = -inf adds 0.0f to l: the
+// row's bits are the window kernel's.  sink = +inf or NaN: the head's rows are NaN.
+// In scope: template parameters D, FMT, BYTE; arguments a (SkvAttn), two, sel, -- paged -- pg (SkvPages), -- packed queries -- vq,
+// -- window -- wn and -- sink -- sn (SkvSink).
 #if QATTN_SKV_VARQ
 #define SKV_SQ Sq_i
 #define SKV_ROWS rows_i
@@ -25,6 +31,7 @@
 #define SKV_QROW0 qrow0   // ... and the first row of the kv head's group: what a padding lane reads
 #define SKV_OROW orow     // row of the token-major [total_q, Hq] space: out, partial_o
 #define SKV_LROW lrow     // row of the head-major [Hq, total_q] space: lse, row_path, partial_lse, partial_path
+#define SKV_HEAD head     // this lane's query head: the sink's index
 #else
 #define SKV_SQ a.Sq
 #define SKV_ROWS a.rows
@@ -32,6 +39,7 @@
 #define SKV_QROW0 ((long)kvh * a.rows)
 #define SKV_OROW grow
 #define SKV_LROW grow
+#define SKV_HEAD ((kvh % a.Hkv) * a.G + g)
 #endif
     constexpr int CH = 64 * D, MB = D / 32, KS = D / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -113,7 +121,21 @@
 #endif
     if (keys == 0) {   // no key for any row of the tile in this split (L = 0, a split past the last block, a split above the causal edge)
         if (a.ns == 1) {
+#if QATTN_SKV_SINK
+            // the sink alone: zero rows with LSE = sink (-inf: the window kernel's empty row); +inf and NaN make the rows NaN
+            const float snk = sn.sink[SKV_HEAD];
+            const float sink1 = snk < INFINITY ? snk : NAN;
+            v16f z[MB];
+#pragma unroll
+            for (int m = 0; m < MB; m++)
+#pragma unroll
+                for (int e = 0; e < 16; e++) z[m][e] = 0.0f;
+            store_o_rows<MB>(a.out, a.out_fmt, z, sink1 != sink1 ? sink1 : 0.0f, (rvalid ? SKV_OROW : 0L) * (2L * D), hh, rvalid);
+            if (a.lse && hh == 0 && rvalid) a.lse[SKV_LROW] = sink1;
+            if (a.path && hh == 0 && rvalid) a.path[SKV_LROW] = (unsigned char)QATTN_PATH_ONE_TERM;
+#else
             fpv_store_empty<D>(a.out, a.out_fmt, (rvalid ? SKV_OROW : 0L) * (2L * D), a.lse, SKV_LROW, a.path, SKV_LROW, hh, rvalid);
+#endif
         } else {
             const long prow = (long)s * a.part_rows + (rvalid ? SKV_OROW : 0L), plrow = (long)s * a.part_rows + (rvalid ? SKV_LROW : 0L);
             v16f z[MB];
@@ -238,9 +260,36 @@
     const float lse_row = has_key ? 0.6931471805599453f * (sw.m_run * sw.c - kPShift) + __logf(l_tot) : -INFINITY;
     const unsigned char code = (unsigned char)((!BYTE && two) ? QATTN_PATH_TWO_TERM : QATTN_PATH_ONE_TERM);
     if (a.ns == 1) {
+#if QATTN_SKV_SINK
+        // The sink joins the row's sum under the sweep's own shift: P' = 2^(x c - base), base = m_run c - kPShift, so the sink's term is
+        // e = 2^(sink log2e - base).  (Loaded here, after the loop; a padding row reads the sink of head G - 1 and stores nothing.)
+        const float snk = sn.sink[SKV_HEAD];
+        const float sink1 = snk < INFINITY ? snk : NAN;   // +inf, NaN: the head's rows are NaN
+        float inv_s, lse_s;
+        if (has_key) {
+            const float d = sink1 * 1.4426950408889634f - (sw.m_run * sw.c - kPShift);
+            if (d > 64.0f) {   // a sink far above every score: sum under the SINK's shift instead, so that e cannot overflow
+                const float r = __builtin_amdgcn_exp2f(-d);
+                const float l_s = l_tot * r + 1.0f;
+                inv_s = a.sv[kvh] * r / l_s;
+                lse_s = sink1 + __logf(l_s);
+            } else {           // (sink = -inf: e = 0, and l_tot + 0.0f is l_tot -- the bits of the kernel without a sink)
+                const float l_s = l_tot + __builtin_amdgcn_exp2f(d);
+                inv_s = a.sv[kvh] / l_s;
+                lse_s = 0.6931471805599453f * (sw.m_run * sw.c - kPShift) + __logf(l_s);
+            }
+        } else {               // no key for this row (m_run may still stand at its start value: it is not read): the sink alone
+            inv_s = sink1 != sink1 ? sink1 : 0.0f;
+            lse_s = sink1;
+        }
+        store_o_rows<MB>(a.out, a.out_fmt, sw.o, inv_s, (rvalid ? SKV_OROW : 0L) * (2L * D), hh, rvalid);
+        if (!BYTE && a.lse && hh == 0 && rvalid) a.lse[SKV_LROW] = lse_s;
+        if (a.path && hh == 0 && rvalid) a.path[SKV_LROW] = code;
+#else
         store_o_rows<MB>(a.out, a.out_fmt, sw.o, inv, (rvalid ? SKV_OROW : 0L) * (2L * D), hh, rvalid);
         if (!BYTE && a.lse && hh == 0 && rvalid) a.lse[SKV_LROW] = lse_row;
         if (a.path && hh == 0 && rvalid) a.path[SKV_LROW] = code;
+#endif
     } else {
         const long prow = (long)s * a.part_rows + (rvalid ? SKV_OROW : 0L), plrow = (long)s * a.part_rows + (rvalid ? SKV_LROW : 0L);
         store_o_rows_f32<MB>(a.po + prow * D, sw.o, inv, hh, rvalid);
@@ -253,3 +302,4 @@
 #undef SKV_QROW0
 #undef SKV_OROW
 #undef SKV_LROW
+#undef SKV_HEAD

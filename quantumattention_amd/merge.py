@@ -20,19 +20,34 @@ _STATE_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
 _MERGE_HEAD_DIMS = (64, 128, 256)
 
 
-def merge_attn_states_eager(outs: Sequence[torch.Tensor], lses: Sequence[torch.Tensor], out_dtype: Optional[torch.dtype] = None):
+def sink_or_nan(sinks: torch.Tensor) -> torch.Tensor:
+    """fp32 sinks with +inf replaced by NaN: a sink of +inf or NaN makes its head's rows NaN (include/qattn_sinks.h)."""
+    s = sinks.to(torch.float32)
+    return torch.where(s < math.inf, s, torch.full_like(s, math.nan))
+
+
+def merge_attn_states_eager(outs: Sequence[torch.Tensor], lses: Sequence[torch.Tensor], out_dtype: Optional[torch.dtype] = None, *,
+                            sinks: Optional[torch.Tensor] = None):
     """The merge in torch ops on the tensors' device: the definition the HIP kernel implements and the reference implementation of the op
     `quantumattention_amd::attention_state_merge` -- fp32, m = max_i lse_i, e_i = exp(lse_i - m), partials summed in index order, one
     rounding to out_dtype.  A partial of weight zero (lse_i = -inf) contributes nothing whatever its rows hold; rows whose partials are
-    all at -inf are zero rows with an LSE of -inf; an LSE of +inf or NaN makes the row NaN.  Returns (out, lse), both dense."""
+    all at -inf are zero rows with an LSE of -inf; an LSE of +inf or NaN makes the row NaN.  Returns (out, lse), both dense.
+    sinks (fp32 [H], None: none): the definition of `quantumattention_amd::attention_state_merge_sink` (include/qattn_sinks.h) -- the
+    head's sink is one more state with LSE sink_h and no O row: it joins m, is summed into den after the partials, and a row whose
+    partials are all at -inf is a zero row with LSE sink_h."""
     packed = lses[0].dim() == 2
     L = torch.stack([l.to(torch.float32) for l in lses])
     m = L.max(dim=0).values                                   # (propagates NaN)
+    if sinks is not None:
+        snk = sink_or_nan(sinks)[:, None] if packed else sink_or_nan(sinks)[None, :, None]
+        m = torch.where((snk > m) | (snk != snk), snk.expand_as(m), m)
     empty = m == -math.inf
     e = torch.exp(L - torch.where(empty, torch.zeros_like(m), m))   # an empty row: exp(-inf - 0) = 0 for every partial
     den = e[0].clone()
     for i in range(1, len(lses)):
         den = den + e[i]
+    if sinks is not None:
+        den = den + torch.exp(snk - torch.where(empty, torch.zeros_like(m), m))
     rows = (lambda w: w.transpose(0, 1)[..., None]) if packed else (lambda w: w[..., None])   # a per-row figure over the rows of O
     acc = None
     for i, o in enumerate(outs):

@@ -117,7 +117,7 @@ def _resolve_varlen_splits(num_splits: int, B: int, Hq: int, Hkv: int, total_q: 
     return _native.paged_varlen_auto_splits(B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, cus)
 
 
-def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, ns, precision, window=None):
+def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, ns, precision, sinks=None, window=None):
     """CPU tensors and config.attention.force_eager_fallback: per sequence slot, splitkv._splitkv_eager on the slot's queries and on its
     keys gathered through the table, scattered into the packed outputs.  Rows of tokens that belong to no sequence: zeros.  (This path
     reads cu_seqlens_q, seqused_k and the table on the host.)"""
@@ -141,7 +141,7 @@ def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, 
         one = PreparedKV(kv.k[b:b + 1], kv.v[b:b + 1], kv.scale_k[b:b + 1], kv.scale_v[b:b + 1], (1,) + tuple(kv.shape[1:]), kv.fp8_format,
                          kv.dtype, kv.numerics, "rowmajor")
         o, l, p_o, p_l, p_p = _splitkv_eager(q[start:end].transpose(0, 1)[None], one, causal, scale, seqused_k[b:b + 1], ns, precision,
-                                             window)
+                                             sinks, window)
         out[start:end] = o[0].transpose(0, 1)
         lse[:, start:end] = l[0]
         if n:

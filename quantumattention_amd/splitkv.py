@@ -190,14 +190,17 @@ def split_plan_window(L: int, Sq: int, window_left: int, num_splits: int):
     return [(min(BLOCK_N * (kb0 + s * per), L), min(BLOCK_N * (kb0 + (s + 1) * per), L)) for s in range(num_splits)]
 
 
-def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, window=None):
+def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, sinks=None, window=None):
     """CPU tensors and config.attention.force_eager_fallback: the torch definition.  The eager quantiser on q (head-wise), the prepared
     row-major bytes de-quantised; per split an fp32 softmax partial (o_s, lse_s) over the split's keys of every batch element's first L_b
     keys -- a row without a key there: a zero row, LSE -inf --, then merge.merge_attn_states_eager.  The path bytes restate the kernel's
     rule per (kv head, 128-row tile of packed rows, split).  Returns (out, lse, partial_o, partial_lse, partial_path); with one split the
     partials are empty.  (This path reads seqused_k on the host.)
     window = (left, right): the definition of the window entries (include/qattn_splitkv_window.h) -- `causal` is not read; the splits are
-    split_plan_window's, position p keeps the keys p + delta - left .. p + delta + right, and the path byte counts the keys klo .. khi."""
+    split_plan_window's, position p keeps the keys p + delta - left .. p + delta + right, and the path byte counts the keys klo .. khi.
+    sinks = fp32 [Hq] (None: none): the definition of the sink entries (include/qattn_sinks.h) -- one split: the row's LSE becomes
+    L = logaddexp(lse, sink_h) and the weights exp(score - L), an empty row a zero row with LSE = sink_h; more splits: the partials stay
+    free of the sink and it enters merge.merge_attn_states_eager once.  +inf and NaN make the head's rows NaN."""
     fp8_dtype = _native.fp8_dtype_of(kv.fp8_format)
     B, Hq, Sq, D = q.shape
     _, Hkv, Skv, _ = kv.shape
@@ -243,6 +246,8 @@ def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, window=None):
                 path[s, b].view(Hkv, G * Sq)[:, r0:r1 + 1] = code
         sc = s_all.masked_fill(~keep, -math.inf)
         lse = torch.logsumexp(sc, dim=-1)
+        if sinks is not None and ns == 1:
+            lse = torch.logaddexp(lse, merge.sink_or_nan(sinks)[None, :, None])
         p = torch.exp(sc - lse.clamp_min(torch.finfo(torch.float32).min)[..., None])   # (a row without keys: exp(-inf) = 0)
         # a key no row of the split attends enters with V = 0, not with its bytes: 0 * NaN would make the row NaN, and bytes behind
         # seqused_k or below a window influence no output bit (the kernels never load them)
@@ -251,7 +256,7 @@ def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, window=None):
     if ns == 1:
         e = lambda dt: torch.empty((0,), dtype=dt, device=q.device)
         return outs[0].to(q.dtype), lses[0], e(torch.float32), e(torch.float32), e(torch.uint8)
-    out, lse = merge.merge_attn_states_eager(outs, lses, q.dtype)
+    out, lse = merge.merge_attn_states_eager(outs, lses, q.dtype, sinks=sinks)
     return out, lse, torch.stack(outs), torch.stack(lses), path
 
 

@@ -15,8 +15,8 @@ The window kernels sweep -- and split -- only the keys a sequence's queries can 
 max(L - Sq - left, 0), not [0, L) (`split_plan_window`), and no chunk and no block-table entry outside it is read.  They always run, also
 for (-1, 0) and (-1, -1), where every output bit is the sibling's.
 
-Package attributes, not names of `__all__`.  Not offered: learned attention sinks, "sink tokens + window" in one call (two calls and
-`merge_attn_states`: INTEGRATION.md section 2e), windows on the 16-bit-P.V numerics."""
+Package attributes, not names of `__all__`.  Learned attention sinks (gpt-oss): the siblings of `sinks.py`.  Not offered: "sink tokens +
+window" in one call (two calls and `merge_attn_states`: INTEGRATION.md section 2e), windows on the 16-bit-P.V numerics."""
 from typing import Optional, Tuple
 
 import torch
@@ -114,7 +114,7 @@ def fp8_attn_splitkv_window_func(q, kv, window_size, *, scale: Optional[float] =
     if eager:
         if kv.layout != "rowmajor":
             raise ValueError("the eager definition needs a PreparedKV made on CPU tensors or under config.attention.force_eager_fallback")
-        res = _splitkv_eager(q, kv, False, scale, seqused_k, ns, precision, (left, right))
+        res = _splitkv_eager(q, kv, False, scale, seqused_k, ns, precision, window=(left, right))
     else:
         if kv.layout != "frag":
             raise ValueError("this PreparedKV holds row-major bytes for the eager definition; prepare it on the device without "
@@ -151,7 +151,7 @@ def fp8_attn_paged_window_func(q, cache: PagedKVCacheFP8, window_size, *, scale:
     if eager:
         if cache.layout != "rowmajor":
             raise ValueError("the eager definition needs a cache made on a CPU device or under config.attention.force_eager_fallback")
-        res = _attend_eager(q, cache, False, scale, used, Skv, ns, precision, (left, right))
+        res = _attend_eager(q, cache, False, scale, used, Skv, ns, precision, window=(left, right))
     else:
         if cache.layout != "frag":
             raise ValueError("this cache holds row-major bytes for the eager definition; make it on the device without "
@@ -188,7 +188,7 @@ def fp8_attn_paged_varlen_window_func(q, cache: PagedKVCacheFP8, cu_seqlens_q: T
     if eager:
         if cache.layout != "rowmajor":
             raise ValueError("the eager definition needs a cache made on a CPU device or under config.attention.force_eager_fallback")
-        res = _attend_varlen_eager(q, cache, cu_seqlens_q, False, scale, used, Skv, ns, precision, (left, right))
+        res = _attend_varlen_eager(q, cache, cu_seqlens_q, False, scale, used, Skv, ns, precision, window=(left, right))
     else:
         if cache.layout != "frag":
             raise ValueError("this cache holds row-major bytes for the eager definition; make it on the device without "
