@@ -315,10 +315,12 @@ def grade_step(st, out, lse, ref):
     return worst, worst_lse
 
 
-def state_failures(trace, st, shadow, lens, pool_rows, gathered=None, product_dead=None):
+def state_failures(trace, st, shadow, lens, pool_rows, gathered=None, product_dead=None, k_rule=None):
     """what is wrong with the cache after a step, as a list of strings (empty: nothing).  lens: the cache's seqlens; pool_rows: (K, V)
     row-major uint8 numpy [P, HKV, page_size, D] of the pools, looked up key by key through the shadow's table (paged_cases.gather_rows) --
-    or `gathered`, (K, V) [B, HKV, >= L, D], for the contiguous cache; product_dead: the product's dead-page counts on a windowed trace."""
+    or `gathered`, (K, V) [B, HKV, >= L, D], for the contiguous cache; product_dead: the product's dead-page counts on a windowed trace.
+    k_rule (tests/serving_trace_rope_sinks.py): what the live K bytes are held to in place of equality, k_rule(got, want, [(lo_b, hi_b)])
+    -> strings; V and everything else stay exact."""
     bad = []
     ps = trace.page_size
     if list(lens) != list(st.lens1):
@@ -326,8 +328,11 @@ def state_failures(trace, st, shadow, lens, pool_rows, gathered=None, product_de
     nan = PC.NAN_BYTE[shadow.cfg.fmt]
     for name, want, rows in (("K", shadow.k8, 0), ("V", shadow.v8, 1)):
         got = gathered[rows] if gathered is not None else PC.gather_rows(pool_rows[rows], st.table, ps)
-        for b in range(B):
-            lo, hi = st.evicted[b] * ps, st.lens1[b]
+        spans = [(st.evicted[b] * ps, st.lens1[b]) for b in range(B)]
+        if name == "K" and k_rule is not None:
+            bad += k_rule(got, want, spans)
+            spans = []
+        for b, (lo, hi) in enumerate(spans):
             if not np.array_equal(got[b][:, lo:hi], want[b][:, lo:hi]):
                 keys = np.nonzero((got[b][:, lo:hi] != want[b][:, lo:hi]).any((0, 2)))[0] + lo
                 bad.append(f"{name} bytes of slot {b}: {len(keys)} live keys differ, first {int(keys[0])}")
