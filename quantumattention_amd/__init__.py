@@ -68,6 +68,9 @@ from .sinks import (  # noqa: E402
     fp8_attn_splitkv_sink_func,
     merge_attn_states_with_sinks,
 )
+# tree-shaped speculative decoding on the paged cache: the verify pass under a draft tree and the compaction of the accepted path
+# (include/qattn_paged_varlen_tree.h): package attributes, not in __all__
+from .tree import fp8_attn_paged_varlen_tree_func, paged_kv_cache_compact_fp8, tree_mask_from_parents  # noqa: E402
 
 __version__ = "0.1.0"
 

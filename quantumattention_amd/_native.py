@@ -61,6 +61,7 @@ EXPORTS = (
     "qattn_paged_kv_cache_append_varlen_rope_fp8", "qattn_rope_paged_varlen",
     "qattn_attention_state_merge_sink", "qattn_fp8_attention_splitkv_sink_forward", "qattn_fp8_attention_paged_splitkv_sink_forward",
     "qattn_fp8_attention_paged_varlen_sink_forward",
+    "qattn_fp8_attention_paged_varlen_tree_forward", "qattn_paged_kv_cache_compact_fp8",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -306,6 +307,14 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_attention_paged_varlen_sink_forward.restype = i
     L.qattn_fp8_attention_paged_varlen_sink_forward.argtypes = [vp, vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i,
                                                                 i, i, i, vp, f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    # tree-shaped speculative decoding (include/qattn_paged_varlen_tree.h): the packed paged entry's arguments with tree_mask in is_causal's
+    # place; k_pool, v_pool, block_table, table_stride, seqlens, cu_seqlens, accept_index, accept_lens, B, Hkv, total, num_pages, page_size,
+    # max_pages, D, stream
+    L.qattn_fp8_attention_paged_varlen_tree_forward.restype = i
+    L.qattn_fp8_attention_paged_varlen_tree_forward.argtypes = [vp, vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i,
+                                                                i, vp, f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.qattn_paged_kv_cache_compact_fp8.restype = i
+    L.qattn_paged_kv_cache_compact_fp8.argtypes = [vp, vp, vp, ll, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1416,6 +1425,40 @@ def paged_kv_cache_append_varlen_fp8(k_pool: torch.Tensor, v_pool: torch.Tensor,
     _check(rc, "qattn_paged_kv_cache_append_varlen_fp8")
 
 
+def paged_kv_cache_compact_fp8(k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, seqlens: torch.Tensor,
+                               cu_seqlens: torch.Tensor, accept_index: torch.Tensor, accept_lens: torch.Tensor, *, Hkv: int, D: int,
+                               num_pages: int, page_size: int) -> None:
+    """qattn_paged_kv_cache_compact_fp8 (include/qattn_paged_varlen_tree.h): in every compactable slot the accepted draft keys
+    accept_index[cu[b] + i], i < accept_lens[b], become the keys base + i, base = seqlens[b] - (cu[b + 1] - cu[b]), and seqlens[b] becomes
+    base + accept_lens[b].  Everything is read on the device.  Mutates k_pool, v_pool and seqlens."""
+    dev = k_pool.device
+    _require(k_pool.is_cuda, "the pools must be device tensors")
+    _require(isinstance(page_size, int) and page_size >= 64 and page_size % 64 == 0, f"page_size must be a positive multiple of 64, got {page_size}")
+    _require(isinstance(num_pages, int) and num_pages > 0, f"num_pages must be positive, got {num_pages}")
+    L = lib()
+    for name, img, layout in (("k", k_pool, LAYOUT_KFRAG), ("v", v_pool, LAYOUT_VFRAG)):
+        _require(img.device == dev and img.dtype == torch.uint8 and img.is_contiguous()
+                 and img.numel() == L.qattn_fp8_tensor_bytes(layout, num_pages, Hkv, page_size, D),
+                 f"the {name} pool does not fit [num_pages={num_pages}, Hkv={Hkv}, page_size={page_size}, D={D}]")
+    _require(block_table.dtype == torch.int32 and block_table.device == dev and block_table.dim() == 2 and block_table.shape[1] > 0
+             and block_table.stride(1) == 1 and (block_table.shape[0] == 1 or block_table.stride(0) >= block_table.shape[1]),
+             f"block_table must be an int32 [B, max_pages] tensor on {dev} with dense rows")
+    B, max_pages = block_table.shape
+    tstride = block_table.stride(0) if B > 1 else max_pages
+    total = accept_index.shape[0] if accept_index.dim() == 1 else -1
+    for name, t, shape in (("seqlens", seqlens, (B,)), ("cu_seqlens", cu_seqlens, (B + 1,)), ("accept_lens", accept_lens, (B,)),
+                           ("accept_index", accept_index, (total,))):
+        _require(t.dtype == torch.int32 and t.device == dev and tuple(t.shape) == shape and t.is_contiguous(),
+                 f"{name} must be a dense int32 {list(shape)} tensor on {dev}")
+    if total == 0:
+        return
+    with torch.cuda.device(dev):
+        rc = L.qattn_paged_kv_cache_compact_fp8(k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), tstride, seqlens.data_ptr(),
+                                                cu_seqlens.data_ptr(), accept_index.data_ptr(), accept_lens.data_ptr(), B, Hkv, total,
+                                                num_pages, page_size, max_pages, D, torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "qattn_paged_kv_cache_compact_fp8")
+
+
 def _paged_rope_tables(cos: torch.Tensor, sin: torch.Tensor, dev, D: int):
     """cos / sin fp32 [T, D/2] as include/qattn_paged_varlen_rope.h takes them: (T, row stride in floats).  Read in place: no copy is made."""
     for name, t in (("cos", cos), ("sin", sin)):
@@ -1572,19 +1615,27 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
                                num_pages: int, page_size: int, fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled",
                                is_causal: bool = False, sm_scale: float = 0.0, precision: str = "accurate", num_splits: int = 0,
                                return_lse: bool = False, return_partials: bool = False, return_quant: bool = False, return_path: bool = False,
-                               window: Optional[Tuple[int, int]] = None, sinks: Optional[torch.Tensor] = None):
+                               window: Optional[Tuple[int, int]] = None, sinks: Optional[torch.Tensor] = None,
+                               tree_mask: Optional[torch.Tensor] = None):
     """Split-KV attention of PACKED queries over a paged cache (qattn_fp8_attention_paged_varlen_forward, include/qattn_paged_varlen.h).
     q [total_q, Hq, D] bf16 / fp16, dense or a view `paged_varlen_q_addressable` accepts (read in place); cu_seqlens_q int32 [B + 1] and
     seqused_k int32 [B] on the device; the pools, the table and the scales as fp8_attention_paged_splitkv.  num_splits 0: the auto rule on
     the device's CU count (resolved here, on the host).  Returns out [total_q, Hq, D], or a tuple of out, [lse [Hq, total_q]], [partial_o
     fp32 [ns, total_q, Hq, D], partial_lse [ns, Hq, total_q], partial_path uint8 -- three empty tensors when the call ran one split],
-    [q8 [Hq total_q D] flat, scale_q [B, Hq]], [row_path uint8 [Hq, total_q]]."""
+    [q8 [Hq total_q D] flat, scale_q [B, Hq]], [row_path uint8 [Hq, total_q]].
+    tree_mask (int64 [total_q] on the device; without window / sinks): qattn_fp8_attention_paged_varlen_tree_forward
+    (include/qattn_paged_varlen_tree.h) -- the causal call under a draft tree per slot; is_causal is not read."""
     _require(precision in ("fast", "accurate"), f"Unsupported precision for the split-KV entry: {precision!r} (expected 'fast' or 'accurate')")
     _require(q.is_cuda and q.dim() == 3 and q.dtype in (torch.bfloat16, torch.float16), "query must be a 3-D bf16 / fp16 device tensor [total_q, Hq, D]")
     _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
     mask_args = (int(bool(is_causal)),) if window is None else _window_args(window)
     total_q, Hq, D = q.shape
     mask_args += _sink_args(sinks, window, Hq, q.device)
+    if tree_mask is not None:
+        _require(window is None and sinks is None, "a tree mask is offered without a window and without sinks")
+        _require(tree_mask.dtype == torch.int64 and tree_mask.device == q.device and tuple(tree_mask.shape) == (total_q,)
+                 and tree_mask.is_contiguous(), f"tree_mask must be a dense int64 [total_q={total_q}] tensor on {q.device}")
+        mask_args = (tree_mask.data_ptr(),)
     if total_q and not paged_varlen_q_addressable(q):
         q = q.contiguous()
     _require(scale_k.dim() == 2, "scale_k / scale_v must be fp32 [B, Hkv]")
@@ -1625,14 +1676,16 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
             live = lambda t: _ptr(t) if t is not None and t.numel() else None
             dense = (Hq * D, D)     # (a dimension of size 1 has no stride of its own)
             s2 = (ctypes.c_longlong * 2)(*[q.stride(i) if q.shape[i] > 1 else dense[i] for i in (0, 1)])
-            fwd = (L.qattn_fp8_attention_paged_varlen_forward if window is None else L.qattn_fp8_attention_paged_varlen_window_forward
+            fwd = (L.qattn_fp8_attention_paged_varlen_tree_forward if tree_mask is not None
+                   else L.qattn_fp8_attention_paged_varlen_forward if window is None else L.qattn_fp8_attention_paged_varlen_window_forward
                    if sinks is None else L.qattn_fp8_attention_paged_varlen_sink_forward)
             rc = fwd(
                 q.data_ptr(), s2, fmt_of(q.dtype), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), tstride, num_pages, page_size,
                 max_pages, scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), seqused_k.data_ptr(), B, Hq,
                 Hkv, total_q, max_seqlen_q, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), *mask_args, float(sm_scale),
                 _precision(precision), ns, live(q8), _ptr(sq), live(path), live(po), live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_attention_paged_varlen_forward" if window is None else "qattn_fp8_attention_paged_varlen_window_forward"
+    _check(rc, "qattn_fp8_attention_paged_varlen_tree_forward" if tree_mask is not None
+           else "qattn_fp8_attention_paged_varlen_forward" if window is None else "qattn_fp8_attention_paged_varlen_window_forward"
            if sinks is None else "qattn_fp8_attention_paged_varlen_sink_forward")
     if not (return_lse or return_partials or return_quant or return_path):
         return out

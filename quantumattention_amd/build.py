@@ -23,7 +23,8 @@ AB_LIBS = os.path.join(os.path.dirname(HERE), "tools", "ab_libs")
 SOURCES = ["qattn_quant.hip", "qattn_attn_v2.hip", "qattn_attn_v4.hip", "qattn_attn16.hip", "qattn_api.hip", "qattn_probe.hip", "qattn_attn_pv16.hip", "qattn_varlen.hip",
            "qattn_block_sparse.hip", "qattn_block_sparse_fp8.hip", "qattn_smooth_k.hip", "qattn_varlen_smooth.hip", "qattn_varlen_window.hip", "qattn_varlen_fp8.hip", "qattn_varlen_window_fp8.hip", "qattn_merge.hip", "qattn_rope_quant.hip", "qattn_splitkv_fp8.hip", "qattn_kvcache_append.hip", "qattn_paged_splitkv_fp8.hip", "qattn_paged_append.hip", "qattn_paged_varlen_splitkv_fp8.hip",
            "qattn_splitkv_window_fp8.hip", "qattn_paged_splitkv_window_fp8.hip", "qattn_paged_varlen_splitkv_window_fp8.hip", "qattn_paged_varlen_append.hip", "qattn_paged_varlen_rope_append.hip",
-           "qattn_merge_sink.hip", "qattn_splitkv_sink_fp8.hip", "qattn_paged_splitkv_sink_fp8.hip", "qattn_paged_varlen_splitkv_sink_fp8.hip"]
+           "qattn_merge_sink.hip", "qattn_splitkv_sink_fp8.hip", "qattn_paged_splitkv_sink_fp8.hip", "qattn_paged_varlen_splitkv_sink_fp8.hip",
+           "qattn_paged_varlen_splitkv_tree_fp8.hip", "qattn_paged_compact.hip"]
 # (source, extra flags, object name): the two big kernel files are compiled once per operand format / head dimension so that
 # the build runs in parallel (the longest single translation unit sets the wall time)
 # (a unit with a define is compiled through a two-line wrapper file named after the unit, so that -save-temps leaves one .s
@@ -74,6 +75,9 @@ UNITS = [
     ("qattn_splitkv_sink_fp8.hip", [], "qattn_splitkv_sink_fp8"),
     ("qattn_paged_splitkv_sink_fp8.hip", [], "qattn_paged_splitkv_sink_fp8"),
     ("qattn_paged_varlen_splitkv_sink_fp8.hip", [], "qattn_paged_varlen_splitkv_sink_fp8"),
+    # tree-shaped speculative decoding (include/qattn_paged_varlen_tree.h): the packed paged sweep under a draft tree, and the compaction of the accepted path
+    ("qattn_paged_varlen_splitkv_tree_fp8.hip", [], "qattn_paged_varlen_splitkv_tree_fp8"),
+    ("qattn_paged_compact.hip", [], "qattn_paged_compact"),
 ]
 # (Until round 5 `--dev` built a second library with -DQATTN_DEV: timing-only ablation instantiations, per-segment cycle stamps, work logs and
 # QATTN_* environment switches.  Round 6 took that scaffolding out of the sources -- identical product ISA, profiles/r06/isa_identity_*.log;
@@ -118,7 +122,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = False, 
     os.makedirs(build_dir, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("qattn.h", "qattn_measure.h", "qattn_varlen.h", "qattn_block_sparse.h", "qattn_smooth.h", "qattn_window.h", "qattn_merge.h", "qattn_rope.h", "qattn_splitkv.h", "qattn_kvcache.h", "qattn_paged.h", "qattn_paged_varlen.h", "qattn_splitkv_window.h", "qattn_paged_varlen_append.h", "qattn_paged_varlen_rope.h", "qattn_sinks.h")]
+    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("qattn.h", "qattn_measure.h", "qattn_varlen.h", "qattn_block_sparse.h", "qattn_smooth.h", "qattn_window.h", "qattn_merge.h", "qattn_rope.h", "qattn_splitkv.h", "qattn_kvcache.h", "qattn_paged.h", "qattn_paged_varlen.h", "qattn_splitkv_window.h", "qattn_paged_varlen_append.h", "qattn_paged_varlen_rope.h", "qattn_sinks.h", "qattn_paged_varlen_tree.h")]
     objs, jobs = [], []
     for src, defines, name in UNITS:
         s = os.path.join(CSRC, src)

@@ -45,14 +45,19 @@ inline int pvq_most_splits(int Skv, int num_splits) {
 
 // WINDOW: the window kernel under (window_left, window_right) in is_causal's place -- also for (-1, 0) and (-1, -1).
 // SINK (with WINDOW; include/qattn_sinks.h): the sink kernel with `sinks` fp32 [Hq], as skv_forward.
-template <bool WINDOW, bool SINK = false>
+// TREE (without WINDOW; include/qattn_paged_varlen_tree.h): the tree kernel under `tree_mask`, one 64-bit word per packed token on the
+// device; the call is causal whatever is_causal says.
+template <bool WINDOW, bool SINK = false, bool TREE = false>
 int pvq_forward(const void* q16, const long long* q_strides2, int in_fmt, const void* k_pool, const void* v_pool, const int* block_table,
                 long long table_stride, int num_pages, int page_size, int max_pages, const float* scale_k, const float* scale_v, void* out,
                 float* lse, const int* cu_seqlens_q, const int* seqused_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int Skv, int D,
                 int fp8_fmt, int numerics, int is_causal, int window_left, int window_right, float sm_scale, int precision, int num_splits,
                 void* q8, float* scale_q, unsigned char* row_path, float* partial_o, float* partial_lse, unsigned char* partial_path,
-                void* workspace, size_t workspace_bytes, void* stream, const float* sinks = nullptr) {
+                void* workspace, size_t workspace_bytes, void* stream, const float* sinks = nullptr,
+                const unsigned long long* tree_mask = nullptr) {
     static_assert(WINDOW || !SINK, "the sink kernel is a window kernel");
+    static_assert(!TREE || !WINDOW, "the tree kernel is the causal kernel");
+    if (TREE && (!tree_mask || (size_t)tree_mask % 8 != 0)) return QATTN_ERR_INVALID_ARG;
     if (WINDOW && (window_left < -1 || window_right < -1)) return QATTN_ERR_INVALID_ARG;
     if (SINK && (!sinks || (size_t)sinks % 4 != 0)) return QATTN_ERR_INVALID_ARG;
     // ---- the paging arguments, as qattn_fp8_attention_paged_splitkv_forward
@@ -129,7 +134,7 @@ int pvq_forward(const void* q16, const long long* q_strides2, int in_fmt, const 
     a.out_fmt = in_fmt; a.Hkv = Hkv; a.G = G; a.Skv = Skv;
     a.ntile = (int)nt;   // (Sq and rows are per sequence: read from cu_seqlens_q on the device)
     a.ns = ns; a.nchunks = ceil_div(Skv, 64);
-    a.causal = is_causal ? 1 : 0;
+    a.causal = (TREE || is_causal) ? 1 : 0;
     a.two_term_keys = kTwoTermKeys;
     a.sm_log2e = (sm_scale > 0.0f ? sm_scale : 1.0f / sqrtf((float)D)) * 1.4426950408889634f;
     SkvPages pg;
@@ -141,9 +146,9 @@ int pvq_forward(const void* q16, const long long* q_strides2, int in_fmt, const 
     // clamped), whatever max_seqlen_q says
     const int max_keys = skv_max_keys(Skv, total_q, WINDOW ? window_left : -1, ns);
     const bool want_lse = SINK || lse != nullptr || ns > 1;
-    rc = launch_skv<(SINK ? kSkvSink : 0) + (WINDOW ? kSkvWindow : 0) + kSkvPagedVarq>(
+    rc = launch_skv<(TREE ? kSkvTree : 0) + (SINK ? kSkvSink : 0) + (WINDOW ? kSkvWindow : 0) + kSkvPagedVarq>(
         a, pg, vq, SkvWindow{window_left, window_right}, (unsigned)((long long)Hkv * nt * ns), max_keys, D, fp8_fmt, precision, want_lse, st,
-        SkvSink{sinks});
+        SkvSink{sinks}, SkvTree{tree_mask});
     if (rc != QATTN_OK) return rc;
     if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
     if (ns == 1) return QATTN_OK;

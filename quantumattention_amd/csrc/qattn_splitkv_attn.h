@@ -12,6 +12,8 @@
 // And three more add a learned attention sink per query head to the window kernels (QATTN_SKV_SINK; include/qattn_sinks.h): the kernels of
 // qattn_splitkv_sink_fp8.hip, qattn_paged_splitkv_sink_fp8.hip and qattn_paged_varlen_splitkv_sink_fp8.hip, the sink again an argument of
 // its own (SkvSink).
+// A tenth puts a draft tree over the packed paged kernel's causal rule (QATTN_SKV_TREE; include/qattn_paged_varlen_tree.h): the kernel of
+// qattn_paged_varlen_splitkv_tree_fp8.hip, its mask words an argument of their own (SkvTree).
 #pragma once
 #include <limits.h>
 
@@ -67,6 +69,12 @@ struct SkvWindow {
 // A kernel argument of its own, as the window: the kernels without a sink keep their kernarg layout.
 struct SkvSink {
     const float* sink;
+};
+
+// TREE: the draft tree of a speculative step (include/qattn_paged_varlen_tree.h): one 64-bit word per packed token, [total_q] on the
+// device; bit i of token (b, p)'s word lets position p attend draft token i of its slot.  A kernel argument of its own, as the window.
+struct SkvTree {
+    const unsigned long long* mask;
 };
 
 // Physical chunk of chunk `ch` of kv head hkv of the page a RAW table entry names. The clamp is what keeps every address inside the
@@ -139,7 +147,9 @@ void attn_splitkv_fp8_kernel(const SkvAttn a, const int two, const int sel) {
 #define QATTN_SKV_VARQ 0
 #define QATTN_SKV_WINDOW 0
 #define QATTN_SKV_SINK 0
+#define QATTN_SKV_TREE 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
@@ -153,7 +163,9 @@ void attn_paged_splitkv_fp8_kernel(const SkvAttn a, const SkvPages pg, const int
 #define QATTN_SKV_VARQ 0
 #define QATTN_SKV_WINDOW 0
 #define QATTN_SKV_SINK 0
+#define QATTN_SKV_TREE 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
@@ -167,7 +179,9 @@ void attn_paged_varlen_splitkv_fp8_kernel(const SkvAttn a, const SkvPages pg, co
 #define QATTN_SKV_VARQ 1
 #define QATTN_SKV_WINDOW 0
 #define QATTN_SKV_SINK 0
+#define QATTN_SKV_TREE 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
@@ -182,7 +196,9 @@ void attn_splitkv_window_fp8_kernel(const SkvAttn a, const SkvWindow wn, const i
 #define QATTN_SKV_VARQ 0
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 0
+#define QATTN_SKV_TREE 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
@@ -196,7 +212,9 @@ void attn_paged_splitkv_window_fp8_kernel(const SkvAttn a, const SkvPages pg, co
 #define QATTN_SKV_VARQ 0
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 0
+#define QATTN_SKV_TREE 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
@@ -211,7 +229,9 @@ void attn_paged_varlen_splitkv_window_fp8_kernel(const SkvAttn a, const SkvPages
 #define QATTN_SKV_VARQ 1
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 0
+#define QATTN_SKV_TREE 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
@@ -227,7 +247,9 @@ void attn_splitkv_window_sink_fp8_kernel(const SkvAttn a, const SkvWindow wn, co
 #define QATTN_SKV_VARQ 0
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 1
+#define QATTN_SKV_TREE 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
@@ -242,7 +264,9 @@ void attn_paged_splitkv_window_sink_fp8_kernel(const SkvAttn a, const SkvPages p
 #define QATTN_SKV_VARQ 0
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 1
+#define QATTN_SKV_TREE 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
@@ -257,21 +281,45 @@ void attn_paged_varlen_splitkv_window_sink_fp8_kernel(const SkvAttn a, const Skv
 #define QATTN_SKV_VARQ 1
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 1
+#define QATTN_SKV_TREE 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
 #undef QATTN_SKV_VARQ
 #undef QATTN_SKV_PAGED
 }
 
-// which of the nine kernels a launch runs (kSkvWindow + one of the first three: that kernel under a window; + kSkvSink: with a sink)
-constexpr int kSkvContig = 0, kSkvPaged = 1, kSkvPagedVarq = 2, kSkvWindow = 4, kSkvSink = 8;
+// ... and the packed paged kernel under a draft tree `tr` (QATTN_SKV_TREE; include/qattn_paged_varlen_tree.h), both sweeps
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_paged_varlen_splitkv_tree_fp8_kernel(const SkvAttn a, const SkvPages pg, const SkvVarq vq, const SkvTree tr, const int two,
+                                               const int sel) {
+#define QATTN_SKV_PAGED 1
+#define QATTN_SKV_VARQ 1
+#define QATTN_SKV_WINDOW 0
+#define QATTN_SKV_SINK 0
+#define QATTN_SKV_TREE 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
+#undef QATTN_SKV_SINK
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+// which of the ten kernels a launch runs (kSkvWindow + one of the first three: that kernel under a window; + kSkvSink: with a sink;
+// kSkvTree + kSkvPagedVarq: the packed paged kernel under a draft tree)
+constexpr int kSkvContig = 0, kSkvPaged = 1, kSkvPagedVarq = 2, kSkvWindow = 4, kSkvSink = 8, kSkvTree = 16;
 
 template <int D, int FMT, int MODE>
 static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys,
-                          int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}) {
+                          int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}, const SkvTree& tr = SkvTree{}) {
     return fpv_precision_ladder(precision, max_keys, a.two_term_keys, want_lse, [&](auto byte, int two, int sel) {
-        if constexpr ((MODE & kSkvSink) != 0) {
+        if constexpr (MODE == kSkvTree + kSkvPagedVarq)
+            return fpv_launch(attn_paged_varlen_splitkv_tree_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg, vq, tr,
+                              two, sel);
+        else if constexpr ((MODE & kSkvSink) != 0) {
             // (the byte-exponential instances are not compiled for the sink kernels: their callers pass want_lse = true)
             if constexpr (decltype(byte)::value) return (int)QATTN_ERR_LAUNCH;
             else if constexpr (MODE == kSkvSink + kSkvWindow + kSkvPagedVarq)
@@ -297,18 +345,18 @@ static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, const SkvVarq& v
 
 template <int D, int MODE>
 static int launch_skv_d(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys, int fp8_fmt,
-                        int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}) {
-    return fp8_fmt == QATTN_FMT_E4M3 ? launch_skv_fmt<D, QATTN_FMT_E4M3, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st, sn)
-                                     : launch_skv_fmt<D, QATTN_FMT_E5M2, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st, sn);
+                        int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}, const SkvTree& tr = SkvTree{}) {
+    return fp8_fmt == QATTN_FMT_E4M3 ? launch_skv_fmt<D, QATTN_FMT_E4M3, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st, sn, tr)
+                                     : launch_skv_fmt<D, QATTN_FMT_E5M2, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st, sn, tr);
 }
 
 // every head dimension of one entry
 template <int MODE>
 static int launch_skv(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys, int D,
-                      int fp8_fmt, int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}) {
-    if (D == 64) return launch_skv_d<64, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn);
-    if (D == 128) return launch_skv_d<128, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn);
-    return launch_skv_d<256, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn);
+                      int fp8_fmt, int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}, const SkvTree& tr = SkvTree{}) {
+    if (D == 64) return launch_skv_d<64, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn, tr);
+    if (D == 128) return launch_skv_d<128, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn, tr);
+    return launch_skv_d<256, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn, tr);
 }
 
 // Host side of a window (include/qattn_splitkv_window.h).  Under left >= 0 a sequence's interval [lo_i, L) holds at most left + Sq keys,

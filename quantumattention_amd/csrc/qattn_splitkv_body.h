@@ -22,8 +22,14 @@
 // lives in no register across it -- and a tile without a key stores zero rows with LSE = sink.  With more splits the partials are written
 // WITHOUT the sink (the statements of the switch-off text): it enters the last launch of the merge chain.  sink = -inf adds 0.0f to l: the
 // row's bits are the window kernel's.  sink = +inf or NaN: the head's rows are NaN.
+// QATTN_SKV_TREE (with QATTN_SKV_PAGED and QATTN_SKV_VARQ, without QATTN_SKV_WINDOW; include/qattn_paged_varlen_tree.h) puts a draft tree
+// over the causal rule: 0, the text above, token for token (profiles/tree/code_objects_vs_parent.log); 1, a sequence with Sq_i <= 64 queries
+// holds its draft tokens in its last Sq_i keys, and the row of position p attends key j >= max(delta, 0) only if bit j - delta of the
+// token's 64-bit word `tr.mask[token]` is set -- one load per lane before the sweep loop, applied in the edge branch below, which is then
+// entered for every chunk that holds a key >= delta.  The split plan, khi, c_first, n_wg, the ring and the epilogue are the causal text:
+// a word with the bits 0 .. p set gives the causal kernel's bits.  (The entry is causal: its driver sets a.causal.)
 // In scope: template parameters D, FMT, BYTE; arguments a (SkvAttn), two, sel, -- paged -- pg (SkvPages), -- packed queries -- vq,
-// -- window -- wn and -- sink -- sn (SkvSink).
+// -- window -- wn, -- sink -- sn (SkvSink) and -- tree -- tr (SkvTree).
 #if QATTN_SKV_VARQ
 #define SKV_SQ Sq_i
 #define SKV_ROWS rows_i
@@ -201,6 +207,13 @@
     // the last key this lane's row attends, and the first chunk end that crosses the causal edge of some valid row
     const int hi_l = (a.causal && rvalid) ? min(L - 1, r - g * SKV_SQ + delta) : L - 1;
     const int edge = a.causal ? smin + delta : INT_MAX;
+#if QATTN_SKV_TREE
+    // the word of this lane's token -- every head of the token reads the same one; a padding row and a sequence with more than 64 queries
+    // (plain causal) read none -- and the first draft key: a chunk that ends at or above it takes the token branch
+    const bool tree_l = SKV_SQ <= 64 && rvalid;
+    const unsigned long long tword = tree_l ? tr.mask[tok] : ~0ull;
+    const int tree_lo = SKV_SQ <= 64 ? max(delta, 0) : INT_MAX;
+#endif
 #endif
 
     for (int t = 0; t < n_wg; t++) {   // step t sweeps chunk c_first + t
@@ -236,6 +249,24 @@
                 const int key = base + 32 * (e >> 4) + (e & 3) + 8 * ((e & 15) >> 2);
                 v16f& sx = (e >> 4) ? s1 : s0;
                 sx[e & 15] = (key < lo_l || key > hi_l) ? -INFINITY : sx[e & 15];
+            }
+        }
+#elif QATTN_SKV_TREE
+        // ---- the ragged tail at L, the causal edge and the draft tree by token, under a workgroup-uniform condition
+        if (__builtin_expect(k0 + 64 > L || k0 + 63 > edge || k0 + 63 >= tree_lo, 0)) {
+            // bit i of aw: key k0 + i passes the tree.  Key j is bit j - delta of the word; the keys below delta are committed ones and
+            // pass; a key at or above delta + 64 lies above every causal edge of a sequence with a tree.  (k0 - delta < Sq_i: an int.)
+            const int sh = k0 - delta;
+            unsigned long long aw = ~0ull;
+            if (tree_l) aw = sh >= 64 ? 0ull : sh >= 0 ? tword >> sh : sh > -64 ? (tword << -sh) | ((1ull << -sh) - 1ull) : ~0ull;
+            aw >>= 4 * hh;
+            const int base = k0 + 4 * hh;
+#pragma unroll
+            for (int e = 0; e < 32; e++) {
+                const int kb = 32 * (e >> 4) + (e & 3) + 8 * ((e & 15) >> 2);   // (kb + 4 hh <= 63)
+                const int key = base + kb;
+                v16f& sx = (e >> 4) ? s1 : s0;
+                sx[e & 15] = (key > hi_l || !((aw >> kb) & 1ull)) ? -INFINITY : sx[e & 15];
             }
         }
 #else

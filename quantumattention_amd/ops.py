@@ -1053,3 +1053,74 @@ def attention_state_merge_sink(outs: Sequence[torch.Tensor], lses: Sequence[torc
 @_register_fake("quantumattention_amd::attention_state_merge_sink")
 def _(outs, lses, sinks, out_dtype=None):
     return (outs[0].new_empty(outs[0].shape, dtype=out_dtype or outs[0].dtype), lses[0].new_empty(lses[0].shape, dtype=torch.float32))
+
+
+# ---- tree-shaped speculative decoding on the paged cache (include/qattn_paged_varlen_tree.h): the packed paged op under a draft tree --
+# tree_mask, int64 [total_q], in is_causal's place (the call is causal) -- and the compaction of the accepted path.
+
+@_custom_op("quantumattention_amd::fp8_paged_varlen_splitkv_tree_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_paged_varlen_splitkv_tree_attention_forward(
+    query: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    tree_mask: torch.Tensor,
+    max_seqlen_q: int,
+    seqlen_k: int,
+    num_pages: int,
+    page_size: int,
+    num_splits: int,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    precision: str = "accurate",
+    return_lse: bool = False,
+    return_partials: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp8_paged_varlen_splitkv_attention_forward(is_causal=True) under a draft tree per sequence slot: in a slot with at most 64 queries
+    position p attends a draft key j >= L_b - Sq_b only if bit j - (L_b - Sq_b) of tree_mask[token] is set.  Reference implementation:
+    paged_varlen._attend_varlen_eager with tree_mask=.  Arguments are validated by tree.fp8_attn_paged_varlen_tree_func."""
+    res = _native.fp8_attention_paged_varlen(
+        query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, cu_seqlens_q, max_seqlen_q=max_seqlen_q, Skv=seqlen_k,
+        num_pages=num_pages, page_size=page_size, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics, is_causal=True,
+        sm_scale=0.0 if scale is None else float(scale), precision=precision, num_splits=num_splits, return_lse=return_lse,
+        return_partials=return_partials, tree_mask=tree_mask)
+    return _skv_pack(res, query, return_lse, return_partials)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_varlen_splitkv_tree_attention_forward")
+def _(query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, cu_seqlens_q, tree_mask, max_seqlen_q, seqlen_k, num_pages, page_size,
+      num_splits, fp8_format="e4m3", numerics="compiled", precision="accurate", return_lse=False, return_partials=False, *, scale=None):
+    total_q, Hq, _ = query.shape
+    return _skv_fake(query, (total_q, Hq), (Hq, total_q), num_splits, return_lse, return_partials)
+
+
+@_custom_op("quantumattention_amd::fp8_paged_kv_cache_compact_", mutates_args=("k_pool", "v_pool", "seqlens"), device_types=("cuda",))
+def fp8_paged_kv_cache_compact_(
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens: torch.Tensor,
+    cu_seqlens: torch.Tensor,
+    accept_index: torch.Tensor,
+    accept_lens: torch.Tensor,
+    num_kv_heads: int,
+    head_dim: int,
+    num_pages: int,
+    page_size: int,
+) -> None:
+    """Compact the accepted draft keys of a tree-shaped speculative step IN PLACE (include/qattn_paged_varlen_tree.h): in every slot with
+    1 .. 64 draft tokens key base + i takes the bytes of key base + accept_index[cu[b] + i] for i < accept_lens[b], and seqlens[b] becomes
+    base + accept_lens[b].  Reference implementation: tree._compact_eager.  Arguments are validated by tree.paged_kv_cache_compact_fp8."""
+    _native.paged_kv_cache_compact_fp8(k_pool, v_pool, block_table, seqlens, cu_seqlens, accept_index, accept_lens, Hkv=num_kv_heads,
+                                       D=head_dim, num_pages=num_pages, page_size=page_size)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_kv_cache_compact_")
+def _(k_pool, v_pool, block_table, seqlens, cu_seqlens, accept_index, accept_lens, num_kv_heads, head_dim, num_pages, page_size):
+    return None

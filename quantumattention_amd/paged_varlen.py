@@ -117,10 +117,12 @@ def _resolve_varlen_splits(num_splits: int, B: int, Hq: int, Hkv: int, total_q: 
     return _native.paged_varlen_auto_splits(B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, cus)
 
 
-def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, ns, precision, sinks=None, window=None):
+def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, ns, precision, tree_mask=None, sinks=None, window=None):
     """CPU tensors and config.attention.force_eager_fallback: per sequence slot, splitkv._splitkv_eager on the slot's queries and on its
     keys gathered through the table, scattered into the packed outputs.  Rows of tokens that belong to no sequence: zeros.  (This path
-    reads cu_seqlens_q, seqused_k and the table on the host.)"""
+    reads cu_seqlens_q, seqused_k and the table on the host.)
+    tree_mask = int64 [total_q] (None: none; with causal): the draft tree of include/qattn_paged_varlen_tree.h -- in a slot with at most 64
+    queries position p keeps key j >= max(delta, 0), delta = L_b - Sq_b, only if bit j - delta of the token's word is set."""
     total_q, Hq, D = q.shape
     B = cache.batch_size
     n = ns if ns > 1 else 0
@@ -140,8 +142,16 @@ def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, 
             continue
         one = PreparedKV(kv.k[b:b + 1], kv.v[b:b + 1], kv.scale_k[b:b + 1], kv.scale_v[b:b + 1], (1,) + tuple(kv.shape[1:]), kv.fp8_format,
                          kv.dtype, kv.numerics, "rowmajor")
+        also = None
+        if tree_mask is not None and end - start <= 64:
+            delta = min(max(int(seqused_k[b]), 0), Skv) - (end - start)
+            bits = ((tree_mask[start:end, None] >> torch.arange(64, device=q.device)) & 1).bool()           # [Sq_b, 64]: bit i of word p
+            j0, j1 = max(delta, 0), max(min(delta + 64, Skv), 0)
+            also = torch.ones((1, end - start, Skv), dtype=torch.bool, device=q.device)
+            if j1 > j0:
+                also[0, :, j0:j1] = bits[:, j0 - delta:j1 - delta]
         o, l, p_o, p_l, p_p = _splitkv_eager(q[start:end].transpose(0, 1)[None], one, causal, scale, seqused_k[b:b + 1], ns, precision,
-                                             sinks, window)
+                                             keep_also=also, sinks=sinks, window=window)
         out[start:end] = o[0].transpose(0, 1)
         lse[:, start:end] = l[0]
         if n:

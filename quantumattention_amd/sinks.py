@@ -86,7 +86,7 @@ def fp8_attn_splitkv_sink_func(q, kv, sinks, window_size=(-1, 0), *, scale: Opti
     if eager:
         if kv.layout != "rowmajor":
             raise ValueError("the eager definition needs a PreparedKV made on CPU tensors or under config.attention.force_eager_fallback")
-        res = _splitkv_eager(q, kv, False, scale, seqused_k, ns, precision, sinks, (left, right))
+        res = _splitkv_eager(q, kv, False, scale, seqused_k, ns, precision, sinks=sinks, window=(left, right))
     else:
         if kv.layout != "frag":
             raise ValueError("this PreparedKV holds row-major bytes for the eager definition; prepare it on the device without "
@@ -122,7 +122,7 @@ def fp8_attn_paged_sink_func(q, cache: PagedKVCacheFP8, sinks, window_size=(-1, 
     if eager:
         if cache.layout != "rowmajor":
             raise ValueError("the eager definition needs a cache made on a CPU device or under config.attention.force_eager_fallback")
-        res = _attend_eager(q, cache, False, scale, used, Skv, ns, precision, sinks, (left, right))
+        res = _attend_eager(q, cache, False, scale, used, Skv, ns, precision, sinks=sinks, window=(left, right))
     else:
         if cache.layout != "frag":
             raise ValueError("this cache holds row-major bytes for the eager definition; make it on the device without "
@@ -159,7 +159,7 @@ def fp8_attn_paged_varlen_sink_func(q, cache: PagedKVCacheFP8, cu_seqlens_q: Ten
     if eager:
         if cache.layout != "rowmajor":
             raise ValueError("the eager definition needs a cache made on a CPU device or under config.attention.force_eager_fallback")
-        res = _attend_varlen_eager(q, cache, cu_seqlens_q, False, scale, used, Skv, ns, precision, sinks, (left, right))
+        res = _attend_varlen_eager(q, cache, cu_seqlens_q, False, scale, used, Skv, ns, precision, sinks=sinks, window=(left, right))
     else:
         if cache.layout != "frag":
             raise ValueError("this cache holds row-major bytes for the eager definition; make it on the device without "

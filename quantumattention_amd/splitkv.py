@@ -190,7 +190,7 @@ def split_plan_window(L: int, Sq: int, window_left: int, num_splits: int):
     return [(min(BLOCK_N * (kb0 + s * per), L), min(BLOCK_N * (kb0 + (s + 1) * per), L)) for s in range(num_splits)]
 
 
-def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, sinks=None, window=None):
+def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, keep_also=None, sinks=None, window=None):
     """CPU tensors and config.attention.force_eager_fallback: the torch definition.  The eager quantiser on q (head-wise), the prepared
     row-major bytes de-quantised; per split an fp32 softmax partial (o_s, lse_s) over the split's keys of every batch element's first L_b
     keys -- a row without a key there: a zero row, LSE -inf --, then merge.merge_attn_states_eager.  The path bytes restate the kernel's
@@ -200,7 +200,9 @@ def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, sinks=None, w
     split_plan_window's, position p keeps the keys p + delta - left .. p + delta + right, and the path byte counts the keys klo .. khi.
     sinks = fp32 [Hq] (None: none): the definition of the sink entries (include/qattn_sinks.h) -- one split: the row's LSE becomes
     L = logaddexp(lse, sink_h) and the weights exp(score - L), an empty row a zero row with LSE = sink_h; more splits: the partials stay
-    free of the sink and it enters merge.merge_attn_states_eager once.  +inf and NaN make the head's rows NaN."""
+    free of the sink and it enters merge.merge_attn_states_eager once.  +inf and NaN make the head's rows NaN.
+    keep_also = bool [B, Sq, Skv] (None: none): one more condition on (position, key), on top of the rule above -- the draft tree of
+    tree.fp8_attn_paged_varlen_tree_func; the splits and the path bytes do not see it."""
     fp8_dtype = _native.fp8_dtype_of(kv.fp8_format)
     B, Hq, Sq, D = q.shape
     _, Hkv, Skv, _ = kv.shape
@@ -229,6 +231,8 @@ def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, sinks=None, w
                     m = m & (key <= pos + (L - Sq + window[1]))
             elif causal:
                 m = m & (key <= pos + (L - Sq))
+            if keep_also is not None:
+                m = m & keep_also[b]
             keep[b, 0] = m.expand(Sq, Skv)
             # the kernel's path byte: per tile of the kv head's packed rows, by the keys the workgroup sweeps
             for t in range(ntile):
