@@ -59,9 +59,11 @@
  * outside {0, 1}; the table rules above; more than 2^31 - 1 blocks of 256 units.  QATTN_ERR_UNSUPPORTED_DIM / _FMT as the append.
  * total = 0 (after these checks): QATTN_OK, nothing launched.
  *
+ * A positions tensor (vLLM's `positions`; a tree node of a speculative step sits at base + depth) is taken by the siblings of
+ * include/qattn_paged_varlen_rope_pos.h, not by these entries.
  * Not offered: RoPE fused into the q pre-pass of the paged attention (the pre-pass is shared by every split-KV entry); per-slot position
- * offsets or a positions tensor; a [B, T, D/2] table per slot; a partial rotary_dim; scaled / YaRN tables beyond what the caller puts
- * into cos / sin; the padded and the contiguous appends.
+ * offsets; a [B, T, D/2] table per slot; a partial rotary_dim; multi-axis (M-RoPE) positions; scaled / YaRN tables beyond what the caller
+ * puts into cos / sin; the padded and the contiguous appends, with or without positions.
  */
 #ifndef QATTN_PAGED_VARLEN_ROPE_H_
 #define QATTN_PAGED_VARLEN_ROPE_H_

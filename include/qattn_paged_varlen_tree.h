@@ -60,10 +60,12 @@
  * num_pages, max_pages, Hkv, B <= 0, total < 0, page_size no positive multiple of 64, table_stride < max_pages, a capacity or a grid
  * B Hkv above 2^31 - 1; QATTN_ERR_UNSUPPORTED_DIM for D not in {64, 128, 256}.  total = 0 (after these checks): QATTN_OK, nothing launched.
  *
- * Not offered: sliding windows under a tree mask; sinks folded into the tree unit (compose: the LSE of this call and
- * qattn_attention_state_merge_sink); trees above 64 tokens per slot; a positions tensor for the fused RoPE append (a tree node's position
- * is base + depth, not base + index: rotate the drafts at the caller's positions and use the plain packed append); the contiguous
- * KVCacheFP8; masks for the dense, 16-bit and block-sparse entries.
+ * Offered elsewhere, not by these two entries: sliding windows under a tree mask and sinks folded into the tree unit -- both are
+ * qattn_fp8_attention_paged_varlen_tree_window_forward (include/qattn_paged_varlen_tree_window.h), for windows (left, 0) with left = -1
+ * or left >= 63; a positions tensor for the fused RoPE append and for q's packed rotation (a tree node's position is base + depth, not
+ * base + index) -- include/qattn_paged_varlen_rope_pos.h.
+ * Not offered: a window with left < 63 under a tree; trees above 64 tokens per slot; the contiguous KVCacheFP8; masks for the dense,
+ * 16-bit and block-sparse entries.
  */
 #ifndef QATTN_PAGED_VARLEN_TREE_H_
 #define QATTN_PAGED_VARLEN_TREE_H_

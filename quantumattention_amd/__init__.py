@@ -54,6 +54,8 @@ from .paged_varlen import paged_kv_cache_append_varlen_fp8  # noqa: E402
 # ... and the same with the rotary embedding of K inside the append, and q's packed rotation at the same positions
 # (include/qattn_paged_varlen_rope.h): package attributes, not in __all__
 from .paged_varlen import apply_rope_paged_varlen, paged_kv_cache_append_varlen_rope_fp8  # noqa: E402
+# ... and at the caller's positions (include/qattn_paged_varlen_rope_pos.h): package attributes, not in __all__
+from .paged_varlen import apply_rope_positions, paged_kv_cache_append_varlen_rope_pos_fp8  # noqa: E402
 # sliding windows for the split-KV, paged and packed-paged entries (include/qattn_splitkv_window.h): package attributes, not in __all__
 from .splitkv_window import (  # noqa: E402
     fp8_attn_paged_varlen_window_func,
@@ -71,6 +73,9 @@ from .sinks import (  # noqa: E402
 # tree-shaped speculative decoding on the paged cache: the verify pass under a draft tree and the compaction of the accepted path
 # (include/qattn_paged_varlen_tree.h): package attributes, not in __all__
 from .tree import fp8_attn_paged_varlen_tree_func, paged_kv_cache_compact_fp8, tree_mask_from_parents  # noqa: E402
+# ... on windowed layers and layers with learned sinks, and the drafts' rotary positions (include/qattn_paged_varlen_tree_window.h,
+# include/qattn_paged_varlen_rope_pos.h): package attributes, not in __all__ (the reason functions stay in their modules, as the others)
+from .tree import fp8_attn_paged_varlen_tree_window_func, tree_positions  # noqa: E402
 
 __version__ = "0.1.0"
 

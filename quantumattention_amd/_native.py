@@ -62,6 +62,8 @@ EXPORTS = (
     "qattn_attention_state_merge_sink", "qattn_fp8_attention_splitkv_sink_forward", "qattn_fp8_attention_paged_splitkv_sink_forward",
     "qattn_fp8_attention_paged_varlen_sink_forward",
     "qattn_fp8_attention_paged_varlen_tree_forward", "qattn_paged_kv_cache_compact_fp8",
+    "qattn_fp8_attention_paged_varlen_tree_window_forward",
+    "qattn_paged_kv_cache_append_varlen_rope_pos_fp8", "qattn_rope_packed_positions",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -315,6 +317,18 @@ def lib() -> ctypes.CDLL:
                                                                 i, vp, f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.qattn_paged_kv_cache_compact_fp8.restype = i
     L.qattn_paged_kv_cache_compact_fp8.argtypes = [vp, vp, vp, ll, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
+    # the tree under a window, optionally with sinks (include/qattn_paged_varlen_tree_window.h): the tree entry's arguments with window_left,
+    # window_right, sinks (NULL: none) after tree_mask
+    L.qattn_fp8_attention_paged_varlen_tree_window_forward.restype = i
+    L.qattn_fp8_attention_paged_varlen_tree_window_forward.argtypes = [vp, vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, vp, i, i, i, i, i,
+                                                                       i, i, i, i, vp, i, i, vp, f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    # the rotary embedding at the caller's positions (include/qattn_paged_varlen_rope_pos.h): the rope append's arguments with positions before
+    # stream; x16, in_fmt, x_strides2, out16, positions, H, total, D, cos, sin, table_row_stride, T, interleaved, stream
+    L.qattn_paged_kv_cache_append_varlen_rope_pos_fp8.restype = i
+    L.qattn_paged_kv_cache_append_varlen_rope_pos_fp8.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, ll, vp, vp, i, i, i, i, i, i, i, i, i, vp,
+                                                                  vp, ll, i, i, vp, vp]
+    L.qattn_rope_packed_positions.restype = i
+    L.qattn_rope_packed_positions.argtypes = [vp, i, vp, vp, vp, i, i, i, vp, vp, ll, i, i, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1536,6 +1550,74 @@ def rope_paged_varlen(x: torch.Tensor, seqlens: torch.Tensor, cu_seqlens: torch.
     return out
 
 
+def _positions_check(positions: torch.Tensor, total: int, dev) -> None:
+    _require(positions.dtype == torch.int64 and positions.device == dev and tuple(positions.shape) == (total,) and positions.is_contiguous(),
+             f"positions must be a dense int64 [total={total}] tensor on {dev}")
+
+
+def paged_kv_cache_append_varlen_rope_pos_fp8(k_pool: torch.Tensor, v_pool: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor,
+                                              block_table: torch.Tensor, seqlens: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
+                                              cu_seqlens: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, *,
+                                              num_pages: int, page_size: int, fp8_dtype=torch.float8_e4m3fn, interleaved: bool = False,
+                                              advance: bool = True) -> None:
+    """qattn_paged_kv_cache_append_varlen_rope_pos_fp8 (include/qattn_paged_varlen_rope_pos.h): paged_kv_cache_append_varlen_rope_fp8 with
+    token t rotated with row clamp(positions[t], 0, T - 1) of cos / sin; positions int64 [total] on the device.  Where a key is stored
+    does not change.  Mutates k_pool, v_pool and seqlens."""
+    _require(k_new.is_cuda and k_new.dim() == 3 and k_new.dtype in (torch.bfloat16, torch.float16), "k_new must be a 3-D bf16 / fp16 device tensor")
+    _require(v_new.shape == k_new.shape and v_new.dtype == k_new.dtype and v_new.device == k_new.device, "k_new and v_new must agree in shape, dtype and device")
+    total, Hkv, D = k_new.shape
+    if total == 0:
+        return
+    _require(paged_varlen_q_addressable(k_new) and paged_varlen_q_addressable(v_new), "k_new / v_new need head_dim innermost and 16-byte-aligned rows")
+    B = block_table.shape[0] if block_table.dim() == 2 else 0
+    L = lib()
+    dev = k_new.device
+    max_pages, tstride = _paged_pool_checks(L, k_pool, v_pool, block_table, scale_k, scale_v, dev, B, Hkv, num_pages, page_size, D)
+    _require(seqlens.dtype == torch.int32 and seqlens.device == dev and tuple(seqlens.shape) == (B,) and seqlens.is_contiguous(),
+             f"seqlens must be a dense int32 [B] tensor on {dev}")
+    _require(cu_seqlens.dtype == torch.int32 and cu_seqlens.device == dev and tuple(cu_seqlens.shape) == (B + 1,) and cu_seqlens.is_contiguous(),
+             f"cu_seqlens must be a dense int32 [B + 1] tensor on {dev}")
+    _positions_check(positions, total, dev)
+    T, tr = _paged_rope_tables(cos, sin, dev, D)
+    dense = (Hkv * D, D)     # (a dimension of size 1 has no stride of its own)
+    s2 = lambda t: (ctypes.c_longlong * 2)(*[t.stride(i) if t.shape[i] > 1 else dense[i] for i in (0, 1)])
+    with torch.cuda.device(dev):
+        rc = L.qattn_paged_kv_cache_append_varlen_rope_pos_fp8(k_new.data_ptr(), v_new.data_ptr(), fmt_of(k_new.dtype), s2(k_new), s2(v_new),
+                                                               k_pool.data_ptr(), v_pool.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(),
+                                                               block_table.data_ptr(), tstride, seqlens.data_ptr(), cu_seqlens.data_ptr(),
+                                                               int(bool(advance)), B, Hkv, total, num_pages, page_size, max_pages, D,
+                                                               fmt_of(fp8_dtype), cos.data_ptr(), sin.data_ptr(), tr, T,
+                                                               int(bool(interleaved)), positions.data_ptr(), _stream(k_new))
+    _check(rc, "qattn_paged_kv_cache_append_varlen_rope_pos_fp8")
+
+
+def rope_packed_positions(x: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, *, interleaved: bool = False,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qattn_rope_packed_positions (include/qattn_paged_varlen_rope_pos.h): packed rows x [total, H, D] (dense or a view
+    `paged_varlen_q_addressable` accepts, read in place), row t rotated with row clamp(positions[t], 0, T - 1) of cos / sin -> dense
+    [total, H, D] (`out`, or a new tensor).  positions int64 [total] and the tables are read on the device."""
+    _require(x.is_cuda and x.dim() == 3 and x.dtype in (torch.bfloat16, torch.float16), "x must be a 3-D bf16 / fp16 device tensor")
+    total, H, D = x.shape
+    dev = x.device
+    if out is None:
+        with torch.cuda.device(dev):
+            out = torch.empty((total, H, D), dtype=x.dtype, device=dev)
+    _require(out.shape == x.shape and out.dtype == x.dtype and out.device == dev and out.is_contiguous() and out.data_ptr() % 16 == 0,
+             "out must be a dense, 16-byte-aligned tensor of x's shape, dtype and device")
+    _positions_check(positions, total, dev)
+    if total == 0:
+        return out
+    _require(H > 0 and paged_varlen_q_addressable(x), "x needs head_dim innermost and 16-byte-aligned rows")
+    T, tr = _paged_rope_tables(cos, sin, dev, D)
+    dense = (H * D, D)     # (a dimension of size 1 has no stride of its own)
+    s2 = (ctypes.c_longlong * 2)(*[x.stride(i) if x.shape[i] > 1 else dense[i] for i in (0, 1)])
+    with torch.cuda.device(dev):
+        rc = lib().qattn_rope_packed_positions(x.data_ptr(), fmt_of(x.dtype), s2, out.data_ptr(), positions.data_ptr(), H, total, D,
+                                               cos.data_ptr(), sin.data_ptr(), tr, T, int(bool(interleaved)), _stream(x))
+    _check(rc, "qattn_rope_packed_positions")
+    return out
+
+
 def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor,
                                 block_table: torch.Tensor, seqused_k: torch.Tensor, *, Skv: int, num_pages: int, page_size: int,
                                 fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled", is_causal: bool = False, sm_scale: float = 0.0,
@@ -1623,19 +1705,21 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
     the device's CU count (resolved here, on the host).  Returns out [total_q, Hq, D], or a tuple of out, [lse [Hq, total_q]], [partial_o
     fp32 [ns, total_q, Hq, D], partial_lse [ns, Hq, total_q], partial_path uint8 -- three empty tensors when the call ran one split],
     [q8 [Hq total_q D] flat, scale_q [B, Hq]], [row_path uint8 [Hq, total_q]].
-    tree_mask (int64 [total_q] on the device; without window / sinks): qattn_fp8_attention_paged_varlen_tree_forward
-    (include/qattn_paged_varlen_tree.h) -- the causal call under a draft tree per slot; is_causal is not read."""
+    tree_mask (int64 [total_q] on the device): qattn_fp8_attention_paged_varlen_tree_forward (include/qattn_paged_varlen_tree.h) -- the
+    causal call under a draft tree per slot; is_causal is not read.  With window (and, optionally, sinks):
+    qattn_fp8_attention_paged_varlen_tree_window_forward (include/qattn_paged_varlen_tree_window.h)."""
     _require(precision in ("fast", "accurate"), f"Unsupported precision for the split-KV entry: {precision!r} (expected 'fast' or 'accurate')")
     _require(q.is_cuda and q.dim() == 3 and q.dtype in (torch.bfloat16, torch.float16), "query must be a 3-D bf16 / fp16 device tensor [total_q, Hq, D]")
     _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
     mask_args = (int(bool(is_causal)),) if window is None else _window_args(window)
     total_q, Hq, D = q.shape
     mask_args += _sink_args(sinks, window, Hq, q.device)
+    tree_window = tree_mask is not None and window is not None
     if tree_mask is not None:
-        _require(window is None and sinks is None, "a tree mask is offered without a window and without sinks")
         _require(tree_mask.dtype == torch.int64 and tree_mask.device == q.device and tuple(tree_mask.shape) == (total_q,)
                  and tree_mask.is_contiguous(), f"tree_mask must be a dense int64 [total_q={total_q}] tensor on {q.device}")
-        mask_args = (tree_mask.data_ptr(),)
+        # without a window: the tree entry.  With one: the tree-window entry, its sinks pointer NULL without sinks
+        mask_args = (tree_mask.data_ptr(),) + ((mask_args + (None,))[:3] if tree_window else ())
     if total_q and not paged_varlen_q_addressable(q):
         q = q.contiguous()
     _require(scale_k.dim() == 2, "scale_k / scale_v must be fp32 [B, Hkv]")
@@ -1676,7 +1760,8 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
             live = lambda t: _ptr(t) if t is not None and t.numel() else None
             dense = (Hq * D, D)     # (a dimension of size 1 has no stride of its own)
             s2 = (ctypes.c_longlong * 2)(*[q.stride(i) if q.shape[i] > 1 else dense[i] for i in (0, 1)])
-            fwd = (L.qattn_fp8_attention_paged_varlen_tree_forward if tree_mask is not None
+            fwd = (L.qattn_fp8_attention_paged_varlen_tree_window_forward if tree_window
+                   else L.qattn_fp8_attention_paged_varlen_tree_forward if tree_mask is not None
                    else L.qattn_fp8_attention_paged_varlen_forward if window is None else L.qattn_fp8_attention_paged_varlen_window_forward
                    if sinks is None else L.qattn_fp8_attention_paged_varlen_sink_forward)
             rc = fwd(
@@ -1684,7 +1769,8 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
                 max_pages, scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), seqused_k.data_ptr(), B, Hq,
                 Hkv, total_q, max_seqlen_q, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), *mask_args, float(sm_scale),
                 _precision(precision), ns, live(q8), _ptr(sq), live(path), live(po), live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_attention_paged_varlen_tree_forward" if tree_mask is not None
+    _check(rc, "qattn_fp8_attention_paged_varlen_tree_window_forward" if tree_window
+           else "qattn_fp8_attention_paged_varlen_tree_forward" if tree_mask is not None
            else "qattn_fp8_attention_paged_varlen_forward" if window is None else "qattn_fp8_attention_paged_varlen_window_forward"
            if sinks is None else "qattn_fp8_attention_paged_varlen_sink_forward")
     if not (return_lse or return_partials or return_quant or return_path):

@@ -24,7 +24,8 @@ SOURCES = ["qattn_quant.hip", "qattn_attn_v2.hip", "qattn_attn_v4.hip", "qattn_a
            "qattn_block_sparse.hip", "qattn_block_sparse_fp8.hip", "qattn_smooth_k.hip", "qattn_varlen_smooth.hip", "qattn_varlen_window.hip", "qattn_varlen_fp8.hip", "qattn_varlen_window_fp8.hip", "qattn_merge.hip", "qattn_rope_quant.hip", "qattn_splitkv_fp8.hip", "qattn_kvcache_append.hip", "qattn_paged_splitkv_fp8.hip", "qattn_paged_append.hip", "qattn_paged_varlen_splitkv_fp8.hip",
            "qattn_splitkv_window_fp8.hip", "qattn_paged_splitkv_window_fp8.hip", "qattn_paged_varlen_splitkv_window_fp8.hip", "qattn_paged_varlen_append.hip", "qattn_paged_varlen_rope_append.hip",
            "qattn_merge_sink.hip", "qattn_splitkv_sink_fp8.hip", "qattn_paged_splitkv_sink_fp8.hip", "qattn_paged_varlen_splitkv_sink_fp8.hip",
-           "qattn_paged_varlen_splitkv_tree_fp8.hip", "qattn_paged_compact.hip"]
+           "qattn_paged_varlen_splitkv_tree_fp8.hip", "qattn_paged_compact.hip",
+           "qattn_paged_varlen_splitkv_tree_window_fp8.hip", "qattn_paged_varlen_splitkv_tree_sink_fp8.hip", "qattn_paged_varlen_rope_pos_append.hip"]
 # (source, extra flags, object name): the two big kernel files are compiled once per operand format / head dimension so that
 # the build runs in parallel (the longest single translation unit sets the wall time)
 # (a unit with a define is compiled through a two-line wrapper file named after the unit, so that -save-temps leaves one .s
@@ -78,6 +79,11 @@ UNITS = [
     # tree-shaped speculative decoding (include/qattn_paged_varlen_tree.h): the packed paged sweep under a draft tree, and the compaction of the accepted path
     ("qattn_paged_varlen_splitkv_tree_fp8.hip", [], "qattn_paged_varlen_splitkv_tree_fp8"),
     ("qattn_paged_compact.hip", [], "qattn_paged_compact"),
+    # ... and the tree over the packed paged window sweep, without and with learned sinks (include/qattn_paged_varlen_tree_window.h)
+    ("qattn_paged_varlen_splitkv_tree_window_fp8.hip", [], "qattn_paged_varlen_splitkv_tree_window_fp8"),
+    ("qattn_paged_varlen_splitkv_tree_sink_fp8.hip", [], "qattn_paged_varlen_splitkv_tree_sink_fp8"),
+    # the rotating packed append and q's packed rotation at the caller's positions: a tree node sits at base + depth (include/qattn_paged_varlen_rope_pos.h)
+    ("qattn_paged_varlen_rope_pos_append.hip", [], "qattn_paged_varlen_rope_pos_append"),
 ]
 # (Until round 5 `--dev` built a second library with -DQATTN_DEV: timing-only ablation instantiations, per-segment cycle stamps, work logs and
 # QATTN_* environment switches.  Round 6 took that scaffolding out of the sources -- identical product ISA, profiles/r06/isa_identity_*.log;
@@ -122,7 +128,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = False, 
     os.makedirs(build_dir, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("qattn.h", "qattn_measure.h", "qattn_varlen.h", "qattn_block_sparse.h", "qattn_smooth.h", "qattn_window.h", "qattn_merge.h", "qattn_rope.h", "qattn_splitkv.h", "qattn_kvcache.h", "qattn_paged.h", "qattn_paged_varlen.h", "qattn_splitkv_window.h", "qattn_paged_varlen_append.h", "qattn_paged_varlen_rope.h", "qattn_sinks.h", "qattn_paged_varlen_tree.h")]
+    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("qattn.h", "qattn_measure.h", "qattn_varlen.h", "qattn_block_sparse.h", "qattn_smooth.h", "qattn_window.h", "qattn_merge.h", "qattn_rope.h", "qattn_splitkv.h", "qattn_kvcache.h", "qattn_paged.h", "qattn_paged_varlen.h", "qattn_splitkv_window.h", "qattn_paged_varlen_append.h", "qattn_paged_varlen_rope.h", "qattn_sinks.h", "qattn_paged_varlen_tree.h", "qattn_paged_varlen_tree_window.h", "qattn_paged_varlen_rope_pos.h")]
     objs, jobs = [], []
     for src, defines, name in UNITS:
         s = os.path.join(CSRC, src)

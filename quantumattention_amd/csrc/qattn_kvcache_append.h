@@ -44,6 +44,12 @@ struct KvRope {
     int T;
 };
 
+// POSITIONS (include/qattn_paged_varlen_rope_pos.h): the table row of a rotated key from the caller -- one 64-bit position per packed
+// token, [total] on the device, clamped into [0, T - 1] where it is read
+struct KvPos {
+    const long long* pos;
+};
+
 __device__ __forceinline__ int kv_clampi(int x, int lo, int hi) { return x < lo ? lo : x > hi ? hi : x; }
 
 // the appended keys of batch element b: [p, p + n) cut at the capacity

@@ -14,8 +14,11 @@
 // sequence and rotates with table row min(key0 + r, T - 1) (`rp`, KvRope; template flag IL = interleaved pairs).  The rotated vector is
 // rounded to the input dtype (rope_unit) before has_nonfinite16 and quant8 see it, and lands at the LDS offsets the plain mapping uses;
 // everything behind the barrier, and the V half, is the shared text.  With the switch off the text the compiler sees is what it was.
+// QATTN_KVA_POS (with QATTN_KVA_ROPE; include/qattn_paged_varlen_rope_pos.h; not defined by the other compilations: off) takes the table
+// row of a key from the caller's 64-bit positions tensor (`ps`, KvPos), indexed by the key's TOKEN, instead of from the key's index:
+// the one line that forms `pos`.  Where the key is stored does not change.
 // In scope: template parameters D, IN_FMT, OUT_FMT (rope: IL); arguments a (KvAppendArgs), -- paged -- pg (KvPages), -- packed -- vq
-// (KvVarq) and -- rope -- rp (KvRope).
+// (KvVarq), -- rope -- rp (KvRope) and -- positions -- ps (KvPos).
     constexpr int VPR = D / 8;             // 16-byte input vectors per row
     constexpr int ITERS = 64 * VPR / 256;  // vectors per thread
     constexpr int KPAD = 64 * D + (64 * D / 512) * 16;  // KFRAG image + 16 B per 512 B     (the staging images of quant_multi_kernel)
@@ -79,8 +82,15 @@
                 const uint4* px = xg + (long)r * st + dvh;
                 held[2 * u] = load_nt(px);
                 held[2 * u + 1] = load_nt(px + HV);
+#if QATTN_KVA_POS
+                // key key0 + r is token start + key0 + r - p < start + n <= total of the call: its position is the caller's, clamped in 64
+                // bits so that the row stays inside the tables whatever the tensor holds
+                const long long want = ps.pos[(long)start + key0 + r - p];
+                const int pos = want < 0 ? 0 : want < rp.T ? (int)want : rp.T - 1;
+#else
                 // key0 + r < end <= capacity: an int; the clamp keeps the row inside the tables whatever seqlens holds
                 const int pos = (int)key0 + r < rp.T ? (int)key0 + r : rp.T - 1;
+#endif
                 const int t0 = IL ? dvh : 2 * dvh, t1 = IL ? dvh + HV : 2 * dvh + 1;
                 c[u][0] = cg[pos * tr4 + t0]; c[u][1] = cg[pos * tr4 + t1];
                 s[u][0] = sg[pos * tr4 + t0]; s[u][1] = sg[pos * tr4 + t1];

@@ -47,6 +47,8 @@ inline int pvq_most_splits(int Skv, int num_splits) {
 // SINK (with WINDOW; include/qattn_sinks.h): the sink kernel with `sinks` fp32 [Hq], as skv_forward.
 // TREE (without WINDOW; include/qattn_paged_varlen_tree.h): the tree kernel under `tree_mask`, one 64-bit word per packed token on the
 // device; the call is causal whatever is_causal says.
+// TREE with WINDOW, and with SINK (include/qattn_paged_varlen_tree_window.h): the tree over the window kernel, for windows (left, 0) with
+// left = -1 or left >= 63; the split plan, the num_splits = 0 rule and the merge chain are the window / sink entry's.
 template <bool WINDOW, bool SINK = false, bool TREE = false>
 int pvq_forward(const void* q16, const long long* q_strides2, int in_fmt, const void* k_pool, const void* v_pool, const int* block_table,
                 long long table_stride, int num_pages, int page_size, int max_pages, const float* scale_k, const float* scale_v, void* out,
@@ -56,8 +58,9 @@ int pvq_forward(const void* q16, const long long* q_strides2, int in_fmt, const 
                 void* workspace, size_t workspace_bytes, void* stream, const float* sinks = nullptr,
                 const unsigned long long* tree_mask = nullptr) {
     static_assert(WINDOW || !SINK, "the sink kernel is a window kernel");
-    static_assert(!TREE || !WINDOW, "the tree kernel is the causal kernel");
     if (TREE && (!tree_mask || (size_t)tree_mask % 8 != 0)) return QATTN_ERR_INVALID_ARG;
+    // a tree under a window (include/qattn_paged_varlen_tree_window.h): causal, and a window that holds every ancestor of a draft token
+    if (TREE && WINDOW && (window_right != 0 || (window_left != -1 && window_left < 63))) return QATTN_ERR_INVALID_ARG;
     if (WINDOW && (window_left < -1 || window_right < -1)) return QATTN_ERR_INVALID_ARG;
     if (SINK && (!sinks || (size_t)sinks % 4 != 0)) return QATTN_ERR_INVALID_ARG;
     // ---- the paging arguments, as qattn_fp8_attention_paged_splitkv_forward
@@ -160,5 +163,17 @@ int pvq_forward(const void* q16, const long long* q_strides2, int in_fmt, const 
     if (row_path) return skv_launch_path(plse, ppath, row_path, rows, ns, st);
     return QATTN_OK;
 }
+
+// pvq_forward<true, true, true> behind a function of its own (qattn_paged_varlen_splitkv_tree_sink_fp8.hip), so that the sink kernels are
+// compiled in their own unit: qattn_fp8_attention_paged_varlen_tree_window_forward calls it when `sinks` is given.  The arguments are that
+// entry's, in its order.
+int pvq_tree_window_sink_forward(const void* q16, const long long* q_strides2, int in_fmt, const void* k_pool, const void* v_pool,
+                                 const int* block_table, long long table_stride, int num_pages, int page_size, int max_pages,
+                                 const float* scale_k, const float* scale_v, void* out, float* lse, const int* cu_seqlens_q,
+                                 const int* seqused_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int Skv, int D, int fp8_fmt,
+                                 int numerics, const unsigned long long* tree_mask, int window_left, int window_right, const float* sinks,
+                                 float sm_scale, int precision, int num_splits, void* q8, float* scale_q, unsigned char* row_path,
+                                 float* partial_o, float* partial_lse, unsigned char* partial_path, void* workspace, size_t workspace_bytes,
+                                 void* stream);
 
 }  // namespace qattn

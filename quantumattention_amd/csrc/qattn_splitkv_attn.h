@@ -308,15 +308,60 @@ void attn_paged_varlen_splitkv_tree_fp8_kernel(const SkvAttn a, const SkvPages p
 #undef QATTN_SKV_PAGED
 }
 
-// which of the ten kernels a launch runs (kSkvWindow + one of the first three: that kernel under a window; + kSkvSink: with a sink;
-// kSkvTree + kSkvPagedVarq: the packed paged kernel under a draft tree)
+// ... and the draft tree over the packed paged WINDOW kernel, without and with a sink (QATTN_SKV_TREE with QATTN_SKV_WINDOW;
+// include/qattn_paged_varlen_tree_window.h): the kernels of qattn_paged_varlen_splitkv_tree_window_fp8.hip (both sweeps) and
+// qattn_paged_varlen_splitkv_tree_sink_fp8.hip (the exact instances only, as the sink kernels above)
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_paged_varlen_splitkv_tree_window_fp8_kernel(const SkvAttn a, const SkvPages pg, const SkvVarq vq, const SkvWindow wn,
+                                                      const SkvTree tr, const int two, const int sel) {
+#define QATTN_SKV_PAGED 1
+#define QATTN_SKV_VARQ 1
+#define QATTN_SKV_WINDOW 1
+#define QATTN_SKV_SINK 0
+#define QATTN_SKV_TREE 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
+#undef QATTN_SKV_SINK
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_paged_varlen_splitkv_tree_window_sink_fp8_kernel(const SkvAttn a, const SkvPages pg, const SkvVarq vq, const SkvWindow wn,
+                                                           const SkvSink sn, const SkvTree tr, const int two, const int sel) {
+#define QATTN_SKV_PAGED 1
+#define QATTN_SKV_VARQ 1
+#define QATTN_SKV_WINDOW 1
+#define QATTN_SKV_SINK 1
+#define QATTN_SKV_TREE 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_TREE
+#undef QATTN_SKV_SINK
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+// which of the twelve kernels a launch runs (kSkvWindow + one of the first three: that kernel under a window; + kSkvSink: with a sink;
+// kSkvTree + kSkvPagedVarq: the packed paged kernel under a draft tree; + kSkvWindow: the tree over its window kernel; + kSkvSink: with a sink)
 constexpr int kSkvContig = 0, kSkvPaged = 1, kSkvPagedVarq = 2, kSkvWindow = 4, kSkvSink = 8, kSkvTree = 16;
 
 template <int D, int FMT, int MODE>
 static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys,
                           int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}, const SkvTree& tr = SkvTree{}) {
     return fpv_precision_ladder(precision, max_keys, a.two_term_keys, want_lse, [&](auto byte, int two, int sel) {
-        if constexpr (MODE == kSkvTree + kSkvPagedVarq)
+        if constexpr (MODE == kSkvTree + kSkvSink + kSkvWindow + kSkvPagedVarq) {
+            if constexpr (decltype(byte)::value) return (int)QATTN_ERR_LAUNCH;   // (as the sink kernels below: want_lse = true)
+            else
+                return fpv_launch(attn_paged_varlen_splitkv_tree_window_sink_fp8_kernel<D, FMT, false>, grid, fpv_lds_bytes(D), st, a, pg, vq, wn,
+                                  sn, tr, two, sel);
+        } else if constexpr (MODE == kSkvTree + kSkvWindow + kSkvPagedVarq)
+            return fpv_launch(attn_paged_varlen_splitkv_tree_window_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg,
+                              vq, wn, tr, two, sel);
+        else if constexpr (MODE == kSkvTree + kSkvPagedVarq)
             return fpv_launch(attn_paged_varlen_splitkv_tree_fp8_kernel<D, FMT, decltype(byte)::value>, grid, fpv_lds_bytes(D), st, a, pg, vq, tr,
                               two, sel);
         else if constexpr ((MODE & kSkvSink) != 0) {

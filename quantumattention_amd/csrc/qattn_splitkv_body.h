@@ -28,6 +28,16 @@
 // token's 64-bit word `tr.mask[token]` is set -- one load per lane before the sweep loop, applied in the edge branch below, which is then
 // entered for every chunk that holds a key >= delta.  The split plan, khi, c_first, n_wg, the ring and the epilogue are the causal text:
 // a word with the bits 0 .. p set gives the causal kernel's bits.  (The entry is causal: its driver sets a.causal.)
+// QATTN_SKV_TREE with QATTN_SKV_WINDOW (and, optionally, QATTN_SKV_SINK; include/qattn_paged_varlen_tree_window.h) puts the draft tree over
+// the WINDOW text instead, for windows (left, 0) with left = -1 or left >= 63: a draft token of a sequence with Sq_i <= 64 queries sits at
+// sequence position delta + DEPTH, depth = the set bits of its word below its own index, so wherever the window text takes a row's
+// position for the window's LOWER edge (lo_l, and through smin / smax klo and edge_lo) this text takes the row's depth; the upper edge
+// (hi_l, khi, edge) stays by position, as the tree text has it.  The least and the greatest depth of the tile's valid rows (dmin, dmax)
+// are reduced per wave from the tile's words BEFORE the plan's `keys` count and the `sel` return, so that a chain -- depth = position --
+// reproduces the window kernel's klo, keys, selection and trip range.  With left >= 63 every lo_l <= max(delta, 0): the lower edge never
+// cuts a draft key, so one comparison serves committed and draft keys alike.  A sequence with more than 64 queries reads no word and is
+// the window text (depth = position).  Both switches off the combination: the text above, token for token
+// (profiles/tree_window/code_objects_vs_parent.log).
 // In scope: template parameters D, FMT, BYTE; arguments a (SkvAttn), two, sel, -- paged -- pg (SkvPages), -- packed queries -- vq,
 // -- window -- wn, -- sink -- sn (SkvSink) and -- tree -- tr (SkvTree).
 #if QATTN_SKV_VARQ
@@ -100,7 +110,36 @@
     // positions of the tile's valid rows: [smin, smax] (a tile that crosses a head boundary holds a last and a first position)
     const int g_first = r_first / SKV_SQ, g_last = r_last / SKV_SQ;
     const int smin = g_first != g_last ? 0 : r_first - g_first * SKV_SQ, smax = g_first != g_last ? SKV_SQ - 1 : r_last - g_first * SKV_SQ;
-#if QATTN_SKV_WINDOW
+#if QATTN_SKV_WINDOW && QATTN_SKV_TREE
+    // depths of the tile's valid rows: [dmin, dmax].  Every wave reduces the tile's 128 words by itself -- two per lane, no LDS beside the
+    // ring, no barrier -- and the result is workgroup-uniform.  Row rr of the kv head's packed rows is position rr % Sq_i of the sequence
+    // (any head: the word is the token's); q_start + position < q_start + Sq_i <= total_q.  A sequence with more than 64 queries: positions
+    int dmin = smin, dmax = smax;
+    if (SKV_SQ <= 64) {
+        int d_lo = INT_MAX, d_hi = -1;
+#pragma unroll
+        for (int i = 0; i < kFpvTile; i += 64) {
+            const int rr = r_first + i + lane;
+            if (rr <= r_last) {
+                const int pp = rr % SKV_SQ;
+                const int d = __builtin_popcountll(tr.mask[q_start + pp] & ((1ull << pp) - 1ull));
+                d_lo = min(d_lo, d);
+                d_hi = max(d_hi, d);
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            d_lo = min(d_lo, __shfl_xor(d_lo, off));
+            d_hi = max(d_hi, __shfl_xor(d_hi, off));
+        }
+        dmin = __builtin_amdgcn_readfirstlane(d_lo);
+        dmax = __builtin_amdgcn_readfirstlane(d_hi);
+    }
+    // [klo, khi]: the keys of the split that the tile's valid rows attend -- the lower end by depth, the upper end by position
+    const int klo = max(k_begin, wn.left < 0 ? 0 : clampl((long)dmin + win_lo, 0, L));
+    const int khi = min(k_end - 1, clampl((long)smax + win_hi, -1, L - 1));
+    const int keys = max(khi - klo + 1, 0);       // the keys this workgroup sweeps
+#elif QATTN_SKV_WINDOW
     // [klo, khi]: the keys of the split that the tile's valid rows attend
     const int klo = max(k_begin, wn.left < 0 ? 0 : clampl((long)smin + win_lo, 0, L));
     const int khi = min(k_end - 1, clampl((long)smax + win_hi, -1, L - 1));
@@ -192,10 +231,22 @@
     // the first and the last key this lane's row attends (a padding row: position >= Sq, masked as attn_vfp8_window_kernel masks it), and
     // where a chunk crosses an edge of some valid row: its end above `edge`, its start below `edge_lo`
     const long pos = (long)r - (long)g * SKV_SQ;
+#if QATTN_SKV_TREE
+    // the word of this lane's token, as in the tree text below, and the row's depth in the position's place at the window's lower edge
+    const bool tree_l = SKV_SQ <= 64 && rvalid;
+    const unsigned long long tword = tree_l ? tr.mask[tok] : ~0ull;
+    const int tree_lo = SKV_SQ <= 64 ? (int)max(delta, 0L) : INT_MAX;
+    const long dep = tree_l ? (long)__builtin_popcountll(tword & ((1ull << (int)pos) - 1ull)) : pos;
+    const int lo_l = wn.left < 0 ? 0 : clampl(dep + win_lo, 0, L);
+    const int hi_l = clampl(pos + win_hi, -1, L - 1);
+    const int edge = clampl((long)smin + win_hi, -1, L);
+    const int edge_lo = wn.left < 0 ? 0 : clampl((long)dmax + win_lo, 0, L);
+#else
     const int lo_l = wn.left < 0 ? 0 : clampl(pos + win_lo, 0, L);
     const int hi_l = clampl(pos + win_hi, -1, L - 1);
     const int edge = clampl((long)smin + win_hi, -1, L);
     const int edge_lo = wn.left < 0 ? 0 : clampl((long)smax + win_lo, 0, L);
+#endif
     // The keys below lo_i that share its chunk: no row attends them, so their P is exactly 0 -- and 0 x NaN is NaN in the matrix pipe.
     // The workgroup whose first chunk holds lo_i zeroes their V bytes once the stage has landed, before anyone reads it (the mirror of
     // skv_zero_v_tail; K needs nothing).
@@ -240,7 +291,24 @@
         v16f s0, s1;
         v8i vf0, vf1;
         sw.qk(t, qf, s0, s1, vf0, vf1);
-#if QATTN_SKV_WINDOW
+#if QATTN_SKV_WINDOW && QATTN_SKV_TREE
+        // ---- the ragged tail at L, the window's two edges and the draft tree by token, under a workgroup-uniform condition
+        if (__builtin_expect(k0 + 64 > L || k0 + 63 > edge || k0 < edge_lo || k0 + 63 >= tree_lo, 0)) {
+            // bit i of aw: key k0 + i passes the tree, as in the tree text below.  (With a word: -L <= k0 - delta < 64 + Sq_i, an int.)
+            const int sh = (int)((long)k0 - delta);
+            unsigned long long aw = ~0ull;
+            if (tree_l) aw = sh >= 64 ? 0ull : sh >= 0 ? tword >> sh : sh > -64 ? (tword << -sh) | ((1ull << -sh) - 1ull) : ~0ull;
+            aw >>= 4 * hh;
+            const int base = k0 + 4 * hh;
+#pragma unroll
+            for (int e = 0; e < 32; e++) {
+                const int kb = 32 * (e >> 4) + (e & 3) + 8 * ((e & 15) >> 2);   // (kb + 4 hh <= 63)
+                const int key = base + kb;
+                v16f& sx = (e >> 4) ? s1 : s0;
+                sx[e & 15] = (key < lo_l || key > hi_l || !((aw >> kb) & 1ull)) ? -INFINITY : sx[e & 15];
+            }
+        }
+#elif QATTN_SKV_WINDOW
         // ---- the ragged tail at L and the window's two edges by token, under a workgroup-uniform condition
         if (__builtin_expect(k0 + 64 > L || k0 + 63 > edge || k0 < edge_lo, 0)) {
             const int base = k0 + 4 * hh;

@@ -1124,3 +1124,109 @@ def fp8_paged_kv_cache_compact_(
 @_register_fake("quantumattention_amd::fp8_paged_kv_cache_compact_")
 def _(k_pool, v_pool, block_table, seqlens, cu_seqlens, accept_index, accept_lens, num_kv_heads, head_dim, num_pages, page_size):
     return None
+
+
+# ---- the tree under a sliding window, optionally with learned sinks (include/qattn_paged_varlen_tree_window.h): the tree op's arguments
+# with window_left, window_right after num_splits and `sinks`, fp32 [Hq] or None, after them.
+
+@_custom_op("quantumattention_amd::fp8_paged_varlen_splitkv_tree_window_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_paged_varlen_splitkv_tree_window_attention_forward(
+    query: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    tree_mask: torch.Tensor,
+    max_seqlen_q: int,
+    seqlen_k: int,
+    num_pages: int,
+    page_size: int,
+    num_splits: int,
+    window_left: int,
+    window_right: int,
+    sinks: Optional[torch.Tensor] = None,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    precision: str = "accurate",
+    return_lse: bool = False,
+    return_partials: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp8_paged_varlen_splitkv_tree_attention_forward under a sliding window (left, 0), left = -1 or left >= 63, optionally with learned
+    sinks: a draft token sits at sequence position L_b - Sq_b + depth, depth = the set bits of its word below its own index, and the
+    window's lower edge is taken from there.  Reference implementation: paged_varlen._attend_varlen_eager with tree_mask=, window= and
+    sinks=.  Arguments are validated by tree.fp8_attn_paged_varlen_tree_window_func."""
+    res = _native.fp8_attention_paged_varlen(
+        query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, cu_seqlens_q, max_seqlen_q=max_seqlen_q, Skv=seqlen_k,
+        num_pages=num_pages, page_size=page_size, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics, is_causal=True,
+        sm_scale=0.0 if scale is None else float(scale), precision=precision, num_splits=num_splits, return_lse=return_lse,
+        return_partials=return_partials, window=(window_left, window_right), sinks=sinks, tree_mask=tree_mask)
+    return _skv_pack(res, query, return_lse, return_partials)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_varlen_splitkv_tree_window_attention_forward")
+def _(query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, cu_seqlens_q, tree_mask, max_seqlen_q, seqlen_k, num_pages, page_size,
+      num_splits, window_left, window_right, sinks=None, fp8_format="e4m3", numerics="compiled", precision="accurate", return_lse=False,
+      return_partials=False, *, scale=None):
+    total_q, Hq, _ = query.shape
+    return _skv_fake(query, (total_q, Hq), (Hq, total_q), num_splits, return_lse, return_partials)
+
+
+# ---- the rotary embedding at the caller's positions (include/qattn_paged_varlen_rope_pos.h): the rotating packed append and the packed
+# rotation with `positions`, int64 [total] -- a tree node sits at base + depth.
+
+@_custom_op("quantumattention_amd::fp8_paged_varlen_rope_pos_kv_cache_append_", mutates_args=("k_pool", "v_pool", "seqlens"), device_types=("cuda",))
+def fp8_paged_varlen_rope_pos_kv_cache_append_(
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens: torch.Tensor,
+    k_new: torch.Tensor,
+    v_new: torch.Tensor,
+    cu_seqlens: torch.Tensor,
+    positions: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    num_pages: int,
+    page_size: int,
+    fp8_format: str = "e4m3",
+    interleaved: bool = False,
+    advance: bool = True,
+) -> None:
+    """fp8_paged_varlen_rope_kv_cache_append_ with token t rotated with row clamp(positions[t], 0, T - 1) of cos / sin instead of the row of
+    its key's index; where the key is stored is unchanged.  Reference implementation: paged_varlen._append_varlen_rope_pos_eager.
+    Arguments are validated by paged_varlen.paged_kv_cache_append_varlen_rope_pos_fp8."""
+    _native.paged_kv_cache_append_varlen_rope_pos_fp8(k_pool, v_pool, scale_k, scale_v, block_table, seqlens, k_new, v_new, cu_seqlens, positions,
+                                                      cos, sin, num_pages=num_pages, page_size=page_size,
+                                                      fp8_dtype=_native.fp8_dtype_of(fp8_format), interleaved=interleaved, advance=advance)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_varlen_rope_pos_kv_cache_append_")
+def _(k_pool, v_pool, scale_k, scale_v, block_table, seqlens, k_new, v_new, cu_seqlens, positions, cos, sin, num_pages, page_size,
+      fp8_format="e4m3", interleaved=False, advance=True):
+    return None
+
+
+@_custom_op("quantumattention_amd::rope_packed_positions", mutates_args=(), device_types=("cuda",))
+def rope_packed_positions(
+    x: torch.Tensor,
+    positions: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    interleaved: bool = False,
+) -> torch.Tensor:
+    """Packed rows x [total, H, D], row t rotated with row clamp(positions[t], 0, T - 1) of cos / sin (include/qattn_paged_varlen_rope_pos.h)
+    -> dense [total, H, D].  Reference implementation: rope.apply_rope_eager at those positions.  Arguments are validated by
+    paged_varlen.apply_rope_positions."""
+    return _native.rope_packed_positions(x, positions, cos, sin, interleaved=interleaved)
+
+
+@_register_fake("quantumattention_amd::rope_packed_positions")
+def _(x, positions, cos, sin, interleaved=False):
+    return x.new_empty(x.shape)

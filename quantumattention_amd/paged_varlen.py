@@ -28,8 +28,11 @@ memory:
     paged_kv_cache_append_varlen_rope_fp8(cache, qkv[:, Hq:Hq + Hkv], qkv[:, Hq + Hkv:], cu, cos, sin)
     out = fp8_attn_paged_varlen_func(q, cache, cu, max_seqlen_q, causal=True, max_seqlen_k=longest_live_sequence)
 
-Package attributes, not names of `__all__`.  Not offered: RoPE fused into the attention's q pre-pass, per-slot position offsets or a
-positions tensor, a partial rotary_dim, scaled / YaRN tables beyond what the caller puts into cos / sin, RoPE in the padded and the
+At the CALLER's positions instead (include/qattn_paged_varlen_rope_pos.h; vLLM's `positions`, and the base + depth
+of a draft tree's tokens, `tree.tree_positions`): `paged_kv_cache_append_varlen_rope_pos_fp8` and `apply_rope_positions`.
+
+Package attributes, not names of `__all__`.  Not offered: RoPE fused into the attention's q pre-pass, per-slot position offsets, a partial
+rotary_dim, multi-axis (M-RoPE) positions, scaled / YaRN tables beyond what the caller puts into cos / sin, RoPE in the padded and the
 contiguous appends, a per-token slot_mapping form, a per-call table whose batch differs from the cache's slots, the contiguous
 `KVCacheFP8`, page allocation.  Sliding windows: splitkv_window.fp8_attn_paged_varlen_window_func."""
 import math
@@ -42,7 +45,7 @@ from . import _native, nn
 from .kvcache import _is_int
 from .paged import PagedKVCacheFP8, _append_eager, _cache_reason, _lens_reason, gather_paged_eager
 from .rope import _TABLE_DTYPES, apply_rope_eager
-from .splitkv import _CPU_NUM_CUS, MAX_SPLITS, PreparedKV, _splitkv_eager
+from .splitkv import _CPU_NUM_CUS, MAX_SPLITS, PreparedKV, _splitkv_eager_depth
 from .utils import checks
 
 
@@ -122,7 +125,10 @@ def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, 
     keys gathered through the table, scattered into the packed outputs.  Rows of tokens that belong to no sequence: zeros.  (This path
     reads cu_seqlens_q, seqused_k and the table on the host.)
     tree_mask = int64 [total_q] (None: none; with causal): the draft tree of include/qattn_paged_varlen_tree.h -- in a slot with at most 64
-    queries position p keeps key j >= max(delta, 0), delta = L_b - Sq_b, only if bit j - delta of the token's word is set."""
+    queries position p keeps key j >= max(delta, 0), delta = L_b - Sq_b, only if bit j - delta of the token's word is set.
+    tree_mask with window = (left, 0) (and, optionally, sinks): the definition of include/qattn_paged_varlen_tree_window.h -- in such a
+    slot the window's lower edge is taken from the token's DEPTH (the set bits of its word below its own index) and cuts committed keys
+    only; a slot with more than 64 queries is the window rule."""
     total_q, Hq, D = q.shape
     B = cache.batch_size
     n = ns if ns > 1 else 0
@@ -142,16 +148,20 @@ def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, 
             continue
         one = PreparedKV(kv.k[b:b + 1], kv.v[b:b + 1], kv.scale_k[b:b + 1], kv.scale_v[b:b + 1], (1,) + tuple(kv.shape[1:]), kv.fp8_format,
                          kv.dtype, kv.numerics, "rowmajor")
-        also = None
+        also = depth = None
         if tree_mask is not None and end - start <= 64:
+            if window is not None:   # depth_p = popcount(w_p & (2^p - 1)): the set bits below p (an arithmetic shift: the low bits are the word's)
+                p = torch.arange(end - start, device=q.device)
+                below = ((tree_mask[start:end, None] >> torch.arange(64, device=q.device)) & 1).bool() & (torch.arange(64, device=q.device) < p[:, None])
+                depth = [below.sum(1)]
             delta = min(max(int(seqused_k[b]), 0), Skv) - (end - start)
             bits = ((tree_mask[start:end, None] >> torch.arange(64, device=q.device)) & 1).bool()           # [Sq_b, 64]: bit i of word p
             j0, j1 = max(delta, 0), max(min(delta + 64, Skv), 0)
             also = torch.ones((1, end - start, Skv), dtype=torch.bool, device=q.device)
             if j1 > j0:
                 also[0, :, j0:j1] = bits[:, j0 - delta:j1 - delta]
-        o, l, p_o, p_l, p_p = _splitkv_eager(q[start:end].transpose(0, 1)[None], one, causal, scale, seqused_k[b:b + 1], ns, precision,
-                                             keep_also=also, sinks=sinks, window=window)
+        o, l, p_o, p_l, p_p = _splitkv_eager_depth(q[start:end].transpose(0, 1)[None], one, causal, scale, seqused_k[b:b + 1], ns, precision,
+                                                   also, sinks, window, depth)
         out[start:end] = o[0].transpose(0, 1)
         lse[:, start:end] = l[0]
         if n:
@@ -524,3 +534,157 @@ def apply_rope_paged_varlen(x: Tensor, cache: PagedKVCacheFP8, cu_seqlens: Tenso
         res = nn._ops().rope_paged_varlen(x, cache.seqlens, cu_seqlens, cos, sin, cache.capacity, il, ap)
         return res if out is None else out.copy_(res)
     return _native.rope_paged_varlen(x, cache.seqlens, cu_seqlens, cos, sin, capacity=cache.capacity, interleaved=il, appended=ap, out=out)
+
+
+# ---- the rotary embedding at the CALLER's positions (include/qattn_paged_varlen_rope_pos.h) ------------------------------------------------
+def _positions_reason(positions, total: int, device) -> Optional[str]:
+    if not isinstance(positions, Tensor) or positions.dtype != torch.int64:
+        return f"Expected positions to be a torch.int64 tensor [total], but got {getattr(positions, 'dtype', type(positions))}"
+    if tuple(positions.shape) != (total,):
+        return f"Expected positions to have shape [{total}] (one position per packed token), but got {list(positions.shape)}."
+    if positions.device != device:
+        return f"Expected positions to be on {device}, but got {positions.device} instead."
+    if not positions.is_contiguous():
+        return "Expected positions to be contiguous"
+    return None
+
+
+def paged_varlen_rope_pos_append_input_reason(cache, k_new, v_new, cu_seqlens, positions, cos, sin) -> Optional[str]:
+    """The first rule the arguments of `paged_kv_cache_append_varlen_rope_pos_fp8` break, or None: `paged_varlen_append_input_reason`,
+    then positions int64 [total], contiguous, on the cache's device, then the table rules of `paged_varlen_rope_append_input_reason`
+    with any T >= 1 (positions are clamped into the tables).  Shapes, dtypes, devices and strides only: nothing is read on the device."""
+    reason = paged_varlen_append_input_reason(cache, k_new, v_new, cu_seqlens)
+    if reason:
+        return reason
+    reason = _positions_reason(positions, k_new.shape[0], cache.device)
+    if reason:
+        return reason
+    return _rope_tables_reason(cos, sin, cache.shape[3], 1, cache.device)
+
+
+def _clamped_rows(positions: Tensor, rows, T: int):
+    """the table rows of the packed rows `rows`: clamp(positions[row], 0, T - 1), as a host list (the eager definitions only)"""
+    at = positions.tolist()
+    return [min(max(int(at[r]), 0), T - 1) for r in rows]
+
+
+def _append_varlen_rope_pos_eager(cache: PagedKVCacheFP8, k_new: Tensor, v_new: Tensor, cu_seqlens: Tensor, positions: Tensor, cos: Tensor,
+                                  sin: Tensor, interleaved: bool, advance: bool) -> None:
+    """CPU tensors and config.attention.force_eager_fallback: the rule's composition -- `apply_rope_eager` on the owned rows of k_new at
+    the caller's (clamped) positions, then `_append_varlen_eager`.  (This path reads cu_seqlens and positions on the host.)"""
+    rows, _ = _rope_positions_host(cache, cu_seqlens, k_new.shape[0], cos.shape[0], False)
+    k_rot = torch.zeros(k_new.shape, dtype=k_new.dtype, device=k_new.device)      # (rows nobody owns are not read by the append)
+    if rows:
+        k_rot[rows] = _rope_rows_eager(k_new, rows, _clamped_rows(positions, rows, cos.shape[0]), cos, sin, interleaved)
+    _append_varlen_eager(cache, k_rot, v_new, cu_seqlens, advance)
+
+
+def paged_kv_cache_append_varlen_rope_pos_fp8(cache: PagedKVCacheFP8, k_new: Tensor, v_new: Tensor, cu_seqlens: Tensor, positions: Tensor,
+                                              cos: Tensor, sin: Tensor, *, interleaved: bool = False, advance: bool = True) -> PagedKVCacheFP8:
+    """`paged_kv_cache_append_varlen_rope_fp8` at the CALLER's positions (vLLM's `positions`); in place, returns `cache`.
+
+    cache, k_new, v_new, cu_seqlens, cos, sin, interleaved, advance: those of `paged_kv_cache_append_varlen_rope_fp8`, except that the
+    tables may hold any T >= 1 rows.  positions: int64 [total] on the device.  Token t is rotated with table row
+    clamp(positions[t], 0, T - 1).  WHERE the key is stored is unchanged: token start_b + t becomes key seqlens[b] + t of slot b.  Under
+    tree-shaped speculative decoding a draft token's position is base + depth (`tree_positions`): siblings share a position while their
+    keys lie next to each other.  Rows behind cu[B] are not read.
+    The rule: pools and seqlens end, byte for byte, as `apply_rope_eager` on K at those positions followed by
+    `paged_kv_cache_append_varlen_fp8` leaves them; with positions[start_b + t] = seqlens[b] + t the bits are those of
+    `paged_kv_cache_append_varlen_rope_fp8`.  Exactly the bytes of the appended keys change.
+    Everything is read on the device: no host synchronisation, no allocation (16-bit tables excepted), graph-capture safe, and a
+    captured call follows the later contents of positions, cu_seqlens, seqlens, the table and cos / sin.  total = 0 returns at once.
+    CPU tensors and config.attention.force_eager_fallback run the eager definition (`_append_varlen_rope_pos_eager`); on the device
+    there is no fallback.  Invalid input raises ValueError(reason).  Not offered: a partial rotary_dim, multi-axis (M-RoPE) positions,
+    positions in the padded and the contiguous appends."""
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = paged_varlen_rope_pos_append_input_reason(cache, k_new, v_new, cu_seqlens, positions, cos, sin)
+        if reason:
+            raise ValueError(reason)
+    if k_new.shape[0] == 0:
+        return cache
+    cos, sin = _fp32_tables(cos, sin)
+    il = bool(interleaved)
+    eager = (not k_new.is_cuda or checks.config_value("attention.force_eager_fallback")) and not torch.compiler.is_dynamo_compiling()
+    if eager:
+        if cache.layout != "rowmajor":
+            raise ValueError("the eager definition needs a cache made on a CPU device or under config.attention.force_eager_fallback")
+        _append_varlen_rope_pos_eager(cache, k_new, v_new, cu_seqlens, positions, cos, sin, il, bool(advance))
+        return cache
+    if cache.layout != "frag":
+        raise ValueError("this cache holds row-major bytes for the eager definition; make it on the device without "
+                         "config.attention.force_eager_fallback")
+    ok, why = nn._pre_check_can_use_hip_attention(device=k_new.device)
+    if not ok:
+        raise ValueError(why)
+    if torch.compiler.is_compiling():
+        nn._ops().fp8_paged_varlen_rope_pos_kv_cache_append_(cache.k, cache.v, cache.scale_k, cache.scale_v, cache.block_table, cache.seqlens,
+                                                             k_new, v_new, cu_seqlens, positions, cos, sin, cache.num_pages, cache.page_size,
+                                                             cache.fp8_format, il, bool(advance))
+    else:
+        # outside a trace: the op's own body, without the dispatcher's bookkeeping for a mutating op (as paged_kv_cache_append_varlen_fp8)
+        _native.paged_kv_cache_append_varlen_rope_pos_fp8(cache.k, cache.v, cache.scale_k, cache.scale_v, cache.block_table, cache.seqlens,
+                                                          k_new, v_new, cu_seqlens, positions, cos, sin, num_pages=cache.num_pages,
+                                                          page_size=cache.page_size, fp8_dtype=_native.fp8_dtype_of(cache.fp8_format),
+                                                          interleaved=il, advance=bool(advance))
+    return cache
+
+
+def rope_positions_input_reason(x, positions, cos, sin, out=None) -> Optional[str]:
+    """The first rule the arguments of `apply_rope_positions` break, or None.  Shapes, dtypes, devices and strides only."""
+    if not isinstance(x, Tensor) or x.dim() != 3:
+        return "NYI: x must be a 3-D tensor [total, H, head_dim]"
+    if x.requires_grad:
+        return "NYI: x must be a leaf tensor (no backward)"
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        return f"Expected x to have dtype torch.float16 or torch.bfloat16, but got x.dtype: {x.dtype} instead."
+    D = x.shape[2]
+    if D not in (64, 128, 256):
+        return f"head_dim must be one of [64, 128, 256], got {D}"
+    if x.shape[1] == 0:
+        return "Expected a non-empty head count"
+    if x.shape[0] > 0 and not _q_rows_addressable(x):
+        return (f"Expected x to have head_dim innermost and 16-byte-aligned rows (strides that are multiples of 8 elements), but got "
+                f"strides {tuple(x.stride())} at storage offset {x.storage_offset()}; pass x.contiguous()")
+    reason = _positions_reason(positions, x.shape[0], x.device)
+    if reason:
+        return reason
+    if out is not None:
+        if not isinstance(out, Tensor) or out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+            return f"Expected out to have x's shape {list(x.shape)}, dtype and device"
+        if not out.is_contiguous() or (not torch.compiler.is_dynamo_compiling() and out.storage_offset() % 8 != 0):
+            return "Expected out to be contiguous and 16-byte aligned"
+    return _rope_tables_reason(cos, sin, D, 1, x.device)
+
+
+def apply_rope_positions(x: Tensor, positions: Tensor, cos: Tensor, sin: Tensor, *, interleaved: bool = False,
+                         out: Optional[Tensor] = None) -> Tensor:
+    """Rotate packed rows -- q, any strided q slice of a packed projection -- at the CALLER's positions.
+
+    x [total, H, D] bf16 / fp16, D in {64, 128, 256}, read through its {token, head} strides under the packed append's stride rules.
+    positions: int64 [total] on x's device; row t is rotated with table row clamp(positions[t], 0, T - 1) of cos / sin [T, D/2] (as
+    `paged_kv_cache_append_varlen_rope_pos_fp8` takes them).  Returns dense [total, H, D] in x.dtype (`out`, if given: contiguous,
+    16-byte aligned).  Every row is read and written: there is no cu_seqlens here.  Bit for bit `apply_rope_eager` at these positions,
+    and with the positions of `apply_rope_paged_varlen` its bits.
+    One launch; everything is read on the device: no host synchronisation, no allocation beyond the result (16-bit tables excepted),
+    graph-capture safe.  CPU tensors and config.attention.force_eager_fallback run the eager definition; on the device there is no
+    fallback.  Invalid input raises ValueError(reason)."""
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = rope_positions_input_reason(x, positions, cos, sin, out)
+        if reason:
+            raise ValueError(reason)
+    cos, sin = _fp32_tables(cos, sin)
+    il = bool(interleaved)
+    eager = (not x.is_cuda or checks.config_value("attention.force_eager_fallback")) and not torch.compiler.is_dynamo_compiling()
+    if eager:
+        res = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+        rows = list(range(x.shape[0]))
+        if rows:
+            res[rows] = _rope_rows_eager(x, rows, _clamped_rows(positions, rows, cos.shape[0]), cos, sin, il)
+        return res
+    ok, why = nn._pre_check_can_use_hip_attention(device=x.device)
+    if not ok:
+        raise ValueError(why)
+    if torch.compiler.is_compiling():
+        res = nn._ops().rope_packed_positions(x, positions, cos, sin, il)
+        return res if out is None else out.copy_(res)
+    return _native.rope_packed_positions(x, positions, cos, sin, interleaved=il, out=out)

@@ -203,6 +203,15 @@ def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, keep_also=Non
     free of the sink and it enters merge.merge_attn_states_eager once.  +inf and NaN make the head's rows NaN.
     keep_also = bool [B, Sq, Skv] (None: none): one more condition on (position, key), on top of the rule above -- the draft tree of
     tree.fp8_attn_paged_varlen_tree_func; the splits and the path bytes do not see it."""
+    return _splitkv_eager_depth(q, kv, causal, scale, seqused_k, ns, precision, keep_also, sinks, window, None)
+
+
+def _splitkv_eager_depth(q, kv, causal, scale, seqused_k, ns, precision, keep_also, sinks, window, depth):
+    """`_splitkv_eager`, whose definition this is, with one more input for the tree under a window
+    (include/qattn_paged_varlen_tree_window.h).  depth = a list per batch element of None or an int64 [Sq] tensor (None: none anywhere),
+    with window: an element with depths is a slot of draft tokens -- position p sits at sequence position L - Sq + depth[p], the window's
+    lower edge is taken from there and cuts COMMITTED keys (j < L - Sq) only, and the path byte's klo takes the least depth of the
+    tile's rows where the window rule takes their least position."""
     fp8_dtype = _native.fp8_dtype_of(kv.fp8_format)
     B, Hq, Sq, D = q.shape
     _, Hkv, Skv, _ = kv.shape
@@ -224,8 +233,11 @@ def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, keep_also=Non
         for b, L in enumerate(used):
             lo, hi = split_plan(L, ns)[s] if window is None else split_plan_window(L, Sq, window[0], ns)[s]
             m = (key >= lo) & (key < hi)
+            dep = None if depth is None else depth[b]
             if window is not None:
-                if window[0] >= 0:
+                if window[0] >= 0 and dep is not None:
+                    m = m & ((key >= dep[:, None] + (L - Sq - window[0])) | (key >= L - Sq))
+                elif window[0] >= 0:
                     m = m & (key >= pos + (L - Sq - window[0]))
                 if window[1] >= 0:
                     m = m & (key <= pos + (L - Sq + window[1]))
@@ -240,6 +252,8 @@ def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, keep_also=Non
                 smax = Sq - 1 if r0 // Sq != r1 // Sq else r1 % Sq
                 if window is not None:
                     smin = 0 if r0 // Sq != r1 // Sq else r0 % Sq
+                    if dep is not None:   # the least depth of the tile's rows
+                        smin = int(dep[torch.arange(r0, r1 + 1, device=dep.device) % Sq].min())
                     klo = max(lo, 0 if window[0] < 0 else max(smin + L - Sq - window[0], 0))
                     khi = min(hi - 1, L - 1 if window[1] < 0 else smax + L - Sq + window[1])
                     keys = max(khi - klo + 1, 0)
