@@ -76,6 +76,13 @@ from .tree import fp8_attn_paged_varlen_tree_func, paged_kv_cache_compact_fp8, t
 # ... on windowed layers and layers with learned sinks, and the drafts' rotary positions (include/qattn_paged_varlen_tree_window.h,
 # include/qattn_paged_varlen_rope_pos.h): package attributes, not in __all__ (the reason functions stay in their modules, as the others)
 from .tree import fp8_attn_paged_varlen_tree_window_func, tree_positions  # noqa: E402
+# logit soft-capping for the three window entries (Gemma-2, Grok-1; include/qattn_softcap.h): package attributes, not in __all__
+from .softcap import (  # noqa: E402
+    fp8_attn_paged_softcap_func,
+    fp8_attn_paged_varlen_softcap_func,
+    fp8_attn_splitkv_softcap_func,
+    softcap_input_reason,
+)
 
 __version__ = "0.1.0"
 

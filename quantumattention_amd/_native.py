@@ -64,6 +64,8 @@ EXPORTS = (
     "qattn_fp8_attention_paged_varlen_tree_forward", "qattn_paged_kv_cache_compact_fp8",
     "qattn_fp8_attention_paged_varlen_tree_window_forward",
     "qattn_paged_kv_cache_append_varlen_rope_pos_fp8", "qattn_rope_packed_positions",
+    "qattn_fp8_attention_splitkv_softcap_forward", "qattn_fp8_attention_paged_splitkv_softcap_forward",
+    "qattn_fp8_attention_paged_varlen_softcap_forward",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -329,6 +331,16 @@ def lib() -> ctypes.CDLL:
                                                                   vp, ll, i, i, vp, vp]
     L.qattn_rope_packed_positions.restype = i
     L.qattn_rope_packed_positions.argtypes = [vp, i, vp, vp, vp, i, i, i, vp, vp, ll, i, i, vp]
+    # logit soft-capping (include/qattn_softcap.h): the window entries' arguments with the host float softcap after window_right
+    L.qattn_fp8_attention_splitkv_softcap_forward.restype = i
+    L.qattn_fp8_attention_splitkv_softcap_forward.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, f, f, i, i,
+                                                              vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.qattn_fp8_attention_paged_splitkv_softcap_forward.restype = i
+    L.qattn_fp8_attention_paged_splitkv_softcap_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i,
+                                                                    i, f, f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.qattn_fp8_attention_paged_varlen_softcap_forward.restype = i
+    L.qattn_fp8_attention_paged_varlen_softcap_forward.argtypes = [vp, vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i,
+                                                                   i, i, i, i, f, f, i, i, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1252,6 +1264,17 @@ def _sink_args(sinks, window, Hq, dev):
     return (sinks.data_ptr(),)
 
 
+def _softcap_args(softcap, window, sinks, tree_mask=None):
+    """() without a soft cap, else (the float,): the soft-cap entries (include/qattn_softcap.h) take it right after window_left, window_right."""
+    if softcap is None:
+        return ()
+    _require(window is not None, "softcap is offered by the window entries: pass window=(left, right)")
+    _require(sinks is None and tree_mask is None, "softcap is not offered with sinks or under a draft tree")
+    _require(isinstance(softcap, (int, float)) and not isinstance(softcap, bool) and math.isfinite(softcap) and softcap > 0,
+             f"softcap must be a finite float > 0, got {softcap!r}")
+    return (float(softcap),)
+
+
 def splitkv_auto_splits(B: int, Hq: int, Hkv: int, Sq: int, Skv: int, D: int, num_cus: int) -> int:
     """qattn_splitkv_auto_splits (include/qattn_splitkv.h): the num_splits = 0 rule, a pure host function of the shape and the CU count."""
     return int(lib().qattn_splitkv_auto_splits(B, Hq, Hkv, Sq, Skv, D, num_cus))
@@ -1262,7 +1285,7 @@ def fp8_attention_splitkv(q: torch.Tensor, k_frag: torch.Tensor, v_frag: torch.T
                           sm_scale: float = 0.0, precision: str = "accurate", num_splits: int = 0,
                           seqused_k: Optional[torch.Tensor] = None, return_lse: bool = False, return_partials: bool = False,
                           return_quant: bool = False, return_path: bool = False, window: Optional[Tuple[int, int]] = None,
-                          sinks: Optional[torch.Tensor] = None):
+                          sinks: Optional[torch.Tensor] = None, softcap: Optional[float] = None):
     """Split-KV attention over prepared K / V (qattn_fp8_attention_splitkv_forward, include/qattn_splitkv.h).  q [B, Hq, Sq, D] bf16 / fp16;
     k_frag / v_frag: the KFRAG / VFRAG images (flat uint8) of [B, Hkv, Skv, D] in fp8_dtype with scale_k / scale_v fp32 [B, Hkv];
     seqused_k int32 [B] on the device or None.  num_splits 0: the auto rule on the device's CU count (resolved here, on the host).
@@ -1271,14 +1294,16 @@ def fp8_attention_splitkv(q: torch.Tensor, k_frag: torch.Tensor, v_frag: torch.T
     window = (left, right): qattn_fp8_attention_splitkv_window_forward (include/qattn_splitkv_window.h) instead -- the window stands in
     is_causal's place, which is then not read; the same for the two paged functions below.
     sinks (with window; fp32 [Hq] on the device): qattn_fp8_attention_splitkv_sink_forward (include/qattn_sinks.h) -- a learned sink logit
-    per query head in the softmax denominator; the partials stay free of it.  Again the same for the two paged functions."""
+    per query head in the softmax denominator; the partials stay free of it.  Again the same for the two paged functions.
+    softcap (with window, without sinks; a finite float > 0): qattn_fp8_attention_splitkv_softcap_forward (include/qattn_softcap.h) --
+    y = softcap tanh(x / softcap) on the scaled scores, before the mask.  Again the same for the two paged functions."""
     _require(precision in ("fast", "accurate"), f"Unsupported precision for the split-KV entry: {precision!r} (expected 'fast' or 'accurate')")
     _require(q.is_cuda and q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16), "query must be a 4-D bf16 / fp16 device tensor")
     _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
     mask_args = (int(bool(is_causal)),) if window is None else _window_args(window)
     q = q.contiguous()
     B, Hq, Sq, D = q.shape
-    mask_args += _sink_args(sinks, window, Hq, q.device)
+    mask_args += _sink_args(sinks, window, Hq, q.device) + _softcap_args(softcap, window, sinks)
     _require(scale_k.dim() == 2 and scale_k.shape[0] == B and scale_k.shape == scale_v.shape, "scale_k / scale_v must be fp32 [B, Hkv]")
     Hkv = scale_k.shape[1]
     _require(Hkv > 0 and Hq % Hkv == 0, f"Hq={Hq} is not a multiple of Hkv={Hkv}")
@@ -1313,13 +1338,15 @@ def fp8_attention_splitkv(q: torch.Tensor, k_frag: torch.Tensor, v_frag: torch.T
         ws_bytes = L.qattn_fp8_attention_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, ns)
         ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
         live = lambda t: _ptr(t) if t is not None and t.numel() else None
-        fwd = (L.qattn_fp8_attention_splitkv_forward if window is None else L.qattn_fp8_attention_splitkv_window_forward if sinks is None
+        fwd = (L.qattn_fp8_attention_splitkv_softcap_forward if softcap is not None
+               else L.qattn_fp8_attention_splitkv_forward if window is None else L.qattn_fp8_attention_splitkv_window_forward if sinks is None
                else L.qattn_fp8_attention_splitkv_sink_forward)
         rc = fwd(
             q.data_ptr(), fmt_of(q.dtype), k_frag.data_ptr(), v_frag.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(),
             _ptr(lse), _ptr(seqused_k), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), *mask_args, float(sm_scale),
             _precision(precision), ns, _ptr(q8), _ptr(sq), _ptr(path), live(po), live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_attention_splitkv_forward" if window is None else "qattn_fp8_attention_splitkv_window_forward" if sinks is None
+    _check(rc, "qattn_fp8_attention_splitkv_softcap_forward" if softcap is not None
+           else "qattn_fp8_attention_splitkv_forward" if window is None else "qattn_fp8_attention_splitkv_window_forward" if sinks is None
            else "qattn_fp8_attention_splitkv_sink_forward")
     if not (return_lse or return_partials or return_quant or return_path):
         return out
@@ -1623,7 +1650,7 @@ def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: t
                                 fp8_dtype=torch.float8_e4m3fn, numerics: str = "compiled", is_causal: bool = False, sm_scale: float = 0.0,
                                 precision: str = "accurate", num_splits: int = 0, return_lse: bool = False, return_partials: bool = False,
                                 return_quant: bool = False, return_path: bool = False, window: Optional[Tuple[int, int]] = None,
-                                sinks: Optional[torch.Tensor] = None):
+                                sinks: Optional[torch.Tensor] = None, softcap: Optional[float] = None):
     """Split-KV attention over a paged cache (qattn_fp8_attention_paged_splitkv_forward, include/qattn_paged.h): fp8_attention_splitkv with
     the pools (flat uint8: the KFRAG / VFRAG images of [num_pages, Hkv, page_size, D]) and block_table int32 [B, max_pages] in place of the
     contiguous images; Skv <= max_pages page_size is the logical bound, seqused_k int32 [B] is required.  Returns what
@@ -1634,7 +1661,7 @@ def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: t
     mask_args = (int(bool(is_causal)),) if window is None else _window_args(window)
     q = q.contiguous()
     B, Hq, Sq, D = q.shape
-    mask_args += _sink_args(sinks, window, Hq, q.device)
+    mask_args += _sink_args(sinks, window, Hq, q.device) + _softcap_args(softcap, window, sinks)
     _require(scale_k.dim() == 2 and scale_k.shape[0] == B, "scale_k / scale_v must be fp32 [B, Hkv]")
     Hkv = scale_k.shape[1]
     _require(Hkv > 0 and Hq % Hkv == 0, f"Hq={Hq} is not a multiple of Hkv={Hkv}")
@@ -1665,14 +1692,16 @@ def fp8_attention_paged_splitkv(q: torch.Tensor, k_pool: torch.Tensor, v_pool: t
         ws_bytes = L.qattn_fp8_attention_paged_splitkv_workspace_bytes(B, Hq, Hkv, Sq, Skv, D, ns)
         ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
         live = lambda t: _ptr(t) if t is not None and t.numel() else None
-        fwd = (L.qattn_fp8_attention_paged_splitkv_forward if window is None else L.qattn_fp8_attention_paged_splitkv_window_forward
+        fwd = (L.qattn_fp8_attention_paged_splitkv_softcap_forward if softcap is not None
+               else L.qattn_fp8_attention_paged_splitkv_forward if window is None else L.qattn_fp8_attention_paged_splitkv_window_forward
                if sinks is None else L.qattn_fp8_attention_paged_splitkv_sink_forward)
         rc = fwd(
             q.data_ptr(), fmt_of(q.dtype), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr(), tstride, num_pages, page_size, max_pages,
             scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(), _ptr(lse), seqused_k.data_ptr(), B, Hq, Hkv, Sq, Skv, D, fmt_of(fp8_dtype),
             _numerics(numerics), *mask_args, float(sm_scale), _precision(precision), ns, _ptr(q8), _ptr(sq), _ptr(path), live(po),
             live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_attention_paged_splitkv_forward" if window is None else "qattn_fp8_attention_paged_splitkv_window_forward"
+    _check(rc, "qattn_fp8_attention_paged_splitkv_softcap_forward" if softcap is not None
+           else "qattn_fp8_attention_paged_splitkv_forward" if window is None else "qattn_fp8_attention_paged_splitkv_window_forward"
            if sinks is None else "qattn_fp8_attention_paged_splitkv_sink_forward")
     if not (return_lse or return_partials or return_quant or return_path):
         return out
@@ -1698,7 +1727,7 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
                                is_causal: bool = False, sm_scale: float = 0.0, precision: str = "accurate", num_splits: int = 0,
                                return_lse: bool = False, return_partials: bool = False, return_quant: bool = False, return_path: bool = False,
                                window: Optional[Tuple[int, int]] = None, sinks: Optional[torch.Tensor] = None,
-                               tree_mask: Optional[torch.Tensor] = None):
+                               tree_mask: Optional[torch.Tensor] = None, softcap: Optional[float] = None):
     """Split-KV attention of PACKED queries over a paged cache (qattn_fp8_attention_paged_varlen_forward, include/qattn_paged_varlen.h).
     q [total_q, Hq, D] bf16 / fp16, dense or a view `paged_varlen_q_addressable` accepts (read in place); cu_seqlens_q int32 [B + 1] and
     seqused_k int32 [B] on the device; the pools, the table and the scales as fp8_attention_paged_splitkv.  num_splits 0: the auto rule on
@@ -1713,7 +1742,7 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
     _require(0 <= int(num_splits) <= SPLITKV_MAX_SPLITS, f"num_splits must be 0 (auto) or 1 .. {SPLITKV_MAX_SPLITS}, got {num_splits}")
     mask_args = (int(bool(is_causal)),) if window is None else _window_args(window)
     total_q, Hq, D = q.shape
-    mask_args += _sink_args(sinks, window, Hq, q.device)
+    mask_args += _sink_args(sinks, window, Hq, q.device) + _softcap_args(softcap, window, sinks, tree_mask)
     tree_window = tree_mask is not None and window is not None
     if tree_mask is not None:
         _require(tree_mask.dtype == torch.int64 and tree_mask.device == q.device and tuple(tree_mask.shape) == (total_q,)
@@ -1760,7 +1789,8 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
             live = lambda t: _ptr(t) if t is not None and t.numel() else None
             dense = (Hq * D, D)     # (a dimension of size 1 has no stride of its own)
             s2 = (ctypes.c_longlong * 2)(*[q.stride(i) if q.shape[i] > 1 else dense[i] for i in (0, 1)])
-            fwd = (L.qattn_fp8_attention_paged_varlen_tree_window_forward if tree_window
+            fwd = (L.qattn_fp8_attention_paged_varlen_softcap_forward if softcap is not None
+                   else L.qattn_fp8_attention_paged_varlen_tree_window_forward if tree_window
                    else L.qattn_fp8_attention_paged_varlen_tree_forward if tree_mask is not None
                    else L.qattn_fp8_attention_paged_varlen_forward if window is None else L.qattn_fp8_attention_paged_varlen_window_forward
                    if sinks is None else L.qattn_fp8_attention_paged_varlen_sink_forward)
@@ -1769,7 +1799,8 @@ def fp8_attention_paged_varlen(q: torch.Tensor, k_pool: torch.Tensor, v_pool: to
                 max_pages, scale_k.data_ptr(), scale_v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(), seqused_k.data_ptr(), B, Hq,
                 Hkv, total_q, max_seqlen_q, Skv, D, fmt_of(fp8_dtype), _numerics(numerics), *mask_args, float(sm_scale),
                 _precision(precision), ns, live(q8), _ptr(sq), live(path), live(po), live(plse), live(ppath), ws.data_ptr(), ws_bytes, _stream(q))
-    _check(rc, "qattn_fp8_attention_paged_varlen_tree_window_forward" if tree_window
+    _check(rc, "qattn_fp8_attention_paged_varlen_softcap_forward" if softcap is not None
+           else "qattn_fp8_attention_paged_varlen_tree_window_forward" if tree_window
            else "qattn_fp8_attention_paged_varlen_tree_forward" if tree_mask is not None
            else "qattn_fp8_attention_paged_varlen_forward" if window is None else "qattn_fp8_attention_paged_varlen_window_forward"
            if sinks is None else "qattn_fp8_attention_paged_varlen_sink_forward")

@@ -25,7 +25,8 @@ SOURCES = ["qattn_quant.hip", "qattn_attn_v2.hip", "qattn_attn_v4.hip", "qattn_a
            "qattn_splitkv_window_fp8.hip", "qattn_paged_splitkv_window_fp8.hip", "qattn_paged_varlen_splitkv_window_fp8.hip", "qattn_paged_varlen_append.hip", "qattn_paged_varlen_rope_append.hip",
            "qattn_merge_sink.hip", "qattn_splitkv_sink_fp8.hip", "qattn_paged_splitkv_sink_fp8.hip", "qattn_paged_varlen_splitkv_sink_fp8.hip",
            "qattn_paged_varlen_splitkv_tree_fp8.hip", "qattn_paged_compact.hip",
-           "qattn_paged_varlen_splitkv_tree_window_fp8.hip", "qattn_paged_varlen_splitkv_tree_sink_fp8.hip", "qattn_paged_varlen_rope_pos_append.hip"]
+           "qattn_paged_varlen_splitkv_tree_window_fp8.hip", "qattn_paged_varlen_splitkv_tree_sink_fp8.hip", "qattn_paged_varlen_rope_pos_append.hip",
+           "qattn_splitkv_softcap_fp8.hip", "qattn_paged_splitkv_softcap_fp8.hip", "qattn_paged_varlen_splitkv_softcap_fp8.hip"]
 # (source, extra flags, object name): the two big kernel files are compiled once per operand format / head dimension so that
 # the build runs in parallel (the longest single translation unit sets the wall time)
 # (a unit with a define is compiled through a two-line wrapper file named after the unit, so that -save-temps leaves one .s
@@ -84,6 +85,10 @@ UNITS = [
     ("qattn_paged_varlen_splitkv_tree_sink_fp8.hip", [], "qattn_paged_varlen_splitkv_tree_sink_fp8"),
     # the rotating packed append and q's packed rotation at the caller's positions: a tree node sits at base + depth (include/qattn_paged_varlen_rope_pos.h)
     ("qattn_paged_varlen_rope_pos_append.hip", [], "qattn_paged_varlen_rope_pos_append"),
+    # logit soft-capping (include/qattn_softcap.h): the three window sweeps with y = softcap tanh(x / softcap) between the scores and the mask
+    ("qattn_splitkv_softcap_fp8.hip", [], "qattn_splitkv_softcap_fp8"),
+    ("qattn_paged_splitkv_softcap_fp8.hip", [], "qattn_paged_splitkv_softcap_fp8"),
+    ("qattn_paged_varlen_splitkv_softcap_fp8.hip", [], "qattn_paged_varlen_splitkv_softcap_fp8"),
 ]
 # (Until round 5 `--dev` built a second library with -DQATTN_DEV: timing-only ablation instantiations, per-segment cycle stamps, work logs and
 # QATTN_* environment switches.  Round 6 took that scaffolding out of the sources -- identical product ISA, profiles/r06/isa_identity_*.log;
@@ -128,7 +133,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = False, 
     os.makedirs(build_dir, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("qattn.h", "qattn_measure.h", "qattn_varlen.h", "qattn_block_sparse.h", "qattn_smooth.h", "qattn_window.h", "qattn_merge.h", "qattn_rope.h", "qattn_splitkv.h", "qattn_kvcache.h", "qattn_paged.h", "qattn_paged_varlen.h", "qattn_splitkv_window.h", "qattn_paged_varlen_append.h", "qattn_paged_varlen_rope.h", "qattn_sinks.h", "qattn_paged_varlen_tree.h", "qattn_paged_varlen_tree_window.h", "qattn_paged_varlen_rope_pos.h")]
+    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("qattn.h", "qattn_measure.h", "qattn_varlen.h", "qattn_block_sparse.h", "qattn_smooth.h", "qattn_window.h", "qattn_merge.h", "qattn_rope.h", "qattn_splitkv.h", "qattn_kvcache.h", "qattn_paged.h", "qattn_paged_varlen.h", "qattn_splitkv_window.h", "qattn_paged_varlen_append.h", "qattn_paged_varlen_rope.h", "qattn_sinks.h", "qattn_paged_varlen_tree.h", "qattn_paged_varlen_tree_window.h", "qattn_paged_varlen_rope_pos.h", "qattn_softcap.h")]
     objs, jobs = [], []
     for src, defines, name in UNITS:
         s = os.path.join(CSRC, src)

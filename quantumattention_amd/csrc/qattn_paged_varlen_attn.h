@@ -49,15 +49,18 @@ inline int pvq_most_splits(int Skv, int num_splits) {
 // device; the call is causal whatever is_causal says.
 // TREE with WINDOW, and with SINK (include/qattn_paged_varlen_tree_window.h): the tree over the window kernel, for windows (left, 0) with
 // left = -1 or left >= 63; the split plan, the num_splits = 0 rule and the merge chain are the window / sink entry's.
-template <bool WINDOW, bool SINK = false, bool TREE = false>
+// SOFTCAP (with WINDOW, without SINK and TREE; include/qattn_softcap.h): the soft-cap kernel under the host float `softcap`, as skv_forward.
+template <bool WINDOW, bool SINK = false, bool TREE = false, bool SOFTCAP = false>
 int pvq_forward(const void* q16, const long long* q_strides2, int in_fmt, const void* k_pool, const void* v_pool, const int* block_table,
                 long long table_stride, int num_pages, int page_size, int max_pages, const float* scale_k, const float* scale_v, void* out,
                 float* lse, const int* cu_seqlens_q, const int* seqused_k, int B, int Hq, int Hkv, int total_q, int max_seqlen_q, int Skv, int D,
                 int fp8_fmt, int numerics, int is_causal, int window_left, int window_right, float sm_scale, int precision, int num_splits,
                 void* q8, float* scale_q, unsigned char* row_path, float* partial_o, float* partial_lse, unsigned char* partial_path,
                 void* workspace, size_t workspace_bytes, void* stream, const float* sinks = nullptr,
-                const unsigned long long* tree_mask = nullptr) {
+                const unsigned long long* tree_mask = nullptr, float softcap = 0.0f) {
     static_assert(WINDOW || !SINK, "the sink kernel is a window kernel");
+    static_assert(!SOFTCAP || (WINDOW && !SINK && !TREE), "the soft-cap kernel is the window kernel without a sink or a tree");
+    if (SOFTCAP && !skv_softcap_ok(softcap)) return QATTN_ERR_INVALID_ARG;
     if (TREE && (!tree_mask || (size_t)tree_mask % 8 != 0)) return QATTN_ERR_INVALID_ARG;
     // a tree under a window (include/qattn_paged_varlen_tree_window.h): causal, and a window that holds every ancestor of a draft token
     if (TREE && WINDOW && (window_right != 0 || (window_left != -1 && window_left < 63))) return QATTN_ERR_INVALID_ARG;
@@ -148,10 +151,10 @@ int pvq_forward(const void* q16, const long long* q_strides2, int in_fmt, const 
     // bound takes total_q for a sequence's query count: cu_seqlens_q is not read on the host, and no sequence holds more (the extents are
     // clamped), whatever max_seqlen_q says
     const int max_keys = skv_max_keys(Skv, total_q, WINDOW ? window_left : -1, ns);
-    const bool want_lse = SINK || lse != nullptr || ns > 1;
-    rc = launch_skv<(TREE ? kSkvTree : 0) + (SINK ? kSkvSink : 0) + (WINDOW ? kSkvWindow : 0) + kSkvPagedVarq>(
+    const bool want_lse = SINK || SOFTCAP || lse != nullptr || ns > 1;
+    rc = launch_skv<(SOFTCAP ? kSkvSoftcap : 0) + (TREE ? kSkvTree : 0) + (SINK ? kSkvSink : 0) + (WINDOW ? kSkvWindow : 0) + kSkvPagedVarq>(
         a, pg, vq, SkvWindow{window_left, window_right}, (unsigned)((long long)Hkv * nt * ns), max_keys, D, fp8_fmt, precision, want_lse, st,
-        SkvSink{sinks}, SkvTree{tree_mask});
+        SkvSink{sinks}, SkvTree{tree_mask}, SOFTCAP ? skv_softcap_arg(softcap, a.sm_log2e) : SkvSoftcap{});
     if (rc != QATTN_OK) return rc;
     if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
     if (ns == 1) return QATTN_OK;

@@ -14,6 +14,9 @@
 // its own (SkvSink).
 // A tenth puts a draft tree over the packed paged kernel's causal rule (QATTN_SKV_TREE; include/qattn_paged_varlen_tree.h): the kernel of
 // qattn_paged_varlen_splitkv_tree_fp8.hip, its mask words an argument of their own (SkvTree).
+// And three more cap the window kernels' scaled scores, y = softcap tanh(x / softcap) (QATTN_SKV_SOFTCAP; include/qattn_softcap.h): the kernels
+// of qattn_splitkv_softcap_fp8.hip, qattn_paged_splitkv_softcap_fp8.hip and qattn_paged_varlen_splitkv_softcap_fp8.hip, the cap's two
+// factors an argument of their own (SkvSoftcap).
 #pragma once
 #include <limits.h>
 
@@ -21,6 +24,7 @@
 #include "qattn_varlen_tile.h"
 #include "../../include/qattn_merge.h"
 #include "../../include/qattn_sinks.h"
+#include "../../include/qattn_softcap.h"
 #include "../../include/qattn_splitkv.h"
 
 namespace qattn {
@@ -75,6 +79,13 @@ struct SkvSink {
 // device; bit i of token (b, p)'s word lets position p attend draft token i of its slot.  A kernel argument of its own, as the window.
 struct SkvTree {
     const unsigned long long* mask;
+};
+
+// SOFTCAP: logit soft-capping (include/qattn_softcap.h), y = softcap tanh(x / softcap) on the scaled scores x.  Two host floats, a kernel
+// argument of their own as the window: c = softcap log2e (the sweep's scores -> log2 units factor, the sweep seeing tanh(x / softcap)) and
+// kin2 = 2 log2e sm_scale / softcap (times the row's scale_q scale_k: raw score -> the exponent of the tanh formula).
+struct SkvSoftcap {
+    float c, kin2;
 };
 
 // Physical chunk of chunk `ch` of kv head hkv of the page a RAW table entry names. The clamp is what keeps every address inside the
@@ -148,7 +159,9 @@ void attn_splitkv_fp8_kernel(const SkvAttn a, const int two, const int sel) {
 #define QATTN_SKV_WINDOW 0
 #define QATTN_SKV_SINK 0
 #define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -164,7 +177,9 @@ void attn_paged_splitkv_fp8_kernel(const SkvAttn a, const SkvPages pg, const int
 #define QATTN_SKV_WINDOW 0
 #define QATTN_SKV_SINK 0
 #define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -180,7 +195,9 @@ void attn_paged_varlen_splitkv_fp8_kernel(const SkvAttn a, const SkvPages pg, co
 #define QATTN_SKV_WINDOW 0
 #define QATTN_SKV_SINK 0
 #define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -197,7 +214,9 @@ void attn_splitkv_window_fp8_kernel(const SkvAttn a, const SkvWindow wn, const i
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 0
 #define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -213,7 +232,9 @@ void attn_paged_splitkv_window_fp8_kernel(const SkvAttn a, const SkvPages pg, co
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 0
 #define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -230,7 +251,9 @@ void attn_paged_varlen_splitkv_window_fp8_kernel(const SkvAttn a, const SkvPages
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 0
 #define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -248,7 +271,9 @@ void attn_splitkv_window_sink_fp8_kernel(const SkvAttn a, const SkvWindow wn, co
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 1
 #define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -265,7 +290,9 @@ void attn_paged_splitkv_window_sink_fp8_kernel(const SkvAttn a, const SkvPages p
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 1
 #define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -282,7 +309,9 @@ void attn_paged_varlen_splitkv_window_sink_fp8_kernel(const SkvAttn a, const Skv
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 1
 #define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -300,7 +329,9 @@ void attn_paged_varlen_splitkv_tree_fp8_kernel(const SkvAttn a, const SkvPages p
 #define QATTN_SKV_WINDOW 0
 #define QATTN_SKV_SINK 0
 #define QATTN_SKV_TREE 1
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -320,7 +351,9 @@ void attn_paged_varlen_splitkv_tree_window_fp8_kernel(const SkvAttn a, const Skv
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 0
 #define QATTN_SKV_TREE 1
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -337,7 +370,9 @@ void attn_paged_varlen_splitkv_tree_window_sink_fp8_kernel(const SkvAttn a, cons
 #define QATTN_SKV_WINDOW 1
 #define QATTN_SKV_SINK 1
 #define QATTN_SKV_TREE 1
+#define QATTN_SKV_SOFTCAP 0
 #include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
 #undef QATTN_SKV_TREE
 #undef QATTN_SKV_SINK
 #undef QATTN_SKV_WINDOW
@@ -345,15 +380,85 @@ void attn_paged_varlen_splitkv_tree_window_sink_fp8_kernel(const SkvAttn a, cons
 #undef QATTN_SKV_PAGED
 }
 
-// which of the twelve kernels a launch runs (kSkvWindow + one of the first three: that kernel under a window; + kSkvSink: with a sink;
-// kSkvTree + kSkvPagedVarq: the packed paged kernel under a draft tree; + kSkvWindow: the tree over its window kernel; + kSkvSink: with a sink)
-constexpr int kSkvContig = 0, kSkvPaged = 1, kSkvPagedVarq = 2, kSkvWindow = 4, kSkvSink = 8, kSkvTree = 16;
+// ... and the three window kernels with the scaled scores soft-capped under `sc` (QATTN_SKV_SOFTCAP; include/qattn_softcap.h).  As with
+// the sink kernels only the exact instances (BYTE = false) are ever launched: the byte-exponential formula is fitted to raw scores.
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_splitkv_window_softcap_fp8_kernel(const SkvAttn a, const SkvWindow wn, const SkvSoftcap sc, const int two, const int sel) {
+#define QATTN_SKV_PAGED 0
+#define QATTN_SKV_VARQ 0
+#define QATTN_SKV_WINDOW 1
+#define QATTN_SKV_SINK 0
+#define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
+#undef QATTN_SKV_TREE
+#undef QATTN_SKV_SINK
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_paged_splitkv_window_softcap_fp8_kernel(const SkvAttn a, const SkvPages pg, const SkvWindow wn, const SkvSoftcap sc, const int two,
+                                                  const int sel) {
+#define QATTN_SKV_PAGED 1
+#define QATTN_SKV_VARQ 0
+#define QATTN_SKV_WINDOW 1
+#define QATTN_SKV_SINK 0
+#define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
+#undef QATTN_SKV_TREE
+#undef QATTN_SKV_SINK
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+template <int D, int FMT, bool BYTE>
+__global__ __launch_bounds__(kFpvWaves * 64, (FpvShape<D, BYTE>::WPS))
+void attn_paged_varlen_splitkv_window_softcap_fp8_kernel(const SkvAttn a, const SkvPages pg, const SkvVarq vq, const SkvWindow wn,
+                                                         const SkvSoftcap sc, const int two, const int sel) {
+#define QATTN_SKV_PAGED 1
+#define QATTN_SKV_VARQ 1
+#define QATTN_SKV_WINDOW 1
+#define QATTN_SKV_SINK 0
+#define QATTN_SKV_TREE 0
+#define QATTN_SKV_SOFTCAP 1
+#include "qattn_splitkv_body.h"
+#undef QATTN_SKV_SOFTCAP
+#undef QATTN_SKV_TREE
+#undef QATTN_SKV_SINK
+#undef QATTN_SKV_WINDOW
+#undef QATTN_SKV_VARQ
+#undef QATTN_SKV_PAGED
+}
+
+// which of the fifteen kernels a launch runs (kSkvWindow + one of the first three: that kernel under a window; + kSkvSink: with a sink;
+// kSkvTree + kSkvPagedVarq: the packed paged kernel under a draft tree; + kSkvWindow: the tree over its window kernel; + kSkvSink: with a sink;
+// kSkvSoftcap + kSkvWindow + one of the first three: that window kernel with soft-capped scores)
+constexpr int kSkvContig = 0, kSkvPaged = 1, kSkvPagedVarq = 2, kSkvWindow = 4, kSkvSink = 8, kSkvTree = 16, kSkvSoftcap = 32;
 
 template <int D, int FMT, int MODE>
 static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys,
-                          int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}, const SkvTree& tr = SkvTree{}) {
+                          int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}, const SkvTree& tr = SkvTree{},
+                          const SkvSoftcap& sc = SkvSoftcap{}) {
     return fpv_precision_ladder(precision, max_keys, a.two_term_keys, want_lse, [&](auto byte, int two, int sel) {
-        if constexpr (MODE == kSkvTree + kSkvSink + kSkvWindow + kSkvPagedVarq) {
+        if constexpr ((MODE & kSkvSoftcap) != 0) {
+            // (the byte-exponential instances are not compiled for the soft-cap kernels: their callers pass want_lse = true)
+            static_assert((MODE & (kSkvSink | kSkvTree)) == 0 && (MODE & kSkvWindow) != 0, "soft-capping sits on the plain window kernels");
+            if constexpr (decltype(byte)::value) return (int)QATTN_ERR_LAUNCH;
+            else if constexpr (MODE == kSkvSoftcap + kSkvWindow + kSkvPagedVarq)
+                return fpv_launch(attn_paged_varlen_splitkv_window_softcap_fp8_kernel<D, FMT, false>, grid, fpv_lds_bytes(D), st, a, pg, vq, wn, sc,
+                                  two, sel);
+            else if constexpr (MODE == kSkvSoftcap + kSkvWindow + kSkvPaged)
+                return fpv_launch(attn_paged_splitkv_window_softcap_fp8_kernel<D, FMT, false>, grid, fpv_lds_bytes(D), st, a, pg, wn, sc, two, sel);
+            else return fpv_launch(attn_splitkv_window_softcap_fp8_kernel<D, FMT, false>, grid, fpv_lds_bytes(D), st, a, wn, sc, two, sel);
+        } else if constexpr (MODE == kSkvTree + kSkvSink + kSkvWindow + kSkvPagedVarq) {
             if constexpr (decltype(byte)::value) return (int)QATTN_ERR_LAUNCH;   // (as the sink kernels below: want_lse = true)
             else
                 return fpv_launch(attn_paged_varlen_splitkv_tree_window_sink_fp8_kernel<D, FMT, false>, grid, fpv_lds_bytes(D), st, a, pg, vq, wn,
@@ -390,19 +495,26 @@ static int launch_skv_fmt(const SkvAttn& a, const SkvPages& pg, const SkvVarq& v
 
 template <int D, int MODE>
 static int launch_skv_d(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys, int fp8_fmt,
-                        int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}, const SkvTree& tr = SkvTree{}) {
-    return fp8_fmt == QATTN_FMT_E4M3 ? launch_skv_fmt<D, QATTN_FMT_E4M3, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st, sn, tr)
-                                     : launch_skv_fmt<D, QATTN_FMT_E5M2, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st, sn, tr);
+                        int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}, const SkvTree& tr = SkvTree{},
+                        const SkvSoftcap& sc = SkvSoftcap{}) {
+    return fp8_fmt == QATTN_FMT_E4M3 ? launch_skv_fmt<D, QATTN_FMT_E4M3, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st, sn, tr, sc)
+                                     : launch_skv_fmt<D, QATTN_FMT_E5M2, MODE>(a, pg, vq, wn, grid, max_keys, precision, want_lse, st, sn, tr, sc);
 }
 
 // every head dimension of one entry
 template <int MODE>
 static int launch_skv(const SkvAttn& a, const SkvPages& pg, const SkvVarq& vq, const SkvWindow& wn, unsigned grid, int max_keys, int D,
-                      int fp8_fmt, int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}, const SkvTree& tr = SkvTree{}) {
-    if (D == 64) return launch_skv_d<64, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn, tr);
-    if (D == 128) return launch_skv_d<128, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn, tr);
-    return launch_skv_d<256, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn, tr);
+                      int fp8_fmt, int precision, bool want_lse, hipStream_t st, const SkvSink& sn = SkvSink{}, const SkvTree& tr = SkvTree{},
+                      const SkvSoftcap& sc = SkvSoftcap{}) {
+    if (D == 64) return launch_skv_d<64, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn, tr, sc);
+    if (D == 128) return launch_skv_d<128, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn, tr, sc);
+    return launch_skv_d<256, MODE>(a, pg, vq, wn, grid, max_keys, fp8_fmt, precision, want_lse, st, sn, tr, sc);
 }
+
+// Host side of a soft cap (include/qattn_softcap.h): finite and > 0 ...
+inline bool skv_softcap_ok(float softcap) { return softcap > 0.0f && softcap <= 3.402823466e38f; }
+// ... and the kernel's two factors from it and the call's sm_scale log2e (a.sm_log2e)
+inline SkvSoftcap skv_softcap_arg(float softcap, float sm_log2e) { return SkvSoftcap{softcap * 1.4426950408889634f, 2.0f * sm_log2e / softcap}; }
 
 // Host side of a window (include/qattn_splitkv_window.h).  Under left >= 0 a sequence's interval [lo_i, L) holds at most left + Sq keys,
 // which touch at most ceil((left + Sq) / 128) + 1 key blocks.
@@ -503,13 +615,18 @@ inline int skv_merge_chain(const float* po, const float* plse, int ns, long rows
 // WINDOW: the window kernels under (window_left, window_right) in is_causal's place -- also for (-1, 0) and (-1, -1).
 // SINK (with WINDOW; include/qattn_sinks.h): the sink kernels with `sinks` fp32 [Hq] on the device -- folded into the sweep's epilogue with
 // one split, into the last launch of the merge chain with more.  Under FAST they take the exact one-term sweep, never the byte one.
-template <bool PAGED, bool WINDOW = false, bool SINK = false>
+// SOFTCAP (with WINDOW, without SINK; include/qattn_softcap.h): the soft-cap kernels under the host float `softcap`, finite and > 0 -- a
+// kernel argument, so a captured graph keeps the value it was captured with.  The partials are ordinary states over the capped scores: the
+// merge chain is the window entry's.  Under FAST the exact one-term sweep, as SINK.
+template <bool PAGED, bool WINDOW = false, bool SINK = false, bool SOFTCAP = false>
 int skv_forward(const void* q16, int in_fmt, const void* k8, const void* v8, const SkvPages& pg, const float* scale_k, const float* scale_v,
                 void* out, float* lse, const int* seqused_k, int B, int Hq, int Hkv, int Sq, int Skv, int D, int fp8_fmt, int numerics,
                 int is_causal, float sm_scale, int precision, int num_splits, void* q8, float* scale_q, unsigned char* row_path,
                 float* partial_o, float* partial_lse, unsigned char* partial_path, void* workspace, size_t workspace_bytes, void* stream,
-                int window_left = -1, int window_right = -1, const float* sinks = nullptr) {
+                int window_left = -1, int window_right = -1, const float* sinks = nullptr, float softcap = 0.0f) {
     static_assert(WINDOW || !SINK, "the sink kernels are window kernels");
+    static_assert(!SOFTCAP || (WINDOW && !SINK), "the soft-cap kernels are window kernels without a sink");
+    if (SOFTCAP && !skv_softcap_ok(softcap)) return QATTN_ERR_INVALID_ARG;
     if (WINDOW && (window_left < -1 || window_right < -1)) return QATTN_ERR_INVALID_ARG;
     if (SINK && (!sinks || (size_t)sinks % 4 != 0)) return QATTN_ERR_INVALID_ARG;
     if (!q16 || !k8 || !v8 || !scale_k || !scale_v || !out) return QATTN_ERR_INVALID_ARG;
@@ -574,10 +691,11 @@ int skv_forward(const void* q16, int in_fmt, const void* k8, const void* v8, con
     a.sm_log2e = (sm_scale > 0.0f ? sm_scale : 1.0f / sqrtf((float)D)) * 1.4426950408889634f;
     // the most keys a split can own; the sweep asks for the LSE whenever it feeds the merge
     const int max_keys = skv_max_keys(Skv, Sq, WINDOW ? window_left : -1, ns);
-    const bool want_lse = SINK || lse != nullptr || ns > 1;
+    const bool want_lse = SINK || SOFTCAP || lse != nullptr || ns > 1;
     const unsigned grid = (unsigned)((long long)B * Hkv * ntile * ns);
-    rc = launch_skv<(SINK ? kSkvSink : 0) + (WINDOW ? kSkvWindow : 0) + (PAGED ? kSkvPaged : kSkvContig)>(
-        a, pg, SkvVarq{}, SkvWindow{window_left, window_right}, grid, max_keys, D, fp8_fmt, precision, want_lse, st, SkvSink{sinks});
+    rc = launch_skv<(SOFTCAP ? kSkvSoftcap : 0) + (SINK ? kSkvSink : 0) + (WINDOW ? kSkvWindow : 0) + (PAGED ? kSkvPaged : kSkvContig)>(
+        a, pg, SkvVarq{}, SkvWindow{window_left, window_right}, grid, max_keys, D, fp8_fmt, precision, want_lse, st, SkvSink{sinks}, SkvTree{},
+        SOFTCAP ? skv_softcap_arg(softcap, a.sm_log2e) : SkvSoftcap{});
     if (rc != QATTN_OK) return rc;
     if (hipGetLastError() != hipSuccess) return QATTN_ERR_LAUNCH;
     if (ns == 1) return QATTN_OK;

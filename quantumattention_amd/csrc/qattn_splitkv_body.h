@@ -38,8 +38,15 @@
 // cuts a draft key, so one comparison serves committed and draft keys alike.  A sequence with more than 64 queries reads no word and is
 // the window text (depth = position).  Both switches off the combination: the text above, token for token
 // (profiles/tree_window/code_objects_vs_parent.log).
+// QATTN_SKV_SOFTCAP (with QATTN_SKV_WINDOW, without QATTN_SKV_SINK and QATTN_SKV_TREE; include/qattn_softcap.h) caps the scaled scores:
+// y = softcap tanh(x / softcap).  0: the text above, token for token (profiles/softcap/code_objects_vs_parent.log); 1, every
+// raw score s of a chunk is replaced by t = tanh(s kin) in [-1, 1] between sw.qk and the token mask -- on every chunk, before the mask, so
+// that a masked key is -inf and never exp(-softcap) -- with the row's kin = sm_scale scale_q scale_k / softcap, and the sweep is handed
+// c = softcap log2e in sm_log2e scale_q scale_k's place: m_run, the rescale limit, the two-term split and the LSE epilogue work on t as
+// they work on raw scores.  tanh is 1 - 2 / (1 + 2^(2 log2e u)): one v_exp_f32 and one v_rcp_f32 per score, +-1 at large |u| without a
+// NaN, NaN for a NaN score.  sc.kin2 carries 2 log2e sm_scale / softcap, so the exponent is one multiply away from the raw score.
 // In scope: template parameters D, FMT, BYTE; arguments a (SkvAttn), two, sel, -- paged -- pg (SkvPages), -- packed queries -- vq,
-// -- window -- wn, -- sink -- sn (SkvSink) and -- tree -- tr (SkvTree).
+// -- window -- wn, -- sink -- sn (SkvSink), -- tree -- tr (SkvTree) and -- soft cap -- sc (SkvSoftcap).
 #if QATTN_SKV_VARQ
 #define SKV_SQ Sq_i
 #define SKV_ROWS rows_i
@@ -225,7 +232,14 @@
 #endif
     sw.park_q(a.q8 + (rvalid ? SKV_QROW : SKV_QROW0) * D + hh * 32, rvalid);
     constexpr float kNoKeyYet = -1.0e20f;   // (attn_vfp8_window_kernel's header comment)
+#if QATTN_SKV_SOFTCAP
+    // the sweep sees t = tanh(x / softcap): its scores -> log2 units factor is softcap log2e, and this row's raw score -> exponent of the
+    // tanh factor is kin2 (the row's own head's scale_q: the tile may hold several heads)
+    sw.init_state(sc.c, kNoKeyYet);
+    const float kin2 = sc.kin2 * a.sq[(long)kvh * a.G + g] * a.sk[kvh];
+#else
     sw.init_state(a.sm_log2e * a.sq[(long)kvh * a.G + g] * a.sk[kvh], kNoKeyYet);
+#endif
     const int one = fpv_ones_word(lane);
 #if QATTN_SKV_WINDOW
     // the first and the last key this lane's row attends (a padding row: position >= Sq, masked as attn_vfp8_window_kernel masks it), and
@@ -291,6 +305,27 @@
         v16f s0, s1;
         v8i vf0, vf1;
         sw.qk(t, qf, s0, s1, vf0, vf1);
+#if QATTN_SKV_SOFTCAP
+        // ---- the cap, on all 32 scores of every chunk and BEFORE the mask: s -> tanh(s kin) = 1 - 2 / (1 + 2^(s kin2)).  Eight scores at a
+        // time: the empty asm hands the eight results and kq on, so that the next eight start after these -- eight independent chains keep
+        // the transcendental pipe full, and all 32 in flight at once cost the D = 256 kernels more registers than they have.
+        float kq = kin2;
+#pragma unroll
+        for (int e = 0; e < 16; e += 4) {
+            float x[8];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                x[u] = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(s0[e + u] * kq)), 1.0f);
+                x[4 + u] = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(s1[e + u] * kq)), 1.0f);
+            }
+            asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(kq));
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                s0[e + u] = x[u];
+                s1[e + u] = x[4 + u];
+            }
+        }
+#endif
 #if QATTN_SKV_WINDOW && QATTN_SKV_TREE
         // ---- the ragged tail at L, the window's two edges and the draft tree by token, under a workgroup-uniform condition
         if (__builtin_expect(k0 + 64 > L || k0 + 63 > edge || k0 < edge_lo || k0 + 63 >= tree_lo, 0)) {

@@ -1230,3 +1230,127 @@ def rope_packed_positions(
 @_register_fake("quantumattention_amd::rope_packed_positions")
 def _(x, positions, cos, sin, interleaved=False):
     return x.new_empty(x.shape)
+
+
+# ---- logit soft-capping (include/qattn_softcap.h): the three window ops with the host float `softcap` after window_right --
+# y = softcap tanh(x / softcap) on the scaled scores, before the mask.  A model constant: it is baked into a traced or captured graph.
+
+@_custom_op("quantumattention_amd::fp8_splitkv_softcap_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_splitkv_softcap_attention_forward(
+    query: torch.Tensor,
+    k_frag: torch.Tensor,
+    v_frag: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    seqused_k: Optional[torch.Tensor],
+    seqlen_k: int,
+    num_splits: int,
+    window_left: int,
+    window_right: int,
+    softcap: float,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    precision: str = "accurate",
+    return_lse: bool = False,
+    return_partials: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp8_splitkv_window_attention_forward with soft-capped scores (include/qattn_softcap.h).  Reference implementation:
+    splitkv._splitkv_eager with softcap=.  Arguments are validated by softcap.fp8_attn_splitkv_softcap_func."""
+    res = _native.fp8_attention_splitkv(
+        query, k_frag, v_frag, scale_k, scale_v, Skv=seqlen_k, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics,
+        sm_scale=0.0 if scale is None else float(scale), precision=precision, num_splits=num_splits, seqused_k=seqused_k,
+        return_lse=return_lse, return_partials=return_partials, window=(window_left, window_right), softcap=softcap)
+    return _skv_pack(res, query, return_lse, return_partials)
+
+
+@_register_fake("quantumattention_amd::fp8_splitkv_softcap_attention_forward")
+def _(query, k_frag, v_frag, scale_k, scale_v, seqused_k, seqlen_k, num_splits, window_left, window_right, softcap, fp8_format="e4m3",
+      numerics="compiled", precision="accurate", return_lse=False, return_partials=False, *, scale=None):
+    B, Hq, Sq, _ = query.shape
+    return _skv_fake(query, (B, Hq, Sq), (B, Hq, Sq), num_splits, return_lse, return_partials)
+
+
+@_custom_op("quantumattention_amd::fp8_paged_splitkv_softcap_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_paged_splitkv_softcap_attention_forward(
+    query: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    seqlen_k: int,
+    num_pages: int,
+    page_size: int,
+    num_splits: int,
+    window_left: int,
+    window_right: int,
+    softcap: float,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    precision: str = "accurate",
+    return_lse: bool = False,
+    return_partials: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp8_paged_splitkv_window_attention_forward with soft-capped scores (include/qattn_softcap.h).  Reference implementation:
+    paged._attend_eager with softcap=.  Arguments are validated by softcap.fp8_attn_paged_softcap_func."""
+    res = _native.fp8_attention_paged_splitkv(
+        query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, Skv=seqlen_k, num_pages=num_pages, page_size=page_size,
+        fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics, sm_scale=0.0 if scale is None else float(scale), precision=precision,
+        num_splits=num_splits, return_lse=return_lse, return_partials=return_partials, window=(window_left, window_right), softcap=softcap)
+    return _skv_pack(res, query, return_lse, return_partials)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_splitkv_softcap_attention_forward")
+def _(query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, seqlen_k, num_pages, page_size, num_splits, window_left, window_right,
+      softcap, fp8_format="e4m3", numerics="compiled", precision="accurate", return_lse=False, return_partials=False, *, scale=None):
+    B, Hq, Sq, _ = query.shape
+    return _skv_fake(query, (B, Hq, Sq), (B, Hq, Sq), num_splits, return_lse, return_partials)
+
+
+@_custom_op("quantumattention_amd::fp8_paged_varlen_splitkv_softcap_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_paged_varlen_splitkv_softcap_attention_forward(
+    query: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    scale_v: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    max_seqlen_q: int,
+    seqlen_k: int,
+    num_pages: int,
+    page_size: int,
+    num_splits: int,
+    window_left: int,
+    window_right: int,
+    softcap: float,
+    fp8_format: str = "e4m3",
+    numerics: str = "compiled",
+    precision: str = "accurate",
+    return_lse: bool = False,
+    return_partials: bool = False,
+    *,
+    scale: Optional[float] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp8_paged_varlen_splitkv_window_attention_forward with soft-capped scores (include/qattn_softcap.h).  Reference implementation:
+    paged_varlen._attend_varlen_eager with softcap=.  Arguments are validated by softcap.fp8_attn_paged_varlen_softcap_func."""
+    res = _native.fp8_attention_paged_varlen(
+        query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, cu_seqlens_q, max_seqlen_q=max_seqlen_q, Skv=seqlen_k,
+        num_pages=num_pages, page_size=page_size, fp8_dtype=_native.fp8_dtype_of(fp8_format), numerics=numerics,
+        sm_scale=0.0 if scale is None else float(scale), precision=precision, num_splits=num_splits, return_lse=return_lse,
+        return_partials=return_partials, window=(window_left, window_right), softcap=softcap)
+    return _skv_pack(res, query, return_lse, return_partials)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_varlen_splitkv_softcap_attention_forward")
+def _(query, k_pool, v_pool, scale_k, scale_v, block_table, seqused_k, cu_seqlens_q, max_seqlen_q, seqlen_k, num_pages, page_size, num_splits,
+      window_left, window_right, softcap, fp8_format="e4m3", numerics="compiled", precision="accurate", return_lse=False, return_partials=False,
+      *, scale=None):
+    total_q, Hq, _ = query.shape
+    return _skv_fake(query, (total_q, Hq), (Hq, total_q), num_splits, return_lse, return_partials)

@@ -264,9 +264,9 @@ def gather_paged_eager(cache: PagedKVCacheFP8, Skv: Optional[int] = None) -> Pre
                       cache.numerics, "rowmajor")
 
 
-def _attend_eager(q, cache, causal, scale, seqused_k, Skv, ns, precision, sinks=None, window=None):
+def _attend_eager(q, cache, causal, scale, seqused_k, Skv, ns, precision, softcap=None, sinks=None, window=None):
     """CPU tensors and config.attention.force_eager_fallback: splitkv._splitkv_eager on the cache gathered through the table."""
-    return _splitkv_eager(q, gather_paged_eager(cache, Skv), causal, scale, seqused_k, ns, precision, sinks=sinks, window=window)
+    return _splitkv_eager(q, gather_paged_eager(cache, Skv), causal, scale, seqused_k, ns, precision, sinks=sinks, softcap=softcap, window=window)
 
 
 def paged_kv_cache_append_fp8(cache: PagedKVCacheFP8, k_new: Tensor, v_new: Tensor, *, new_lens: Optional[Tensor] = None,

@@ -120,7 +120,8 @@ def _resolve_varlen_splits(num_splits: int, B: int, Hq: int, Hkv: int, total_q: 
     return _native.paged_varlen_auto_splits(B, Hq, Hkv, total_q, max_seqlen_q, Skv, D, cus)
 
 
-def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, ns, precision, tree_mask=None, sinks=None, window=None):
+def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, ns, precision, tree_mask=None, softcap=None, sinks=None,
+                         window=None):
     """CPU tensors and config.attention.force_eager_fallback: per sequence slot, splitkv._splitkv_eager on the slot's queries and on its
     keys gathered through the table, scattered into the packed outputs.  Rows of tokens that belong to no sequence: zeros.  (This path
     reads cu_seqlens_q, seqused_k and the table on the host.)
@@ -128,7 +129,8 @@ def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, 
     queries position p keeps key j >= max(delta, 0), delta = L_b - Sq_b, only if bit j - delta of the token's word is set.
     tree_mask with window = (left, 0) (and, optionally, sinks): the definition of include/qattn_paged_varlen_tree_window.h -- in such a
     slot the window's lower edge is taken from the token's DEPTH (the set bits of its word below its own index) and cuts committed keys
-    only; a slot with more than 64 queries is the window rule."""
+    only; a slot with more than 64 queries is the window rule.
+    softcap = a float > 0 (None: none; with window): the scaled scores capped before the mask, as splitkv._splitkv_eager defines it."""
     total_q, Hq, D = q.shape
     B = cache.batch_size
     n = ns if ns > 1 else 0
@@ -161,7 +163,7 @@ def _attend_varlen_eager(q, cache, cu_seqlens_q, causal, scale, seqused_k, Skv, 
             if j1 > j0:
                 also[0, :, j0:j1] = bits[:, j0 - delta:j1 - delta]
         o, l, p_o, p_l, p_p = _splitkv_eager_depth(q[start:end].transpose(0, 1)[None], one, causal, scale, seqused_k[b:b + 1], ns, precision,
-                                                   also, sinks, window, depth)
+                                                   also, sinks, window, depth, softcap=softcap)
         out[start:end] = o[0].transpose(0, 1)
         lse[:, start:end] = l[0]
         if n:

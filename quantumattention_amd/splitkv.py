@@ -190,7 +190,7 @@ def split_plan_window(L: int, Sq: int, window_left: int, num_splits: int):
     return [(min(BLOCK_N * (kb0 + s * per), L), min(BLOCK_N * (kb0 + (s + 1) * per), L)) for s in range(num_splits)]
 
 
-def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, keep_also=None, sinks=None, window=None):
+def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, keep_also=None, softcap=None, sinks=None, window=None):
     """CPU tensors and config.attention.force_eager_fallback: the torch definition.  The eager quantiser on q (head-wise), the prepared
     row-major bytes de-quantised; per split an fp32 softmax partial (o_s, lse_s) over the split's keys of every batch element's first L_b
     keys -- a row without a key there: a zero row, LSE -inf --, then merge.merge_attn_states_eager.  The path bytes restate the kernel's
@@ -201,12 +201,14 @@ def _splitkv_eager(q, kv, causal, scale, seqused_k, ns, precision, keep_also=Non
     sinks = fp32 [Hq] (None: none): the definition of the sink entries (include/qattn_sinks.h) -- one split: the row's LSE becomes
     L = logaddexp(lse, sink_h) and the weights exp(score - L), an empty row a zero row with LSE = sink_h; more splits: the partials stay
     free of the sink and it enters merge.merge_attn_states_eager once.  +inf and NaN make the head's rows NaN.
+    softcap = a float > 0 (None: none): the definition of the soft-cap entries (include/qattn_softcap.h) -- every scaled score x becomes
+    softcap tanh(x / softcap) BEFORE the mask, so a masked key weighs 0; the LSE and the partials are those of the capped scores.
     keep_also = bool [B, Sq, Skv] (None: none): one more condition on (position, key), on top of the rule above -- the draft tree of
     tree.fp8_attn_paged_varlen_tree_func; the splits and the path bytes do not see it."""
-    return _splitkv_eager_depth(q, kv, causal, scale, seqused_k, ns, precision, keep_also, sinks, window, None)
+    return _splitkv_eager_depth(q, kv, causal, scale, seqused_k, ns, precision, keep_also, sinks, window, None, softcap=softcap)
 
 
-def _splitkv_eager_depth(q, kv, causal, scale, seqused_k, ns, precision, keep_also, sinks, window, depth):
+def _splitkv_eager_depth(q, kv, causal, scale, seqused_k, ns, precision, keep_also, sinks, window, depth, softcap=None):
     """`_splitkv_eager`, whose definition this is, with one more input for the tree under a window
     (include/qattn_paged_varlen_tree_window.h).  depth = a list per batch element of None or an int64 [Sq] tensor (None: none anywhere),
     with window: an element with depths is a slot of draft tokens -- position p sits at sequence position L - Sq + depth[p], the window's
@@ -222,6 +224,8 @@ def _splitkv_eager_depth(q, kv, causal, scale, seqused_k, ns, precision, keep_al
     dk = nn._expand_kv_heads(kv.k.float() * kv.scale_k[..., None, None], Hq)
     dv = nn._expand_kv_heads(kv.v.float() * kv.scale_v[..., None, None], Hq)
     s_all = (dq @ dk.transpose(-1, -2)) * sm                                    # [B, Hq, Sq, Skv]
+    if softcap is not None:   # the cap on the scaled scores, before any mask
+        s_all = float(softcap) * torch.tanh(s_all / float(softcap))
     used = [Skv] * B if seqused_k is None else [min(max(int(x), 0), Skv) for x in seqused_k.tolist()]
     pos = torch.arange(Sq, device=q.device)[:, None]
     key = torch.arange(Skv, device=q.device)[None, :]
