@@ -154,6 +154,22 @@
  *              influence no result (NaN patterns included).
  *   block_table  the entries lo_i / page_size .. ceil(L_i / page_size) - 1 of row i at the most, each clamped before it forms an address;
  *              the leading entries may hold anything (their pages may have been handed to another sequence).
+ *
+ * qattn_paged_mla_cache_append_fp8 and qattn_fp8_mla_paged_forward (qattn_mla.h; held by tests/test_gpu_mla.py): the table, lengths and
+ * clamping lines of the paged entries above, with ONE pool and no head axis.
+ *   pool       qattn_mla_pool_bytes(num_pages, page_size) = num_pages (page_size / 64) 36 864 bytes, 16-byte aligned.  The append writes the
+ *              576 bytes of every appended key, as 36 stores of 16 bytes, and no other byte; the attention reads the chunks
+ *              0 .. ceil(L_b / 64) - 1 of slot b at the most; bytes at or behind key L_b are fetched and influence no result.
+ *   scale      fp32 [B], 4-byte aligned, read.
+ *   ckv16, kpe16  [B, T, 512] / [B, T, 64] 16-bit rows through {batch, token} element strides (multiples of 8), bases 16-byte aligned; read:
+ *              the rows of the appended tokens.
+ *   q16        [B, Hq, Sq, 576] through {batch, head, position} element strides (multiples of 8; NULL: dense), 16-byte aligned, read.
+ *   out        dense [B, Hq, Sq, 512] in q16's format, 16-byte aligned, every element written.  lse fp32 [B, Hq, Sq] (may be NULL), every
+ *              element written.
+ *   q8, scale_q  optional: dense e4m3 [B, Hq, Sq, 576], 16-byte aligned, and fp32 [B, Hq, Sq]; every element written (by split 0).
+ *   partial_o, partial_lse  optional: fp32 [ns, B, Hq, Sq, 512] and [ns, B, Hq, Sq]; every element written when ns > 1, none otherwise.
+ *   workspace  qattn_fp8_mla_paged_workspace_bytes(B, Hq, Sq, ns) bytes with the resolved ns, 16-byte aligned; 0 bytes (NULL allowed) for
+ *              one split.  It holds the partials the caller did not provide.
  */
 #ifndef QATTN_BUFFERS_H_
 #define QATTN_BUFFERS_H_

@@ -95,3 +95,13 @@ __all__ = [
     "fp8_token_wise_attn_func",
     "fp8_token_wise_attn_func_with_fallback",
 ]
+
+# multi-head latent attention (DeepSeek-V2 / V3 / R1, Kimi-K2) in its absorbed decode form over a one-image paged FP8 latent cache
+# (include/qattn_mla.h): package attributes, not in __all__
+from .mla import (  # noqa: E402
+    PagedMLACacheFP8,
+    alloc_paged_mla_cache_fp8,
+    fp8_mla_paged_func,
+    mla_input_reason,
+    paged_mla_cache_append_fp8,
+)
