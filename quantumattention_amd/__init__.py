@@ -105,3 +105,10 @@ from .mla import (  # noqa: E402
     mla_input_reason,
     paged_mla_cache_append_fp8,
 )
+# ... and its sparse (top-k indexed) form on a row-major cache (include/qattn_mla_sparse.h): package attributes, not in __all__
+from .mla import (  # noqa: E402
+    alloc_paged_mla_row_cache_fp8,
+    fp8_mla_paged_sparse_func,
+    mla_sparse_input_reason,
+    paged_mla_row_cache_append_fp8,
+)

@@ -68,6 +68,8 @@ EXPORTS = (
     "qattn_fp8_attention_paged_varlen_softcap_forward",
     "qattn_mla_pool_bytes", "qattn_mla_auto_splits", "qattn_fp8_mla_paged_workspace_bytes", "qattn_paged_mla_cache_append_fp8",
     "qattn_fp8_mla_paged_forward",
+    "qattn_mla_row_pool_bytes", "qattn_mla_sparse_auto_splits", "qattn_fp8_mla_paged_sparse_workspace_bytes",
+    "qattn_paged_mla_row_cache_append_fp8", "qattn_fp8_mla_paged_sparse_forward",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -75,6 +77,8 @@ _MERGE_FMT = {torch.bfloat16: FMT_BF16, torch.float16: FMT_FP16, torch.float32: 
 BLOCK_SPARSE_BLOCK = 128   # QATTN_BLOCK_SPARSE_BLOCK (include/qattn_block_sparse.h): rows / keys per mask block
 SPLITKV_MAX_SPLITS = 64    # QATTN_SPLITKV_MAX_SPLITS (include/qattn_splitkv.h)
 MLA_D, MLA_D_LATENT, MLA_D_ROPE, MLA_MAX_SPLITS = 576, 512, 64, 64   # QATTN_MLA_* (include/qattn_mla.h)
+MLA_SPARSE_SPLIT_ENTRIES = 2048                                      # QATTN_MLA_SPARSE_SPLIT_ENTRIES (include/qattn_mla_sparse.h)
+MLA_SPARSE_MAX_TOPK = MLA_SPARSE_SPLIT_ENTRIES * MLA_MAX_SPLITS      # QATTN_MLA_SPARSE_MAX_TOPK
 
 
 class PathDesc(ctypes.Structure):
@@ -355,6 +359,18 @@ def lib() -> ctypes.CDLL:
     L.qattn_paged_mla_cache_append_fp8.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, ll, vp, vp, i, i, i, i, i, i, i, vp]
     L.qattn_fp8_mla_paged_forward.restype = i
     L.qattn_fp8_mla_paged_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, vp, i, i, i, i, i, i, f, i, vp, vp, vp, vp, vp, sz, vp]
+    # sparse multi-head latent attention on the row-major latent cache (include/qattn_mla_sparse.h)
+    L.qattn_mla_row_pool_bytes.restype = sz
+    L.qattn_mla_row_pool_bytes.argtypes = [i, i]
+    L.qattn_mla_sparse_auto_splits.restype = i
+    L.qattn_mla_sparse_auto_splits.argtypes = [i, i, i, i, i]
+    L.qattn_fp8_mla_paged_sparse_workspace_bytes.restype = sz
+    L.qattn_fp8_mla_paged_sparse_workspace_bytes.argtypes = [i, i, i, i]
+    L.qattn_paged_mla_row_cache_append_fp8.restype = i
+    L.qattn_paged_mla_row_cache_append_fp8.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, ll, vp, vp, i, i, i, i, i, i, i, vp]
+    L.qattn_fp8_mla_paged_sparse_forward.restype = i
+    L.qattn_fp8_mla_paged_sparse_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, i, vp, vp, vp, i, i, i, i, i, f, i, vp, vp, vp, vp,
+                                                     vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -1915,4 +1931,97 @@ def fp8_mla_paged_attention(q: torch.Tensor, pool: torch.Tensor, scale: torch.Te
                                            q8.data_ptr() if return_q8 else None, sq.data_ptr() if return_q8 else None,
                                            po.data_ptr() if parts else None, pl.data_ptr() if parts else None, _ptr(ws), wsb, _stream(q))
     _check(rc, "qattn_fp8_mla_paged_forward")
+    return out, lse, po, pl, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq
+
+
+def mla_sparse_auto_splits(B: int, Hq: int, Sq: int, topk: int, num_cus: int) -> int:
+    """qattn_mla_sparse_auto_splits (include/qattn_mla_sparse.h): a pure function of the shape and the CU count (no device needed)."""
+    return lib().qattn_mla_sparse_auto_splits(B, Hq, Sq, topk, num_cus)
+
+
+def _mla_row_pool_checks(L, pool, block_table, scale, dev, B, num_pages, page_size):
+    """the pool, the table and the scales of a row-major paged latent cache (include/qattn_mla_sparse.h); returns (max_pages, table_stride)"""
+    _require(isinstance(page_size, int) and page_size >= 1 and isinstance(num_pages, int) and num_pages > 0
+             and num_pages * page_size <= 2 ** 31 - 1, f"num_pages and page_size must be positive with a product below 2^31, got {num_pages}, {page_size}")
+    _require(pool.device == dev and pool.element_size() == 1 and pool.is_contiguous() and tuple(pool.shape) == (num_pages, page_size, MLA_D),
+             f"the pool must be a dense fp8 [num_pages={num_pages}, page_size={page_size}, {MLA_D}] tensor on {dev}")
+    _require(block_table.dtype == torch.int32 and block_table.device == dev and block_table.dim() == 2 and block_table.shape[0] == B
+             and block_table.shape[1] > 0 and block_table.stride(1) == 1 and (B == 1 or block_table.stride(0) >= block_table.shape[1]),
+             f"block_table must be an int32 [B={B}, max_pages] tensor on {dev} with dense rows")
+    _require(scale.dtype == torch.float32 and scale.device == dev and scale.is_contiguous() and tuple(scale.shape) == (B,),
+             f"scale must be a dense float32 [B] tensor on {dev}")
+    max_pages = block_table.shape[1]
+    _require(max_pages * page_size <= 2 ** 31 - 65, "max_pages * page_size must stay below 2^31 - 64")
+    return max_pages, (block_table.stride(0) if B > 1 else max_pages)
+
+
+def paged_mla_row_cache_append_fp8(pool: torch.Tensor, scale: torch.Tensor, block_table: torch.Tensor, seqlens: torch.Tensor,
+                                   ckv_new: torch.Tensor, kpe_new: torch.Tensor, *, num_pages: int, page_size: int,
+                                   fp8_dtype=torch.float8_e4m3fn, new_lens: Optional[torch.Tensor] = None, advance: bool = True) -> None:
+    """qattn_paged_mla_row_cache_append_fp8 (include/qattn_mla_sparse.h): ckv_new [B, T, 512] and kpe_new [B, T, 64] (views accepted) into the
+    row-major pool [num_pages, page_size, 576] through block_table.  The table, seqlens and new_lens are read on the device.  Mutates pool
+    and seqlens."""
+    _require(ckv_new.is_cuda and ckv_new.dim() == 3 and ckv_new.dtype in (torch.bfloat16, torch.float16) and ckv_new.shape[2] == MLA_D_LATENT,
+             f"ckv_new must be a bf16 / fp16 device tensor [B, T, {MLA_D_LATENT}]")
+    _require(kpe_new.dim() == 3 and kpe_new.dtype == ckv_new.dtype and kpe_new.device == ckv_new.device
+             and tuple(kpe_new.shape) == (ckv_new.shape[0], ckv_new.shape[1], MLA_D_ROPE), f"kpe_new must be [B, T, {MLA_D_ROPE}] beside ckv_new")
+    _require(mla_rows_addressable(ckv_new) and mla_rows_addressable(kpe_new), "ckv_new / kpe_new need dense channels and 16-byte-aligned rows")
+    B, T, _ = ckv_new.shape
+    _require(T > 0, "T must be positive")
+    L = lib()
+    dev = ckv_new.device
+    max_pages, tstride = _mla_row_pool_checks(L, pool, block_table, scale, dev, B, num_pages, page_size)
+    _lens_check("seqlens", seqlens, B, dev)
+    _lens_check("new_lens", new_lens, B, dev, optional=True)
+    s2 = lambda t: (ctypes.c_longlong * 2)(*[t.stride(i) if t.shape[i] > 1 else (T * t.shape[2], t.shape[2])[i] for i in (0, 1)])
+    with torch.cuda.device(dev):
+        rc = L.qattn_paged_mla_row_cache_append_fp8(ckv_new.data_ptr(), kpe_new.data_ptr(), fmt_of(ckv_new.dtype), s2(ckv_new), s2(kpe_new),
+                                                    pool.data_ptr(), scale.data_ptr(), block_table.data_ptr(), tstride, seqlens.data_ptr(),
+                                                    _ptr(new_lens), int(bool(advance)), B, T, num_pages, page_size, max_pages,
+                                                    fmt_of(fp8_dtype), _stream(ckv_new))
+    _check(rc, "qattn_paged_mla_row_cache_append_fp8")
+
+
+def fp8_mla_paged_sparse_attention(q: torch.Tensor, pool: torch.Tensor, scale: torch.Tensor, block_table: torch.Tensor, seqused_k: torch.Tensor,
+                                   indices: torch.Tensor, *, num_pages: int, page_size: int, fp8_dtype=torch.float8_e4m3fn, is_causal: bool,
+                                   sm_scale: float, num_splits: int, return_partials: bool = False, return_q8: bool = False):
+    """qattn_fp8_mla_paged_sparse_forward (include/qattn_mla_sparse.h) with num_splits >= 1 resolved by the caller; indices int32
+    [B, Sq, topk] with a dense last dimension.  Returns (out [B, Hq, Sq, 512], lse [B, Hq, Sq], partial_o, partial_lse, q8, scale_q); the
+    last four are empty unless asked for (partials: and num_splits > 1)."""
+    _require(q.is_cuda and q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[3] == MLA_D,
+             f"q must be a bf16 / fp16 device tensor [B, Hq, Sq, {MLA_D}]")
+    _require(mla_rows_addressable(q), "q needs dense channels and 16-byte-aligned rows")
+    B, Hq, Sq, _ = q.shape
+    dev = q.device
+    _require(indices.dtype == torch.int32 and indices.device == dev and indices.dim() == 3 and tuple(indices.shape[:2]) == (B, Sq)
+             and 1 <= indices.shape[2] <= MLA_SPARSE_MAX_TOPK and (indices.shape[2] == 1 or indices.stride(2) == 1)
+             and all(indices.shape[i] == 1 or indices.stride(i) >= 0 for i in (0, 1)),
+             f"indices must be an int32 [B={B}, Sq={Sq}, 1 <= topk <= {MLA_SPARSE_MAX_TOPK}] tensor on {dev} with a dense last dimension")
+    topk = indices.shape[2]
+    _require(isinstance(num_splits, int) and max(1, -(-topk // MLA_SPARSE_SPLIT_ENTRIES)) <= num_splits <= MLA_MAX_SPLITS,
+             f"num_splits must be in ceil(topk / {MLA_SPARSE_SPLIT_ENTRIES}) .. {MLA_MAX_SPLITS} here, got {num_splits}")
+    L = lib()
+    max_pages, tstride = _mla_row_pool_checks(L, pool, block_table, scale, dev, B, num_pages, page_size)
+    _lens_check("seqused_k", seqused_k, B, dev)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = torch.empty((B, Hq, Sq, MLA_D_LATENT), dtype=q.dtype, device=dev)
+    lse = f32(B, Hq, Sq)
+    parts = num_splits > 1 and return_partials
+    po, pl = (f32(num_splits, B, Hq, Sq, MLA_D_LATENT), f32(num_splits, B, Hq, Sq)) if parts else (f32(0), f32(0))
+    q8 = torch.empty((B, Hq, Sq, MLA_D) if return_q8 else (0,), dtype=torch.uint8, device=dev)
+    sq = f32(B, Hq, Sq) if return_q8 else f32(0)
+    wsb = 0 if parts else L.qattn_fp8_mla_paged_sparse_workspace_bytes(B, Hq, Sq, num_splits)
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev) if wsb else None
+    dense = (Hq * Sq * MLA_D, Sq * MLA_D, MLA_D)
+    s3 = None if q.is_contiguous() else (ctypes.c_longlong * 3)(*[q.stride(i) if q.shape[i] > 1 else dense[i] for i in (0, 1, 2)])
+    idense = (Sq * topk, topk)
+    i2 = None if indices.is_contiguous() else (ctypes.c_longlong * 2)(*[indices.stride(i) if indices.shape[i] > 1 else idense[i] for i in (0, 1)])
+    with torch.cuda.device(dev):
+        rc = L.qattn_fp8_mla_paged_sparse_forward(q.data_ptr(), fmt_of(q.dtype), s3, pool.data_ptr(), block_table.data_ptr(), tstride, num_pages,
+                                                  page_size, max_pages, scale.data_ptr(), indices.data_ptr(), i2, topk, out.data_ptr(),
+                                                  lse.data_ptr(), seqused_k.data_ptr(), B, Hq, Sq, fmt_of(fp8_dtype), int(bool(is_causal)),
+                                                  float(sm_scale), num_splits, q8.data_ptr() if return_q8 else None,
+                                                  sq.data_ptr() if return_q8 else None, po.data_ptr() if parts else None,
+                                                  pl.data_ptr() if parts else None, _ptr(ws), wsb, _stream(q))
+    _check(rc, "qattn_fp8_mla_paged_sparse_forward")
     return out, lse, po, pl, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq

@@ -17,8 +17,13 @@ a constant and q_pe by its inverse.  `scale` of the attention call is REQUIRED: 
 YaRN factor), never 1/sqrt(576).  q is quantised inside the kernel, token-wise, always to e4m3.  Table, lengths and clamping: paged.py.
 
 Package attributes, not names of `__all__`.  Not offered: packed variable-length q; windows, sinks, soft cap or trees on MLA; RoPE inside the
-append; the non-absorbed prefill form (ordinary MHA at D 192 / 128); precision "fast" / "auto"; per-token cache scales; DeepSeek-V3.2's
-sparse indexer."""
+append; the non-absorbed prefill form (ordinary MHA at D 192 / 128); precision "fast" / "auto"; per-token cache scales; the indexer of
+DeepSeek-V3.2's sparse attention (its scores and the top-k selection -- the attention over the selected keys is below).
+
+SPARSE (top-k indexed) decode, the attention of DeepSeek-V3.2-style layers (include/qattn_mla_sparse.h):
+`alloc_paged_mla_row_cache_fp8`, `paged_mla_row_cache_append_fp8`, `fp8_mla_paged_sparse_func`.  The cache is ROW-MAJOR -- a key is one
+contiguous 576-byte row, any page_size -- and `indices` int32 [B, Sq, topk] names the LOGICAL key positions each query token attends, shared
+by all its heads; the kernel resolves them through the block table and gathers exactly those rows."""
 import math
 from typing import Optional, Tuple
 
@@ -31,6 +36,7 @@ from .paged import _lens_reason
 from .utils import checks
 
 D, D_LATENT, D_ROPE, MAX_SPLITS = _native.MLA_D, _native.MLA_D_LATENT, _native.MLA_D_ROPE, _native.MLA_MAX_SPLITS
+SPLIT_ENTRIES, MAX_TOPK = _native.MLA_SPARSE_SPLIT_ENTRIES, _native.MLA_SPARSE_MAX_TOPK
 _CHUNK = 64 * D
 _CPU_NUM_CUS = 256   # the CU count the split rule assumes where there is no device to ask (CPU tensors: the eager definition)
 
@@ -125,10 +131,13 @@ def alloc_paged_mla_cache_fp8(num_pages: int, page_size: int, *, batch_size: int
     return PagedMLACacheFP8(pool, sc, table, seqlens, num_pages, page_size, fp8_format, dtype, "frag")
 
 
-def _cache_reason(cache) -> Optional[str]:
+def _cache_reason(cache, row: bool = False) -> Optional[str]:
+    """row: the rules of the row-major cache of the sparse call (any page_size >= 1) instead of the chunk image's"""
     if not isinstance(cache, PagedMLACacheFP8):
         return "Expected cache to be a PagedMLACacheFP8 (alloc_paged_mla_cache_fp8)"
-    if not (_is_int(cache.page_size) and cache.page_size >= 64 and cache.page_size % 64 == 0):
+    if row and not (_is_int(cache.page_size) and cache.page_size >= 1):
+        return f"page_size must be a positive integer, got {cache.page_size!r}"
+    if not row and not (_is_int(cache.page_size) and cache.page_size >= 64 and cache.page_size % 64 == 0):
         return f"page_size must be a positive multiple of 64 (a page holds whole 64-key chunks), got {cache.page_size!r}"
     t = cache.block_table
     if not isinstance(t, Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] == 0 or t.shape[1] == 0 or t.stride(1) != 1:
@@ -141,28 +150,25 @@ def _cache_reason(cache) -> Optional[str]:
     return None
 
 
-def mla_input_reason(q, cache, *, scale=None, seqused_k=None, max_seqlen_k=None, num_splits=0, ckv_new=None, kpe_new=None,
-                     new_lens=None) -> Optional[str]:
-    """The first rule the arguments of `fp8_mla_paged_func` (q given) or `paged_mla_cache_append_fp8` (q None; ckv_new, kpe_new given) break,
-    or None.  Shapes, dtypes, devices and strides only: the CONTENTS of block_table / seqlens are read on the device."""
-    reason = _cache_reason(cache)
-    if reason:
-        return reason
+def _append_reason(cache, ckv_new, kpe_new, new_lens) -> Optional[str]:
     B = cache.batch_size
-    if q is None:
-        for name, t, ch in (("ckv_new", ckv_new, D_LATENT), ("kpe_new", kpe_new, D_ROPE)):
-            if not isinstance(t, Tensor) or t.dim() != 3 or t.shape[0] != B or t.shape[1] == 0 or t.shape[2] != ch:
-                return f"Expected {name} to be a tensor [{B}, T >= 1, {ch}], but got {list(getattr(t, 'shape', ()))}"
-            if t.dtype != cache.dtype or t.requires_grad:
-                return f"Expected {name} to be a leaf tensor of the cache's dtype {cache.dtype}, but got {t.dtype}"
-            if t.device != cache.device:
-                return f"Expected {name} to be on the cache's device {cache.device}, but got {t.device} instead."
-            if not _native.mla_rows_addressable(t):
-                return f"Expected {name} to have dense channels and 16-byte-aligned rows, but got strides {tuple(t.stride())}; pass {name}.contiguous()"
-        if ckv_new.shape[1] != kpe_new.shape[1]:
-            return f"Expect ckv_new and kpe_new to hold the same tokens but got T = {ckv_new.shape[1]} and {kpe_new.shape[1]}."
-        reason = _lens_reason("cache.seqlens", cache.seqlens, B, cache.device)
-        return reason if reason or new_lens is None else _lens_reason("new_lens", new_lens, B, cache.device)
+    for name, t, ch in (("ckv_new", ckv_new, D_LATENT), ("kpe_new", kpe_new, D_ROPE)):
+        if not isinstance(t, Tensor) or t.dim() != 3 or t.shape[0] != B or t.shape[1] == 0 or t.shape[2] != ch:
+            return f"Expected {name} to be a tensor [{B}, T >= 1, {ch}], but got {list(getattr(t, 'shape', ()))}"
+        if t.dtype != cache.dtype or t.requires_grad:
+            return f"Expected {name} to be a leaf tensor of the cache's dtype {cache.dtype}, but got {t.dtype}"
+        if t.device != cache.device:
+            return f"Expected {name} to be on the cache's device {cache.device}, but got {t.device} instead."
+        if not _native.mla_rows_addressable(t):
+            return f"Expected {name} to have dense channels and 16-byte-aligned rows, but got strides {tuple(t.stride())}; pass {name}.contiguous()"
+    if ckv_new.shape[1] != kpe_new.shape[1]:
+        return f"Expect ckv_new and kpe_new to hold the same tokens but got T = {ckv_new.shape[1]} and {kpe_new.shape[1]}."
+    reason = _lens_reason("cache.seqlens", cache.seqlens, B, cache.device)
+    return reason if reason or new_lens is None else _lens_reason("new_lens", new_lens, B, cache.device)
+
+
+def _query_reason(q, cache, scale, seqused_k) -> Optional[str]:
+    B = cache.batch_size
     if not isinstance(q, Tensor) or q.dim() != 4:
         return "NYI: query must be a 4-D tensor [B, Hq, Sq, 576]"
     if q.requires_grad:
@@ -181,7 +187,19 @@ def mla_input_reason(q, cache, *, scale=None, seqused_k=None, max_seqlen_k=None,
         return "scale is required: MLA's softmax scale is the model's (1/sqrt(192) times its YaRN factor), not 1/sqrt(576)"
     if not (isinstance(scale, (int, float)) and not isinstance(scale, bool) and math.isfinite(scale) and scale > 0):
         return f"scale must be a finite number > 0, got {scale!r}"
-    reason = _lens_reason("seqused_k" if seqused_k is not None else "cache.seqlens", cache.seqlens if seqused_k is None else seqused_k, B, q.device)
+    return _lens_reason("seqused_k" if seqused_k is not None else "cache.seqlens", cache.seqlens if seqused_k is None else seqused_k, B, q.device)
+
+
+def mla_input_reason(q, cache, *, scale=None, seqused_k=None, max_seqlen_k=None, num_splits=0, ckv_new=None, kpe_new=None,
+                     new_lens=None) -> Optional[str]:
+    """The first rule the arguments of `fp8_mla_paged_func` (q given) or `paged_mla_cache_append_fp8` (q None; ckv_new, kpe_new given) break,
+    or None.  Shapes, dtypes, devices and strides only: the CONTENTS of block_table / seqlens are read on the device."""
+    reason = _cache_reason(cache)
+    if reason:
+        return reason
+    if q is None:
+        return _append_reason(cache, ckv_new, kpe_new, new_lens)
+    reason = _query_reason(q, cache, scale, seqused_k)
     if reason:
         return reason
     if max_seqlen_k is not None and not (_is_int(max_seqlen_k) and 1 <= max_seqlen_k <= cache.capacity):
@@ -358,6 +376,184 @@ def fp8_mla_paged_func(q: Tensor, cache: PagedMLACacheFP8, *, scale: Optional[fl
             raise ValueError(why)
         out, lse, po, plse, q8, sq = nn._ops().fp8_paged_mla_attention_forward(
             q, cache.pool, cache.scale, cache.block_table, used, Skv, cache.num_pages, cache.page_size, ns, float(scale), cache.fp8_format,
+            bool(causal), bool(return_partials), bool(return_q8))
+    res: Tuple = (out,)
+    if return_lse:
+        res += (lse,)
+    if return_partials:
+        res += (po, plse)
+    if return_q8:
+        res += (q8, sq)
+    return res if len(res) > 1 else out
+
+
+# ---- sparse (top-k indexed) decode on a row-major cache (include/qattn_mla_sparse.h) -------------------------------------------------------------
+def alloc_paged_mla_row_cache_fp8(num_pages: int, page_size: int, *, batch_size: int, max_pages_per_seq: int, scale, dtype, device,
+                                  fp8_format: Optional[str] = None) -> PagedMLACacheFP8:
+    """An empty ROW-MAJOR paged latent cache for `fp8_mla_paged_sparse_func`: a zero-filled fp8 pool [num_pages, page_size, 576] (a key is one
+    contiguous row; page_size is any integer >= 1), a zero-filled block table int32 [batch_size, max_pages_per_seq] and seqlens = 0, on
+    any device.  num_pages * page_size <= 2^31 - 1 and max_pages_per_seq * page_size <= 2^31 - 65; scale and dtype as
+    `alloc_paged_mla_cache_fp8`.  layout = "rowmajor"."""
+    reason = _alloc_reason(num_pages, 64, batch_size, max_pages_per_seq, scale, dtype)
+    if not reason and not (_is_int(page_size) and page_size >= 1):
+        reason = f"page_size must be a positive integer, got {page_size!r}"
+    if not reason and (num_pages * page_size > 2 ** 31 - 1 or max_pages_per_seq * page_size > 2 ** 31 - 65):
+        reason = "num_pages * page_size and max_pages_per_seq * page_size must stay below 2^31"
+    if reason:
+        raise ValueError(reason)
+    fp8_format = checks.config_value("attention.fp8_format") if fp8_format is None else fp8_format
+    fp8_dtype = _native.fp8_dtype_of(fp8_format)
+    device = torch.device(device)
+    if device.type == "cuda" and not checks.config_value("attention.force_eager_fallback"):
+        ok, why = nn._pre_check_can_use_hip_attention(device=device)
+        if not ok:
+            raise ValueError(why)
+    sc = (torch.as_tensor(scale, dtype=torch.float32, device=device) if isinstance(scale, Tensor)
+          else torch.full((), float(scale), dtype=torch.float32, device=device)).expand(batch_size).contiguous()
+    table = torch.zeros((batch_size, max_pages_per_seq), dtype=torch.int32, device=device)
+    seqlens = torch.zeros((batch_size,), dtype=torch.int32, device=device)
+    pool = torch.zeros((num_pages, page_size, D), dtype=torch.uint8, device=device).view(fp8_dtype)
+    return PagedMLACacheFP8(pool, sc, table, seqlens, num_pages, page_size, fp8_format, dtype, "rowmajor")
+
+
+def mla_sparse_input_reason(q, cache, indices=None, *, scale=None, seqused_k=None, num_splits=0, ckv_new=None, kpe_new=None,
+                            new_lens=None) -> Optional[str]:
+    """The first rule the arguments of `fp8_mla_paged_sparse_func` (q, indices given) or `paged_mla_row_cache_append_fp8` (q None; ckv_new,
+    kpe_new given) break, or None.  Shapes, dtypes, devices and strides only: the CONTENTS of indices / block_table / seqlens are read on
+    the device."""
+    reason = _cache_reason(cache, row=True)
+    if reason:
+        return reason
+    p = cache.pool
+    if cache.layout != "rowmajor" or not isinstance(p, Tensor) or tuple(p.shape) != (cache.num_pages, cache.page_size, D) or not p.is_contiguous():
+        return (f"Expected a row-major cache (alloc_paged_mla_row_cache_fp8) with a dense pool [num_pages, page_size, {D}]; "
+                "a chunk-image cache (alloc_paged_mla_cache_fp8) serves fp8_mla_paged_func")
+    if q is None:
+        return _append_reason(cache, ckv_new, kpe_new, new_lens)
+    reason = _query_reason(q, cache, scale, seqused_k)
+    if reason:
+        return reason
+    B, Sq = q.shape[0], q.shape[2]
+    if (not isinstance(indices, Tensor) or indices.dtype != torch.int32 or indices.dim() != 3 or tuple(indices.shape[:2]) != (B, Sq)
+            or not 1 <= indices.shape[2] <= MAX_TOPK):
+        return (f"Expected indices to be a torch.int32 tensor [{B}, {Sq}, 1 <= topk <= {MAX_TOPK}] of logical key positions, but got "
+                f"{getattr(indices, 'dtype', None)} {list(getattr(indices, 'shape', ()))}")
+    if indices.device != q.device:
+        return f"Expected indices to be on the query's device {q.device}, but got {indices.device} instead."
+    if (indices.shape[2] > 1 and indices.stride(2) != 1) or any(indices.shape[i] > 1 and indices.stride(i) < 0 for i in (0, 1)):
+        return f"Expected indices to have a dense last dimension, but got strides {tuple(indices.stride())}; pass indices.contiguous()"
+    least = -(-indices.shape[2] // SPLIT_ENTRIES)
+    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or not (num_splits == 0 or least <= num_splits <= MAX_SPLITS):
+        return (f"num_splits must be 0 (choose) or an integer in ceil(topk / {SPLIT_ENTRIES}) = {least} .. {MAX_SPLITS} (a split resolves at "
+                f"most {SPLIT_ENTRIES} entries), got {num_splits!r}")
+    return None
+
+
+def sparse_split_plan(topk: int, num_splits: int):
+    """Entry ranges [lo, hi) of the splits of a list of topk entries: ceil(topk / 64) groups, per = ceil(groups / ns) per split."""
+    per = -(-(-(-topk // 64)) // num_splits)
+    return [(min(64 * s * per, topk), min(64 * (s + 1) * per, topk)) for s in range(num_splits)]
+
+
+def _attend_sparse_eager(q, cache, indices, causal, scale, seqused_k, ns):
+    """gather the listed valid rows through the (clamped) table, de-quantise, fp32 softmax per split over the entries in list order, values =
+    the first 512 channels; the partials are merged by `combine_eager`.  (Reads indices / block_table / seqused_k on the host.)"""
+    B, Hq, Sq, _ = q.shape
+    topk, ps = indices.shape[2], cache.page_size
+    q8, scale_q = quantize_q_eager(q)
+    qd = q8.float() * scale_q[..., None]
+    table = cache.block_table.clamp(0, cache.num_pages - 1).long()
+    po = torch.zeros((ns, B, Hq, Sq, D_LATENT), dtype=torch.float32, device=q.device)
+    plse = torch.full((ns, B, Hq, Sq), -math.inf, dtype=torch.float32, device=q.device)
+    for b, Lb in enumerate(seqused_k.tolist()):
+        Lb = min(max(int(Lb), 0), cache.capacity)
+        for i in range(Sq):
+            kend = max(Lb - Sq + i + 1, 0) if causal else Lb
+            for s, (lo, hi) in enumerate(sparse_split_plan(topk, ns)):
+                j = indices[b, i, lo:hi].long()
+                j = j[(j >= 0) & (j < kend)]
+                if j.numel() == 0:
+                    continue
+                lat = cache.pool[table[b][j // ps], j % ps].float() * cache.scale[b]          # [n, 576]
+                sc = qd[b, :, i] @ lat.T * scale
+                lse = torch.logsumexp(sc, dim=-1)
+                po[s, b, :, i] = torch.exp(sc - lse[:, None]) @ lat[:, :D_LATENT]
+                plse[s, b, :, i] = lse
+    out, lse = combine_eager(po, plse, q.dtype)
+    empty = torch.empty((0,), dtype=torch.float32, device=q.device)
+    return out, lse, (po if ns > 1 else empty), (plse if ns > 1 else empty), q8, scale_q
+
+
+def paged_mla_row_cache_append_fp8(cache: PagedMLACacheFP8, ckv_new: Tensor, kpe_new: Tensor, *, new_lens: Optional[Tensor] = None,
+                                   advance: bool = True) -> PagedMLACacheFP8:
+    """Append T tokens per slot to the ROW-MAJOR paged latent `cache` (alloc_paged_mla_row_cache_fp8), in place; returns `cache`.  The contract
+    of `paged_mla_cache_append_fp8` word for word -- views read through their strides, the same quantiser, tokens at or beyond the capacity
+    dropped, every table entry clamped, exactly the bytes of the appended keys change, everything read on the device -- with key j of slot
+    b stored as row j % page_size of page block_table[b, j // page_size].  CPU tensors and config.attention.force_eager_fallback run the
+    eager definition (`_append_eager`); on the device there is no fallback.  Invalid input raises ValueError(reason)."""
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = mla_sparse_input_reason(None, cache, ckv_new=ckv_new, kpe_new=kpe_new, new_lens=new_lens)
+        if reason:
+            raise ValueError(reason)
+    if _eager(ckv_new):
+        _append_eager(cache, ckv_new, kpe_new, new_lens, bool(advance))
+        return cache
+    ok, why = nn._pre_check_can_use_hip_attention(device=ckv_new.device)
+    if not ok:
+        raise ValueError(why)
+    if torch.compiler.is_compiling():
+        nn._ops().fp8_paged_mla_row_cache_append_(cache.pool, cache.scale, cache.block_table, cache.seqlens, ckv_new, kpe_new, new_lens,
+                                                  cache.num_pages, cache.page_size, cache.fp8_format, bool(advance))
+    else:
+        _native.paged_mla_row_cache_append_fp8(cache.pool, cache.scale, cache.block_table, cache.seqlens, ckv_new, kpe_new,
+                                               num_pages=cache.num_pages, page_size=cache.page_size,
+                                               fp8_dtype=_native.fp8_dtype_of(cache.fp8_format), new_lens=new_lens, advance=bool(advance))
+    return cache
+
+
+@torch.compiler.assume_constant_result
+def _resolve_sparse_splits(num_splits: int, B: int, Hq: int, Sq: int, topk: int, device) -> int:
+    if num_splits:
+        return num_splits
+    cus = torch.cuda.get_device_properties(device).multi_processor_count if torch.device(device).type == "cuda" else _CPU_NUM_CUS
+    return _native.mla_sparse_auto_splits(B, Hq, Sq, topk, cus)
+
+
+def fp8_mla_paged_sparse_func(q: Tensor, cache: PagedMLACacheFP8, indices: Tensor, *, scale: Optional[float] = None, causal: bool = True,
+                              seqused_k: Optional[Tensor] = None, num_splits: int = 0, return_lse: bool = False,
+                              return_partials: bool = False, return_q8: bool = False):
+    """Sparse absorbed MLA decode (DeepSeek-V3.2-style layers): q [B, Hq, Sq, 576] attends only the keys `indices` names in the row-major
+    paged latent cache; returns out [B, Hq, Sq, 512] in q's dtype.
+
+    indices       int32 [B, Sq, topk] on q's device, last dimension dense, topk >= 1 arbitrary: LOGICAL key positions of slot b, shared by
+                  all Hq heads of (b, i) and resolved through cache.block_table on the device.  An entry j is VALID iff 0 <= j < kend(b, i),
+                  kend = L_b (causal=False) or L_b - Sq + i + 1 (causal=True), L_b = clamp(seqused_k[b], 0, capacity).  Everything else
+                  (-1, padding, positions at or behind the limit) contributes nothing, whatever bytes it points at.  Entries count as often
+                  as they are listed; a row without a valid entry is a zero row with LSE -inf.
+    scale         REQUIRED: the model's softmax scale, as in `fp8_mla_paged_func`.
+    seqused_k     int32 [B] on the device, default cache.seqlens.
+    num_splits    0: `qattn_mla_sparse_auto_splits`; else ceil(topk / 2048) .. 64 splits of the LIST (64-entry groups), merged by ONE
+                  combine launch.
+    return_lse / return_partials / return_q8 as in `fp8_mla_paged_func`.  Numerics are that call's: q quantised in the kernel (token-wise
+    e4m3), two-term e4m3 P, both products on the FP8 matrix instructions.
+    Indices, table and lengths are read on the device: no host synchronisation, graph-capture safe.  CPU tensors and
+    config.attention.force_eager_fallback run the eager definition (`_attend_sparse_eager`); on the device there is no fallback.
+    Unsupported input raises ValueError(reason)."""
+    if not checks.config_value("attention.skip_supported_check"):
+        reason = mla_sparse_input_reason(q, cache, indices, scale=scale, seqused_k=seqused_k, num_splits=num_splits)
+        if reason:
+            raise ValueError(reason)
+    B, Hq, Sq, _ = q.shape
+    used = cache.seqlens if seqused_k is None else seqused_k
+    ns = _resolve_sparse_splits(num_splits, B, Hq, Sq, indices.shape[2], q.device)
+    if _eager(q):
+        out, lse, po, plse, q8, sq = _attend_sparse_eager(q, cache, indices, bool(causal), float(scale), used, ns)
+    else:
+        ok, why = nn._pre_check_can_use_hip_attention(device=q.device)
+        if not ok:
+            raise ValueError(why)
+        out, lse, po, plse, q8, sq = nn._ops().fp8_paged_mla_sparse_attention_forward(
+            q, cache.pool, cache.scale, cache.block_table, used, indices, cache.num_pages, cache.page_size, ns, float(scale), cache.fp8_format,
             bool(causal), bool(return_partials), bool(return_q8))
     res: Tuple = (out,)
     if return_lse:

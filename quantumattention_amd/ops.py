@@ -1416,3 +1416,66 @@ def _(query, pool, scale_kv, block_table, seqused_k, seqlen_k, num_pages, page_s
     po, pl = (f32(n, B, Hq, Sq, 512), f32(n, B, Hq, Sq)) if n else (f32(0), f32(0))
     q8 = query.new_empty((B, Hq, Sq, D), dtype=torch.float8_e4m3fn) if return_q8 else query.new_empty((0,), dtype=torch.uint8)
     return query.new_empty((B, Hq, Sq, 512)), f32(B, Hq, Sq), po, pl, q8, (f32(B, Hq, Sq) if return_q8 else f32(0))
+
+
+@_custom_op("quantumattention_amd::fp8_paged_mla_row_cache_append_", mutates_args=("pool", "seqlens"), device_types=("cuda",))
+def fp8_paged_mla_row_cache_append_(
+    pool: torch.Tensor,
+    scale: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens: torch.Tensor,
+    ckv_new: torch.Tensor,
+    kpe_new: torch.Tensor,
+    new_lens: Optional[torch.Tensor],
+    num_pages: int,
+    page_size: int,
+    fp8_format: str = "e4m3",
+    advance: bool = True,
+) -> None:
+    """Append to the row-major paged FP8 latent cache of sparse multi-head latent attention IN PLACE (include/qattn_mla_sparse.h): ckv_new
+    [B, T, 512] and kpe_new [B, T, 64] through block_table int32 [B, max_pages].  Reference implementation: mla._append_eager.  Arguments
+    are validated by mla.paged_mla_row_cache_append_fp8."""
+    _native.paged_mla_row_cache_append_fp8(pool, scale, block_table, seqlens, ckv_new, kpe_new, num_pages=num_pages, page_size=page_size,
+                                           fp8_dtype=_native.fp8_dtype_of(fp8_format), new_lens=new_lens, advance=advance)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_mla_row_cache_append_")
+def _(pool, scale, block_table, seqlens, ckv_new, kpe_new, new_lens, num_pages, page_size, fp8_format="e4m3", advance=True):
+    return None
+
+
+@_custom_op("quantumattention_amd::fp8_paged_mla_sparse_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_paged_mla_sparse_attention_forward(
+    query: torch.Tensor,
+    pool: torch.Tensor,
+    scale_kv: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    indices: torch.Tensor,
+    num_pages: int,
+    page_size: int,
+    num_splits: int,
+    scale: float,
+    fp8_format: str = "e4m3",
+    is_causal: bool = True,
+    return_partials: bool = False,
+    return_q8: bool = False,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Sparse absorbed multi-head latent attention of query [B, Hq, Sq, 576] over the keys indices int32 [B, Sq, topk] name in the row-major
+    paged FP8 latent cache (include/qattn_mla_sparse.h); num_splits >= 1 (resolved by the caller), scale the model's softmax scale.  Returns
+    (out [B, Hq, Sq, 512], lse [B, Hq, Sq], partial_o, partial_lse, q8, scale_q).  Reference implementation: mla._attend_sparse_eager.
+    Arguments are validated by mla.fp8_mla_paged_sparse_func."""
+    return _native.fp8_mla_paged_sparse_attention(query, pool, scale_kv, block_table, seqused_k, indices, num_pages=num_pages,
+                                                  page_size=page_size, fp8_dtype=_native.fp8_dtype_of(fp8_format), is_causal=is_causal,
+                                                  sm_scale=scale, num_splits=num_splits, return_partials=return_partials, return_q8=return_q8)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_mla_sparse_attention_forward")
+def _(query, pool, scale_kv, block_table, seqused_k, indices, num_pages, page_size, num_splits, scale, fp8_format="e4m3", is_causal=True,
+      return_partials=False, return_q8=False):
+    B, Hq, Sq, D = query.shape
+    f32 = lambda *shape: query.new_empty(shape, dtype=torch.float32)
+    n = num_splits if (num_splits > 1 and return_partials) else 0
+    po, pl = (f32(n, B, Hq, Sq, 512), f32(n, B, Hq, Sq)) if n else (f32(0), f32(0))
+    q8 = query.new_empty((B, Hq, Sq, D), dtype=torch.float8_e4m3fn) if return_q8 else query.new_empty((0,), dtype=torch.uint8)
+    return query.new_empty((B, Hq, Sq, 512)), f32(B, Hq, Sq), po, pl, q8, (f32(B, Hq, Sq) if return_q8 else f32(0))
