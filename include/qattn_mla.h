@@ -55,7 +55,7 @@
  * large enough; formats: QATTN_ERR_UNSUPPORTED_FMT.  Buffers: include/qattn_buffers.h.
  *
  * Not offered: packed variable-length q; windows, sinks, soft cap or trees on MLA; RoPE inside the append (the caller rotates k_pe); the
- * non-absorbed prefill form (ordinary MHA at D 192 / 128); precision "fast" / "auto"; per-token cache scales; DeepSeek-V3.2's sparse indexer.
+ * non-absorbed prefill form (ordinary MHA at D 192 / 128); precision "fast" / "auto"; per-token cache scales.  (DeepSeek-V3.2's sparse indexer: include/qattn_mla_index.h.)
  */
 #ifndef QATTN_MLA_H_
 #define QATTN_MLA_H_

@@ -112,3 +112,12 @@ from .mla import (  # noqa: E402
     mla_sparse_input_reason,
     paged_mla_row_cache_append_fp8,
 )
+# ... and the lightning indexer that produces the sparse form's indices (include/qattn_mla_index.h): package attributes, not in __all__
+from .mla_index import (  # noqa: E402
+    PagedMLAIndexCacheFP8,
+    alloc_paged_mla_index_cache_fp8,
+    fp8_mla_index_topk_func,
+    mla_index_input_reason,
+    mla_index_select,
+    paged_mla_index_cache_append_fp8,
+)

@@ -70,6 +70,8 @@ EXPORTS = (
     "qattn_fp8_mla_paged_forward",
     "qattn_mla_row_pool_bytes", "qattn_mla_sparse_auto_splits", "qattn_fp8_mla_paged_sparse_workspace_bytes",
     "qattn_paged_mla_row_cache_append_fp8", "qattn_fp8_mla_paged_sparse_forward",
+    "qattn_mla_index_pool_bytes", "qattn_fp8_mla_index_workspace_bytes", "qattn_paged_mla_index_cache_append_fp8",
+    "qattn_fp8_mla_index_scores", "qattn_mla_index_select", "qattn_fp8_mla_index_topk",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -79,6 +81,8 @@ SPLITKV_MAX_SPLITS = 64    # QATTN_SPLITKV_MAX_SPLITS (include/qattn_splitkv.h)
 MLA_D, MLA_D_LATENT, MLA_D_ROPE, MLA_MAX_SPLITS = 576, 512, 64, 64   # QATTN_MLA_* (include/qattn_mla.h)
 MLA_SPARSE_SPLIT_ENTRIES = 2048                                      # QATTN_MLA_SPARSE_SPLIT_ENTRIES (include/qattn_mla_sparse.h)
 MLA_SPARSE_MAX_TOPK = MLA_SPARSE_SPLIT_ENTRIES * MLA_MAX_SPLITS      # QATTN_MLA_SPARSE_MAX_TOPK
+MLA_INDEX_D, MLA_INDEX_MAX_HEADS = 128, 64                           # QATTN_MLA_INDEX_* (include/qattn_mla_index.h)
+MLA_INDEX_WG_KEYS, MLA_INDEX_LDS_CANDIDATES = 512, 8192
 
 
 class PathDesc(ctypes.Structure):
@@ -371,6 +375,19 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_mla_paged_sparse_forward.restype = i
     L.qattn_fp8_mla_paged_sparse_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, i, vp, vp, vp, i, i, i, i, i, f, i, vp, vp, vp, vp,
                                                      vp, sz, vp]
+    # the lightning indexer of sparse multi-head latent attention (include/qattn_mla_index.h)
+    L.qattn_mla_index_pool_bytes.restype = sz
+    L.qattn_mla_index_pool_bytes.argtypes = [i, i]
+    L.qattn_fp8_mla_index_workspace_bytes.restype = sz
+    L.qattn_fp8_mla_index_workspace_bytes.argtypes = [i, i, i]
+    L.qattn_paged_mla_index_cache_append_fp8.restype = i
+    L.qattn_paged_mla_index_cache_append_fp8.argtypes = [vp, i, vp, vp, vp, vp, ll, vp, vp, i, i, i, i, i, i, i, vp]
+    L.qattn_fp8_mla_index_scores.restype = i
+    L.qattn_fp8_mla_index_scores.argtypes = [vp, i, vp, vp, vp, vp, vp, ll, i, i, i, vp, vp, i, i, i, i, i, i, vp, vp, i, vp, vp, vp]
+    L.qattn_mla_index_select.restype = i
+    L.qattn_mla_index_select.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp]
+    L.qattn_fp8_mla_index_topk.restype = i
+    L.qattn_fp8_mla_index_topk.argtypes = [vp, i, vp, vp, vp, vp, vp, ll, i, i, i, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -2025,3 +2042,107 @@ def fp8_mla_paged_sparse_attention(q: torch.Tensor, pool: torch.Tensor, scale: t
                                                   pl.data_ptr() if parts else None, _ptr(ws), wsb, _stream(q))
     _check(rc, "qattn_fp8_mla_paged_sparse_forward")
     return out, lse, po, pl, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq
+
+
+def _mla_index_pool_checks(pool, block_table, scale, dev, B, num_pages, page_size):
+    """the pool, the table and the scales of a paged index-key cache (include/qattn_mla_index.h); returns (max_pages, table_stride)"""
+    _require(isinstance(page_size, int) and page_size >= 1 and isinstance(num_pages, int) and num_pages > 0
+             and num_pages * page_size <= 2 ** 31 - 1, f"num_pages and page_size must be positive with a product below 2^31, got {num_pages}, {page_size}")
+    _require(pool.device == dev and pool.element_size() == 1 and pool.is_contiguous() and tuple(pool.shape) == (num_pages, page_size, MLA_INDEX_D),
+             f"the pool must be a dense fp8 [num_pages={num_pages}, page_size={page_size}, {MLA_INDEX_D}] tensor on {dev}")
+    _require(block_table.dtype == torch.int32 and block_table.device == dev and block_table.dim() == 2 and block_table.shape[0] == B
+             and block_table.shape[1] > 0 and block_table.stride(1) == 1 and (B == 1 or block_table.stride(0) >= block_table.shape[1]),
+             f"block_table must be an int32 [B={B}, max_pages] tensor on {dev} with dense rows")
+    _require(scale.dtype == torch.float32 and scale.device == dev and scale.is_contiguous() and tuple(scale.shape) == (B,),
+             f"scale must be a dense float32 [B] tensor on {dev}")
+    max_pages = block_table.shape[1]
+    _require(max_pages * page_size <= 2 ** 31 - 65, "max_pages * page_size must stay below 2^31 - 64")
+    return max_pages, (block_table.stride(0) if B > 1 else max_pages)
+
+
+def paged_mla_index_cache_append_fp8(pool: torch.Tensor, scale: torch.Tensor, block_table: torch.Tensor, seqlens: torch.Tensor,
+                                     k_new: torch.Tensor, *, num_pages: int, page_size: int, fp8_dtype=torch.float8_e4m3fn,
+                                     new_lens: Optional[torch.Tensor] = None, advance: bool = True) -> None:
+    """qattn_paged_mla_index_cache_append_fp8 (include/qattn_mla_index.h): k_new [B, T, 128] (views accepted) into the row-major pool
+    [num_pages, page_size, 128] through block_table.  The table, seqlens and new_lens are read on the device.  Mutates pool and seqlens."""
+    _require(k_new.is_cuda and k_new.dim() == 3 and k_new.dtype in (torch.bfloat16, torch.float16) and k_new.shape[2] == MLA_INDEX_D,
+             f"k_new must be a bf16 / fp16 device tensor [B, T, {MLA_INDEX_D}]")
+    _require(mla_rows_addressable(k_new), "k_new needs dense channels and 16-byte-aligned rows")
+    B, T, _ = k_new.shape
+    _require(T > 0, "T must be positive")
+    dev = k_new.device
+    max_pages, tstride = _mla_index_pool_checks(pool, block_table, scale, dev, B, num_pages, page_size)
+    _lens_check("seqlens", seqlens, B, dev)
+    _lens_check("new_lens", new_lens, B, dev, optional=True)
+    s2 = (ctypes.c_longlong * 2)(*[k_new.stride(i) if k_new.shape[i] > 1 else (T * MLA_INDEX_D, MLA_INDEX_D)[i] for i in (0, 1)])
+    with torch.cuda.device(dev):
+        rc = lib().qattn_paged_mla_index_cache_append_fp8(k_new.data_ptr(), fmt_of(k_new.dtype), s2, pool.data_ptr(), scale.data_ptr(),
+                                                          block_table.data_ptr(), tstride, seqlens.data_ptr(), _ptr(new_lens),
+                                                          int(bool(advance)), B, T, num_pages, page_size, max_pages, fmt_of(fp8_dtype),
+                                                          _stream(k_new))
+    _check(rc, "qattn_paged_mla_index_cache_append_fp8")
+
+
+def _rows2(t: torch.Tensor):
+    """the {batch, position} element strides of a [B, Sq, n] tensor with a dense last dimension, or None for a dense tensor"""
+    if t.is_contiguous():
+        return None
+    dense = (t.shape[1] * t.shape[2], t.shape[2])
+    return (ctypes.c_longlong * 2)(*[t.stride(i) if t.shape[i] > 1 else dense[i] for i in (0, 1)])
+
+
+def mla_index_select(logits: torch.Tensor, seqused_k: torch.Tensor, topk: int, *, is_causal: bool) -> torch.Tensor:
+    """qattn_mla_index_select (include/qattn_mla_index.h): logits fp32 [B, Sq, N] (last dimension dense) -> indices int32 [B, Sq, topk]."""
+    _require(logits.is_cuda and logits.dim() == 3 and logits.dtype == torch.float32 and logits.numel() > 0
+             and (logits.shape[2] == 1 or logits.stride(2) == 1) and all(logits.shape[i] == 1 or logits.stride(i) >= 0 for i in (0, 1)),
+             "logits must be a float32 device tensor [B, Sq, N] with a dense last dimension")
+    _require(isinstance(topk, int) and 1 <= topk <= MLA_SPARSE_MAX_TOPK, f"topk must be in 1 .. {MLA_SPARSE_MAX_TOPK}, got {topk}")
+    B, Sq, N = logits.shape
+    _lens_check("seqused_k", seqused_k, B, logits.device)
+    out = torch.empty((B, Sq, topk), dtype=torch.int32, device=logits.device)
+    with torch.cuda.device(logits.device):
+        rc = lib().qattn_mla_index_select(logits.data_ptr(), _rows2(logits), seqused_k.data_ptr(), B, Sq, N, topk, int(bool(is_causal)),
+                                          out.data_ptr(), _stream(logits))
+    _check(rc, "qattn_mla_index_select")
+    return out
+
+
+def fp8_mla_index_topk(q: torch.Tensor, weights: torch.Tensor, pool: torch.Tensor, scale: torch.Tensor, block_table: torch.Tensor,
+                       seqused_k: torch.Tensor, *, Skv: int, topk: int, num_pages: int, page_size: int, fp8_dtype=torch.float8_e4m3fn,
+                       is_causal: bool, return_logits: bool = False, return_q8: bool = False, select: bool = True):
+    """qattn_fp8_mla_index_topk (include/qattn_mla_index.h), or with select=False qattn_fp8_mla_index_scores alone (logits with a filled
+    tail).  Returns (indices int32 [B, Sq, topk], logits fp32 [B, Sq, Skv], q8 [B, Hi, Sq, 128] e4m3, scale_q [B, Hi, Sq]); what was not
+    asked for (or not computed) is empty."""
+    _require(q.is_cuda and q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[3] == MLA_INDEX_D
+             and 1 <= q.shape[1] <= MLA_INDEX_MAX_HEADS, f"q must be a bf16 / fp16 device tensor [B, Hi <= {MLA_INDEX_MAX_HEADS}, Sq, {MLA_INDEX_D}]")
+    _require(mla_rows_addressable(q), "q needs dense channels and 16-byte-aligned rows")
+    B, Hi, Sq, _ = q.shape
+    dev = q.device
+    _require(weights.dtype == torch.float32 and weights.device == dev and tuple(weights.shape) == (B, Sq, Hi)
+             and (Hi == 1 or weights.stride(2) == 1) and all(weights.shape[i] == 1 or weights.stride(i) >= 0 for i in (0, 1)),
+             f"weights must be a float32 [B={B}, Sq={Sq}, Hi={Hi}] tensor on {dev} with dense heads")
+    _require(isinstance(topk, int) and 1 <= topk <= MLA_SPARSE_MAX_TOPK, f"topk must be in 1 .. {MLA_SPARSE_MAX_TOPK}, got {topk}")
+    max_pages, tstride = _mla_index_pool_checks(pool, block_table, scale, dev, B, num_pages, page_size)
+    _require(isinstance(Skv, int) and 1 <= Skv <= max_pages * page_size and Skv <= 2 ** 30, f"max_seqlen_k must be in 1 .. the capacity, got {Skv}")
+    _lens_check("seqused_k", seqused_k, B, dev)
+    L = lib()
+    own = return_logits or not select
+    logits = torch.empty((B, Sq, Skv) if own else (0,), dtype=torch.float32, device=dev)
+    indices = torch.empty((B, Sq, topk) if select else (0,), dtype=torch.int32, device=dev)
+    q8 = torch.empty((B, Hi, Sq, MLA_INDEX_D) if return_q8 else (0,), dtype=torch.uint8, device=dev)
+    sq = torch.empty((B, Hi, Sq) if return_q8 else (0,), dtype=torch.float32, device=dev)
+    wsb = 0 if own else L.qattn_fp8_mla_index_workspace_bytes(B, Sq, Skv)
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev) if wsb else None
+    dense = (Hi * Sq * MLA_INDEX_D, Sq * MLA_INDEX_D, MLA_INDEX_D)
+    s3 = None if q.is_contiguous() else (ctypes.c_longlong * 3)(*[q.stride(i) if q.shape[i] > 1 else dense[i] for i in (0, 1, 2)])
+    head = (q.data_ptr(), fmt_of(q.dtype), s3, weights.data_ptr(), _rows2(weights), pool.data_ptr(), block_table.data_ptr(), tstride, num_pages,
+            page_size, max_pages, scale.data_ptr(), seqused_k.data_ptr(), B, Hi, Sq, Skv)
+    q8p, sqp = (q8.data_ptr(), sq.data_ptr()) if return_q8 else (None, None)
+    with torch.cuda.device(dev):
+        if select:
+            rc = L.qattn_fp8_mla_index_topk(*head, topk, fmt_of(fp8_dtype), int(bool(is_causal)), indices.data_ptr(),
+                                            logits.data_ptr() if own else None, q8p, sqp, _ptr(ws), wsb, _stream(q))
+        else:
+            rc = L.qattn_fp8_mla_index_scores(*head, fmt_of(fp8_dtype), int(bool(is_causal)), logits.data_ptr(), None, 1, q8p, sqp, _stream(q))
+    _check(rc, "qattn_fp8_mla_index_topk" if select else "qattn_fp8_mla_index_scores")
+    return indices, logits, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq

@@ -1479,3 +1479,75 @@ def _(query, pool, scale_kv, block_table, seqused_k, indices, num_pages, page_si
     po, pl = (f32(n, B, Hq, Sq, 512), f32(n, B, Hq, Sq)) if n else (f32(0), f32(0))
     q8 = query.new_empty((B, Hq, Sq, D), dtype=torch.float8_e4m3fn) if return_q8 else query.new_empty((0,), dtype=torch.uint8)
     return query.new_empty((B, Hq, Sq, 512)), f32(B, Hq, Sq), po, pl, q8, (f32(B, Hq, Sq) if return_q8 else f32(0))
+
+
+@_custom_op("quantumattention_amd::fp8_paged_mla_index_cache_append_", mutates_args=("pool", "seqlens"), device_types=("cuda",))
+def fp8_paged_mla_index_cache_append_(
+    pool: torch.Tensor,
+    scale: torch.Tensor,
+    block_table: torch.Tensor,
+    seqlens: torch.Tensor,
+    k_new: torch.Tensor,
+    new_lens: Optional[torch.Tensor],
+    num_pages: int,
+    page_size: int,
+    fp8_format: str = "e4m3",
+    advance: bool = True,
+) -> None:
+    """Append to the paged FP8 index-key cache of the lightning indexer IN PLACE (include/qattn_mla_index.h): k_new [B, T, 128] through
+    block_table int32 [B, max_pages].  Reference implementation: mla_index._append_eager.  Arguments are validated by
+    mla_index.paged_mla_index_cache_append_fp8."""
+    _native.paged_mla_index_cache_append_fp8(pool, scale, block_table, seqlens, k_new, num_pages=num_pages, page_size=page_size,
+                                             fp8_dtype=_native.fp8_dtype_of(fp8_format), new_lens=new_lens, advance=advance)
+
+
+@_register_fake("quantumattention_amd::fp8_paged_mla_index_cache_append_")
+def _(pool, scale, block_table, seqlens, k_new, new_lens, num_pages, page_size, fp8_format="e4m3", advance=True):
+    return None
+
+
+@_custom_op("quantumattention_amd::fp8_mla_index_topk_forward", mutates_args=(), device_types=("cuda",))
+def fp8_mla_index_topk_forward(
+    query: torch.Tensor,
+    weights: torch.Tensor,
+    pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    seqlen_k: int,
+    topk: int,
+    num_pages: int,
+    page_size: int,
+    fp8_format: str = "e4m3",
+    is_causal: bool = True,
+    return_logits: bool = False,
+    return_q8: bool = False,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The lightning indexer (include/qattn_mla_index.h): index scores of query [B, Hi, Sq, 128] and weights [B, Sq, Hi] over the paged FP8
+    index-key cache, then the exact top-k selection.  Returns (indices int32 [B, Sq, topk], logits, q8, scale_q).  Reference
+    implementation: mla_index._scores_eager and mla_index._select_eager.  Arguments are validated by mla_index.fp8_mla_index_topk_func."""
+    return _native.fp8_mla_index_topk(query, weights, pool, scale_k, block_table, seqused_k, Skv=seqlen_k, topk=topk, num_pages=num_pages,
+                                      page_size=page_size, fp8_dtype=_native.fp8_dtype_of(fp8_format), is_causal=is_causal,
+                                      return_logits=return_logits, return_q8=return_q8)
+
+
+@_register_fake("quantumattention_amd::fp8_mla_index_topk_forward")
+def _(query, weights, pool, scale_k, block_table, seqused_k, seqlen_k, topk, num_pages, page_size, fp8_format="e4m3", is_causal=True,
+      return_logits=False, return_q8=False):
+    B, Hi, Sq, D = query.shape
+    f32 = lambda *shape: query.new_empty(shape, dtype=torch.float32)
+    q8 = query.new_empty((B, Hi, Sq, D), dtype=torch.float8_e4m3fn) if return_q8 else query.new_empty((0,), dtype=torch.uint8)
+    return (query.new_empty((B, Sq, topk), dtype=torch.int32), f32(B, Sq, seqlen_k) if return_logits else f32(0), q8,
+            f32(B, Hi, Sq) if return_q8 else f32(0))
+
+
+@_custom_op("quantumattention_amd::mla_index_select_forward", mutates_args=(), device_types=("cuda",))
+def mla_index_select_forward(logits: torch.Tensor, seqused_k: torch.Tensor, topk: int, is_causal: bool = True) -> torch.Tensor:
+    """The exact top-k selection of the lightning indexer alone (include/qattn_mla_index.h): logits fp32 [B, Sq, N] -> indices int32
+    [B, Sq, topk].  Reference implementation: mla_index._select_eager.  Arguments are validated by mla_index.mla_index_select."""
+    return _native.mla_index_select(logits, seqused_k, topk, is_causal=is_causal)
+
+
+@_register_fake("quantumattention_amd::mla_index_select_forward")
+def _(logits, seqused_k, topk, is_causal=True):
+    return logits.new_empty((logits.shape[0], logits.shape[1], topk), dtype=torch.int32)
