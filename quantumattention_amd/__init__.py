@@ -120,4 +120,5 @@ from .mla_index import (  # noqa: E402
     mla_index_input_reason,
     mla_index_select,
     paged_mla_index_cache_append_fp8,
+    select_splits_reason,
 )

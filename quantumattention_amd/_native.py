@@ -72,6 +72,8 @@ EXPORTS = (
     "qattn_paged_mla_row_cache_append_fp8", "qattn_fp8_mla_paged_sparse_forward",
     "qattn_mla_index_pool_bytes", "qattn_fp8_mla_index_workspace_bytes", "qattn_paged_mla_index_cache_append_fp8",
     "qattn_fp8_mla_index_scores", "qattn_mla_index_select", "qattn_fp8_mla_index_topk",
+    "qattn_mla_index_select_split_workspace_bytes", "qattn_mla_index_select_auto_splits", "qattn_mla_index_select_split",
+    "qattn_fp8_mla_index_topk_split_workspace_bytes", "qattn_fp8_mla_index_topk_split",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -83,6 +85,9 @@ MLA_SPARSE_SPLIT_ENTRIES = 2048                                      # QATTN_MLA
 MLA_SPARSE_MAX_TOPK = MLA_SPARSE_SPLIT_ENTRIES * MLA_MAX_SPLITS      # QATTN_MLA_SPARSE_MAX_TOPK
 MLA_INDEX_D, MLA_INDEX_MAX_HEADS = 128, 64                           # QATTN_MLA_INDEX_* (include/qattn_mla_index.h)
 MLA_INDEX_WG_KEYS, MLA_INDEX_LDS_CANDIDATES = 512, 8192
+MLA_INDEX_MAX_SELECT_SPLITS = 256                                    # QATTN_MLA_INDEX_MAX_SELECT_SPLITS (include/qattn_mla_index_split.h)
+MLA_INDEX_AUTO_MIN_SEG, MLA_INDEX_AUTO_MIN_KEYS = 2048, 16384         # QATTN_MLA_INDEX_AUTO_MIN_SEG, QATTN_MLA_INDEX_AUTO_MIN_KEYS
+MLA_INDEX_AUTO_MIN_SPLITS = 8                                         # QATTN_MLA_INDEX_AUTO_MIN_SPLITS
 
 
 class PathDesc(ctypes.Structure):
@@ -388,6 +393,17 @@ def lib() -> ctypes.CDLL:
     L.qattn_mla_index_select.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp]
     L.qattn_fp8_mla_index_topk.restype = i
     L.qattn_fp8_mla_index_topk.argtypes = [vp, i, vp, vp, vp, vp, vp, ll, i, i, i, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, sz, vp]
+    # ... and its selection with one row cut across workgroups (include/qattn_mla_index_split.h)
+    L.qattn_mla_index_select_split_workspace_bytes.restype = sz
+    L.qattn_mla_index_select_split_workspace_bytes.argtypes = [i, i, i, i]
+    L.qattn_mla_index_select_auto_splits.restype = i
+    L.qattn_mla_index_select_auto_splits.argtypes = [i, i, i, i]
+    L.qattn_mla_index_select_split.restype = i
+    L.qattn_mla_index_select_split.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp, vp, sz, vp]
+    L.qattn_fp8_mla_index_topk_split_workspace_bytes.restype = sz
+    L.qattn_fp8_mla_index_topk_split_workspace_bytes.argtypes = [i, i, i, i, i]
+    L.qattn_fp8_mla_index_topk_split.restype = i
+    L.qattn_fp8_mla_index_topk_split.argtypes = [vp, i, vp, vp, vp, vp, vp, ll, i, i, i, vp, vp, i, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -2107,10 +2123,52 @@ def mla_index_select(logits: torch.Tensor, seqused_k: torch.Tensor, topk: int, *
     return out
 
 
+def mla_index_select_auto_splits(rows: int, N: int, topk: int, num_cus: int) -> int:
+    """qattn_mla_index_select_auto_splits (include/qattn_mla_index_split.h): a pure function of the shape and the CU count (no device needed)."""
+    return lib().qattn_mla_index_select_auto_splits(rows, N, topk, num_cus)
+
+
+def mla_index_resolve_splits(num_splits, rows: int, N: int, topk: int, dev) -> int:
+    """The ONE place where num_splits / select_splits = 0 becomes a count: qattn_mla_index_select_auto_splits on the device's CU count.  Any
+    other value is returned as it is, checked.  The library's entries take the result, 1 .. 256; they reject 0."""
+    _require(isinstance(num_splits, int) and 0 <= num_splits <= MLA_INDEX_MAX_SELECT_SPLITS,
+             f"num_splits must be in 0 .. {MLA_INDEX_MAX_SELECT_SPLITS}, got {num_splits}")
+    return num_splits or mla_index_select_auto_splits(rows, N, topk, torch.cuda.get_device_properties(dev).multi_processor_count)
+
+
+def mla_index_select_split(logits: torch.Tensor, seqused_k: torch.Tensor, topk: int, *, is_causal: bool, num_splits: int = 0,
+                           workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qattn_mla_index_select_split (include/qattn_mla_index_split.h): `mla_index_select` with every row cut across num_splits workgroups
+    (0: resolved by mla_index_resolve_splits; 1: the one-workgroup kernel).  workspace: the caller's uint8 device tensor of at least
+    qattn_mla_index_select_split_workspace_bytes bytes, 16-byte aligned; its contents do not matter.  Default: allocated here."""
+    _require(logits.is_cuda and logits.dim() == 3 and logits.dtype == torch.float32 and logits.numel() > 0
+             and (logits.shape[2] == 1 or logits.stride(2) == 1) and all(logits.shape[i] == 1 or logits.stride(i) >= 0 for i in (0, 1)),
+             "logits must be a float32 device tensor [B, Sq, N] with a dense last dimension")
+    _require(isinstance(topk, int) and 1 <= topk <= MLA_SPARSE_MAX_TOPK, f"topk must be in 1 .. {MLA_SPARSE_MAX_TOPK}, got {topk}")
+    B, Sq, N = logits.shape
+    dev = logits.device
+    _lens_check("seqused_k", seqused_k, B, dev)
+    ns = mla_index_resolve_splits(num_splits, B * Sq, N, topk, dev)
+    _require(ns == 1 or (B <= 65535 and Sq <= 65535), "a split selection needs B, Sq <= 65535")
+    wsb = lib().qattn_mla_index_select_split_workspace_bytes(B, Sq, N, ns)
+    if workspace is None:
+        workspace = torch.empty((wsb,), dtype=torch.uint8, device=dev) if wsb else None
+    else:
+        _require(workspace.dtype == torch.uint8 and workspace.device == dev and workspace.is_contiguous() and workspace.numel() >= wsb
+                 and workspace.data_ptr() % 16 == 0, f"workspace must be a dense 16-byte-aligned uint8 tensor of at least {wsb} bytes on {dev}")
+    out = torch.empty((B, Sq, topk), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib().qattn_mla_index_select_split(logits.data_ptr(), _rows2(logits), seqused_k.data_ptr(), B, Sq, N, topk, int(bool(is_causal)),
+                                                ns, out.data_ptr(), _ptr(workspace), wsb, _stream(logits))
+    _check(rc, "qattn_mla_index_select_split")
+    return out
+
+
 def fp8_mla_index_topk(q: torch.Tensor, weights: torch.Tensor, pool: torch.Tensor, scale: torch.Tensor, block_table: torch.Tensor,
                        seqused_k: torch.Tensor, *, Skv: int, topk: int, num_pages: int, page_size: int, fp8_dtype=torch.float8_e4m3fn,
-                       is_causal: bool, return_logits: bool = False, return_q8: bool = False, select: bool = True):
-    """qattn_fp8_mla_index_topk (include/qattn_mla_index.h), or with select=False qattn_fp8_mla_index_scores alone (logits with a filled
+                       is_causal: bool, return_logits: bool = False, return_q8: bool = False, select: bool = True, select_splits: int = 1):
+    """qattn_fp8_mla_index_topk (include/qattn_mla_index.h), with select_splits != 1 qattn_fp8_mla_index_topk_split
+    (include/qattn_mla_index_split.h; 0: resolved by mla_index_resolve_splits), or with select=False qattn_fp8_mla_index_scores alone (logits with a filled
     tail).  Returns (indices int32 [B, Sq, topk], logits fp32 [B, Sq, Skv], q8 [B, Hi, Sq, 128] e4m3, scale_q [B, Hi, Sq]); what was not
     asked for (or not computed) is empty."""
     _require(q.is_cuda and q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[3] == MLA_INDEX_D
@@ -2131,7 +2189,8 @@ def fp8_mla_index_topk(q: torch.Tensor, weights: torch.Tensor, pool: torch.Tenso
     indices = torch.empty((B, Sq, topk) if select else (0,), dtype=torch.int32, device=dev)
     q8 = torch.empty((B, Hi, Sq, MLA_INDEX_D) if return_q8 else (0,), dtype=torch.uint8, device=dev)
     sq = torch.empty((B, Hi, Sq) if return_q8 else (0,), dtype=torch.float32, device=dev)
-    wsb = 0 if own else L.qattn_fp8_mla_index_workspace_bytes(B, Sq, Skv)
+    ns = mla_index_resolve_splits(select_splits, B * Sq, Skv, topk, dev) if select else 1
+    wsb = L.qattn_fp8_mla_index_topk_split_workspace_bytes(B, Sq, Skv, ns, int(own))
     ws = torch.empty((wsb,), dtype=torch.uint8, device=dev) if wsb else None
     dense = (Hi * Sq * MLA_INDEX_D, Sq * MLA_INDEX_D, MLA_INDEX_D)
     s3 = None if q.is_contiguous() else (ctypes.c_longlong * 3)(*[q.stride(i) if q.shape[i] > 1 else dense[i] for i in (0, 1, 2)])
@@ -2139,10 +2198,13 @@ def fp8_mla_index_topk(q: torch.Tensor, weights: torch.Tensor, pool: torch.Tenso
             page_size, max_pages, scale.data_ptr(), seqused_k.data_ptr(), B, Hi, Sq, Skv)
     q8p, sqp = (q8.data_ptr(), sq.data_ptr()) if return_q8 else (None, None)
     with torch.cuda.device(dev):
-        if select:
+        if select and ns > 1:
+            rc = L.qattn_fp8_mla_index_topk_split(*head, topk, fmt_of(fp8_dtype), int(bool(is_causal)), ns, indices.data_ptr(),
+                                                  logits.data_ptr() if own else None, q8p, sqp, _ptr(ws), wsb, _stream(q))
+        elif select:
             rc = L.qattn_fp8_mla_index_topk(*head, topk, fmt_of(fp8_dtype), int(bool(is_causal)), indices.data_ptr(),
                                             logits.data_ptr() if own else None, q8p, sqp, _ptr(ws), wsb, _stream(q))
         else:
             rc = L.qattn_fp8_mla_index_scores(*head, fmt_of(fp8_dtype), int(bool(is_causal)), logits.data_ptr(), None, 1, q8p, sqp, _stream(q))
-    _check(rc, "qattn_fp8_mla_index_topk" if select else "qattn_fp8_mla_index_scores")
+    _check(rc, ("qattn_fp8_mla_index_topk_split" if ns > 1 else "qattn_fp8_mla_index_topk") if select else "qattn_fp8_mla_index_scores")
     return indices, logits, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq

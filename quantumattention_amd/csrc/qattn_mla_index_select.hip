@@ -17,6 +17,7 @@
 //            atomics on the output.
 // LDS (bytes)  histogram 1 024 | candidates 32 768 | wave counts 128 | control 16.
 #include "qattn_fp8pv_sweep.h"
+#include "qattn_mla_index_select_dev.h"
 #include "../../include/qattn_mla_index.h"
 
 using namespace qattn;
@@ -32,25 +33,6 @@ struct IndexSelectArgs {
     int* out;        // [B, Sq, topk]
     int Sq, N, topk, causal;
 };
-
-__device__ __forceinline__ unsigned order_key(float f) {
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) u = 0xff800000u;   // a NaN ranks as -inf
-    if (u == 0x80000000u) u = 0u;                           // -0.0 equals +0.0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// one count per participating lane; the lanes that share the leading lane's digit go in with one atomic
-__device__ __forceinline__ void hist_add(unsigned* hist, bool on, unsigned digit, int lane) {
-    const unsigned long long act = __ballot(on);
-    if (act == 0ull) return;   // (wave-uniform)
-    const int first = __builtin_ctzll(act);
-    const unsigned d0 = (unsigned)__builtin_amdgcn_readlane((int)digit, first);
-    const bool same = on && digit == d0;
-    const unsigned long long m = __ballot(same);
-    if (lane == first) atomicAdd(&hist[d0], (unsigned)__builtin_popcountll(m));
-    if (on && !same) atomicAdd(&hist[digit], 1u);
-}
 
 // f(position, in range, key) for every position of [0, kend) in rounds of kSelThreads, kUnroll loads in flight; every thread calls f the
 // same number of times (f may vote)

@@ -13,8 +13,13 @@ query of a token and returns the `indices` that `fp8_mla_paged_sparse_func` (mla
     logit[b, i, j] = scale_k[b] sum_h w[b, i, h] scale_q[b, h, i] ReLU(sum_c q8[b, h, i, c] k8[b, j, c])          (no softmax)
     indices[b, i]  = the positions of the min(topk, kend) largest logits among j < kend(b, i), ASCENDING, then -1; ties to the lower position
 
+The selection of a row runs on one workgroup or, for few rows over many keys, cut across up to 256 workgroups (include/qattn_mla_index_split.h,
+DESIGN.md section 4.33): `select_splits=` / `num_splits=`, 0 = `qattn_mla_index_select_auto_splits` on the device's CU count, resolved on
+the host by `_native.mla_index_resolve_splits` (1 unless the row has 16 384 keys or more and B Sq is at most an eighth of the CU count; the
+ops and the library take the resolved count, 1 .. 256).  The indices are the same bit for bit for every value.
+
 Package attributes, not names of `__all__`.  Not offered: per-key cache scales (DeepSeek's own 132-byte index row); RoPE or the LayerNorm of
-the index key; packed variable-length q; a multi-workgroup selection."""
+the index key; packed variable-length q; the first selection histogram fused into the score sweep."""
 from typing import Optional, Tuple
 
 import torch
@@ -27,6 +32,7 @@ from .utils import checks
 
 D, MAX_HEADS, MAX_TOPK = _native.MLA_INDEX_D, _native.MLA_INDEX_MAX_HEADS, _native.MLA_SPARSE_MAX_TOPK
 WG_KEYS, LDS_CANDIDATES = _native.MLA_INDEX_WG_KEYS, _native.MLA_INDEX_LDS_CANDIDATES
+MAX_SELECT_SPLITS = _native.MLA_INDEX_MAX_SELECT_SPLITS
 
 
 class PagedMLAIndexCacheFP8(_mla.PagedMLACacheFP8):
@@ -72,7 +78,18 @@ def alloc_paged_mla_index_cache_fp8(num_pages: int, page_size: int, *, batch_siz
     return PagedMLAIndexCacheFP8(pool, sc, table, lens, num_pages, page_size, fp8_format, dtype, "index")
 
 
-def mla_index_input_reason(q, weights, icache, topk=None, *, seqused_k=None, max_seqlen_k=None, k_new=None, new_lens=None) -> Optional[str]:
+def select_splits_reason(name: str, value, B: int, Sq: int) -> Optional[str]:
+    """The rule a `num_splits` / `select_splits` value breaks, or None: an integer, 0 (the auto rule) .. MAX_SELECT_SPLITS; more than one
+    split needs B, Sq <= 65535 (grid axes)."""
+    if not (_is_int(value) and 0 <= value <= MAX_SELECT_SPLITS):
+        return f"{name} must be an integer in 0 .. {MAX_SELECT_SPLITS} (0: chosen from the shape), got {value!r}"
+    if value > 1 and (B > 65535 or Sq > 65535):
+        return f"{name} > 1 needs B, Sq <= 65535, got B {B}, Sq {Sq}"
+    return None
+
+
+def mla_index_input_reason(q, weights, icache, topk=None, *, seqused_k=None, max_seqlen_k=None, k_new=None, new_lens=None,
+                           select_splits=0) -> Optional[str]:
     """The first rule the arguments of `fp8_mla_index_topk_func` (q, weights, topk given) or `paged_mla_index_cache_append_fp8` (q None; k_new
     given) break, or None.  Shapes, dtypes, devices and strides only: the CONTENTS of block_table / seqlens are read on the device."""
     if not isinstance(icache, PagedMLAIndexCacheFP8):
@@ -122,6 +139,9 @@ def mla_index_input_reason(q, weights, icache, topk=None, *, seqused_k=None, max
         return f"max_seqlen_k must be None or an integer in 1 .. max_pages_per_seq * page_size = {icache.capacity} (at most 2^30), got {max_seqlen_k!r}"
     if max_seqlen_k is None and icache.capacity > 2 ** 30:
         return "max_seqlen_k is required for a capacity above 2^30 keys"
+    reason = select_splits_reason("select_splits", select_splits, B, Sq)
+    if reason:
+        return reason
     return _lens_reason("seqused_k" if seqused_k is not None else "icache.seqlens", icache.seqlens if seqused_k is None else seqused_k, B, q.device)
 
 
@@ -190,7 +210,7 @@ def paged_mla_index_cache_append_fp8(icache: PagedMLAIndexCacheFP8, k_new: Tenso
 
 def fp8_mla_index_topk_func(q_idx: Tensor, weights: Tensor, icache: PagedMLAIndexCacheFP8, topk: int, *, causal: bool = True,
                             seqused_k: Optional[Tensor] = None, max_seqlen_k: Optional[int] = None, return_logits: bool = False,
-                            return_q8: bool = False):
+                            return_q8: bool = False, select_splits: int = 0):
     """The lightning indexer: returns indices int32 [B, Sq, topk] for `fp8_mla_paged_sparse_func`.
 
     q_idx         [B, Hi <= 64, Sq, 128] in icache.dtype (a view with dense channels and 16-byte-aligned rows is read through its strides);
@@ -204,11 +224,14 @@ def fp8_mla_index_topk_func(q_idx: Tensor, weights: Tensor, icache: PagedMLAInde
     max_seqlen_k  a host int: bounds the grid and the logits row; default the capacity.  Pass the longest live sequence.
     return_logits appends logits fp32 [B, Sq, max_seqlen_k], -inf at j >= kend; return_q8 appends (q8 [B, Hi, Sq, 128] e4m3, scale_q
                   [B, Hi, Sq]).
-    Two launches (scores, selection); table, lengths, weights and q are read on the device: no host synchronisation, graph-capture safe.
+    select_splits 0: `qattn_mla_index_select_auto_splits` on the device's CU count; 1: one workgroup selects a row; 2 .. 256: the row is cut
+                  across that many workgroups (include/qattn_mla_index_split.h).  The indices are the same bit for bit.
+    The scores launch and the selection (one launch, or six with a split row), their number a function of the shapes alone; table, lengths,
+    weights and q are read on the device: no host synchronisation, graph-capture safe.
     CPU tensors and config.attention.force_eager_fallback run the eager definitions (`_scores_eager`, `_select_eager`); on the device there
     is no fallback.  Unsupported input raises ValueError(reason)."""
     if not checks.config_value("attention.skip_supported_check"):
-        reason = mla_index_input_reason(q_idx, weights, icache, topk, seqused_k=seqused_k, max_seqlen_k=max_seqlen_k)
+        reason = mla_index_input_reason(q_idx, weights, icache, topk, seqused_k=seqused_k, max_seqlen_k=max_seqlen_k, select_splits=select_splits)
         if reason:
             raise ValueError(reason)
     Skv = icache.capacity if max_seqlen_k is None else int(max_seqlen_k)
@@ -220,9 +243,15 @@ def fp8_mla_index_topk_func(q_idx: Tensor, weights: Tensor, icache: PagedMLAInde
         ok, why = nn._pre_check_can_use_hip_attention(device=q_idx.device)
         if not ok:
             raise ValueError(why)
-        indices, logits, q8, sq = nn._ops().fp8_mla_index_topk_forward(
-            q_idx, weights, icache.pool, icache.scale, icache.block_table, used, Skv, int(topk), icache.num_pages, icache.page_size,
-            icache.fp8_format, bool(causal), bool(return_logits), bool(return_q8))
+        ns = _native.mla_index_resolve_splits(int(select_splits), q_idx.shape[0] * q_idx.shape[2], Skv, int(topk), q_idx.device)
+        if ns == 1:
+            indices, logits, q8, sq = nn._ops().fp8_mla_index_topk_forward(
+                q_idx, weights, icache.pool, icache.scale, icache.block_table, used, Skv, int(topk), icache.num_pages, icache.page_size,
+                icache.fp8_format, bool(causal), bool(return_logits), bool(return_q8))
+        else:
+            indices, logits, q8, sq = nn._ops().fp8_mla_index_topk_split_forward(
+                q_idx, weights, icache.pool, icache.scale, icache.block_table, used, Skv, int(topk), icache.num_pages, icache.page_size, ns,
+                icache.fp8_format, bool(causal), bool(return_logits), bool(return_q8))
     res: Tuple = (indices,)
     if return_logits:
         res += (logits,)
@@ -231,10 +260,11 @@ def fp8_mla_index_topk_func(q_idx: Tensor, weights: Tensor, icache: PagedMLAInde
     return res if len(res) > 1 else indices
 
 
-def mla_index_select(logits: Tensor, topk: int, *, seqused_k: Tensor, causal: bool = True) -> Tensor:
+def mla_index_select(logits: Tensor, topk: int, *, seqused_k: Tensor, causal: bool = True, num_splits: int = 0) -> Tensor:
     """The selection of `fp8_mla_index_topk_func` alone, on the caller's logits fp32 [B, Sq, N] (last dimension dense): indices int32
-    [B, Sq, topk] by the same rule, with L_b = clamp(seqused_k[b], 0, N).  One launch, graph-capture safe; CPU tensors and
-    config.attention.force_eager_fallback run `_select_eager`."""
+    [B, Sq, topk] by the same rule, with L_b = clamp(seqused_k[b], 0, N).  num_splits: `select_splits` of that call -- one launch for 1,
+    six for a split row; the same indices bit for bit.  Graph-capture safe; CPU tensors and config.attention.force_eager_fallback run
+    `_select_eager` (num_splits is validated and ignored)."""
     if not checks.config_value("attention.skip_supported_check"):
         reason = None
         if not isinstance(logits, Tensor) or logits.dtype != torch.float32 or logits.dim() != 3 or logits.numel() == 0 or logits.requires_grad:
@@ -244,7 +274,7 @@ def mla_index_select(logits: Tensor, topk: int, *, seqused_k: Tensor, causal: bo
         elif not (_is_int(topk) and 1 <= topk <= MAX_TOPK):
             reason = f"topk must be an integer in 1 .. {MAX_TOPK}, got {topk!r}"
         else:
-            reason = _lens_reason("seqused_k", seqused_k, logits.shape[0], logits.device)
+            reason = _lens_reason("seqused_k", seqused_k, logits.shape[0], logits.device) or select_splits_reason("num_splits", num_splits, *logits.shape[:2])
         if reason:
             raise ValueError(reason)
     if _mla._eager(logits):
@@ -252,4 +282,7 @@ def mla_index_select(logits: Tensor, topk: int, *, seqused_k: Tensor, causal: bo
     ok, why = nn._pre_check_can_use_hip_attention(device=logits.device)
     if not ok:
         raise ValueError(why)
-    return nn._ops().mla_index_select_forward(logits, seqused_k, int(topk), bool(causal))
+    ns = _native.mla_index_resolve_splits(int(num_splits), logits.shape[0] * logits.shape[1], logits.shape[2], int(topk), logits.device)
+    if ns == 1:
+        return nn._ops().mla_index_select_forward(logits, seqused_k, int(topk), bool(causal))
+    return nn._ops().mla_index_select_split_forward(logits, seqused_k, int(topk), ns, bool(causal))

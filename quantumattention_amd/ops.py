@@ -1551,3 +1551,52 @@ def mla_index_select_forward(logits: torch.Tensor, seqused_k: torch.Tensor, topk
 @_register_fake("quantumattention_amd::mla_index_select_forward")
 def _(logits, seqused_k, topk, is_causal=True):
     return logits.new_empty((logits.shape[0], logits.shape[1], topk), dtype=torch.int32)
+
+
+@_custom_op("quantumattention_amd::fp8_mla_index_topk_split_forward", mutates_args=(), device_types=("cuda",))
+def fp8_mla_index_topk_split_forward(
+    query: torch.Tensor,
+    weights: torch.Tensor,
+    pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    seqlen_k: int,
+    topk: int,
+    num_pages: int,
+    page_size: int,
+    select_splits: int,
+    fp8_format: str = "e4m3",
+    is_causal: bool = True,
+    return_logits: bool = False,
+    return_q8: bool = False,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`fp8_mla_index_topk_forward` with the selection of every row cut across select_splits workgroups (include/qattn_mla_index_split.h;
+    1: the one-workgroup selection): the same four tensors, bit for bit.  mla_index.fp8_mla_index_topk_func validates the arguments and
+    passes a resolved count; a 0 here is resolved by _native.mla_index_resolve_splits like there."""
+    return _native.fp8_mla_index_topk(query, weights, pool, scale_k, block_table, seqused_k, Skv=seqlen_k, topk=topk, num_pages=num_pages,
+                                      page_size=page_size, fp8_dtype=_native.fp8_dtype_of(fp8_format), is_causal=is_causal,
+                                      return_logits=return_logits, return_q8=return_q8, select_splits=select_splits)
+
+
+@_register_fake("quantumattention_amd::fp8_mla_index_topk_split_forward")
+def _(query, weights, pool, scale_k, block_table, seqused_k, seqlen_k, topk, num_pages, page_size, select_splits, fp8_format="e4m3",
+      is_causal=True, return_logits=False, return_q8=False):
+    B, Hi, Sq, D = query.shape
+    f32 = lambda *shape: query.new_empty(shape, dtype=torch.float32)
+    q8 = query.new_empty((B, Hi, Sq, D), dtype=torch.float8_e4m3fn) if return_q8 else query.new_empty((0,), dtype=torch.uint8)
+    return (query.new_empty((B, Sq, topk), dtype=torch.int32), f32(B, Sq, seqlen_k) if return_logits else f32(0), q8,
+            f32(B, Hi, Sq) if return_q8 else f32(0))
+
+
+@_custom_op("quantumattention_amd::mla_index_select_split_forward", mutates_args=(), device_types=("cuda",))
+def mla_index_select_split_forward(logits: torch.Tensor, seqused_k: torch.Tensor, topk: int, num_splits: int, is_causal: bool = True) -> torch.Tensor:
+    """`mla_index_select_forward` with every row cut across num_splits workgroups (include/qattn_mla_index_split.h; 1: the one-workgroup
+    selection): the same indices, bit for bit.  mla_index.mla_index_select validates the arguments and passes a resolved count; a 0 here
+    is resolved by _native.mla_index_resolve_splits like there."""
+    return _native.mla_index_select_split(logits, seqused_k, topk, is_causal=is_causal, num_splits=num_splits)
+
+
+@_register_fake("quantumattention_amd::mla_index_select_split_forward")
+def _(logits, seqused_k, topk, num_splits, is_causal=True):
+    return logits.new_empty((logits.shape[0], logits.shape[1], topk), dtype=torch.int32)
