@@ -122,3 +122,6 @@ from .mla_index import (  # noqa: E402
     paged_mla_index_cache_append_fp8,
     select_splits_reason,
 )
+# ... and the NON-ABSORBED prefill form on packed sequences, head dims 192 / 128 with the rotary slice of K shared by all heads
+# (include/qattn_mla_prefill.h): package attributes, not in __all__
+from .mla_prefill import fp8_mla_prefill_varlen_func, mla_prefill_input_reason  # noqa: E402

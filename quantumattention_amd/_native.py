@@ -74,6 +74,7 @@ EXPORTS = (
     "qattn_fp8_mla_index_scores", "qattn_mla_index_select", "qattn_fp8_mla_index_topk",
     "qattn_mla_index_select_split_workspace_bytes", "qattn_mla_index_select_auto_splits", "qattn_mla_index_select_split",
     "qattn_fp8_mla_index_topk_split_workspace_bytes", "qattn_fp8_mla_index_topk_split",
+    "qattn_fp8_mla_prefill_varlen_workspace_bytes", "qattn_fp8_mla_prefill_varlen_forward",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -88,6 +89,7 @@ MLA_INDEX_WG_KEYS, MLA_INDEX_LDS_CANDIDATES = 512, 8192
 MLA_INDEX_MAX_SELECT_SPLITS = 256                                    # QATTN_MLA_INDEX_MAX_SELECT_SPLITS (include/qattn_mla_index_split.h)
 MLA_INDEX_AUTO_MIN_SEG, MLA_INDEX_AUTO_MIN_KEYS = 2048, 16384         # QATTN_MLA_INDEX_AUTO_MIN_SEG, QATTN_MLA_INDEX_AUTO_MIN_KEYS
 MLA_INDEX_AUTO_MIN_SPLITS = 8                                         # QATTN_MLA_INDEX_AUTO_MIN_SPLITS
+MLA_PREFILL_D_QK, MLA_PREFILL_D_NOPE, MLA_PREFILL_D_ROPE, MLA_PREFILL_D_V = 192, 128, 64, 128   # QATTN_MLA_PREFILL_* (include/qattn_mla_prefill.h)
 
 
 class PathDesc(ctypes.Structure):
@@ -404,6 +406,11 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_mla_index_topk_split_workspace_bytes.argtypes = [i, i, i, i, i]
     L.qattn_fp8_mla_index_topk_split.restype = i
     L.qattn_fp8_mla_index_topk_split.argtypes = [vp, i, vp, vp, vp, vp, vp, ll, i, i, i, vp, vp, i, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, sz, vp]
+    # the non-absorbed prefill form of multi-head latent attention on packed sequences (include/qattn_mla_prefill.h)
+    L.qattn_fp8_mla_prefill_varlen_workspace_bytes.restype = sz
+    L.qattn_fp8_mla_prefill_varlen_workspace_bytes.argtypes = [i, i, i, i]
+    L.qattn_fp8_mla_prefill_varlen_forward.restype = i
+    L.qattn_fp8_mla_prefill_varlen_forward.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, vp, vp, vp, vp, sz, vp]
     if L.qattn_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libqattn_hip.so ABI {L.qattn_abi_version()} != expected {ABI_VERSION}; rebuild it")
     _lib = L
@@ -2208,3 +2215,47 @@ def fp8_mla_index_topk(q: torch.Tensor, weights: torch.Tensor, pool: torch.Tenso
             rc = L.qattn_fp8_mla_index_scores(*head, fmt_of(fp8_dtype), int(bool(is_causal)), logits.data_ptr(), None, 1, q8p, sqp, _stream(q))
     _check(rc, ("qattn_fp8_mla_index_topk_split" if ns > 1 else "qattn_fp8_mla_index_topk") if select else "qattn_fp8_mla_index_scores")
     return indices, logits, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq
+
+
+def fp8_mla_prefill_varlen(q: torch.Tensor, k_nope: torch.Tensor, k_pe: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor,
+                           cu_seqlens_k: torch.Tensor, seqused_k: Optional[torch.Tensor] = None, *, is_causal: bool, sm_scale: float,
+                           fp8_dtype=torch.float8_e4m3fn, return_quantized: bool = False):
+    """qattn_fp8_mla_prefill_varlen_forward (include/qattn_mla_prefill.h): q [total_q, H, 192], k_nope / v [total_k, H, 128], k_pe [total_k, 64]
+    (views that `mla_rows_addressable` accepts, read in place), int32 tables on the device.  Returns (out [total_q, H, 128], lse fp32
+    [H, total_q], q8 [total_q, H, 192] e4m3, scale_q [total_q, H], scale_k [B, H], scale_v [B, H]); the last four are empty unless
+    return_quantized (then zero-filled where no sequence has a token)."""
+    _require(q.is_cuda and q.dim() == 3 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[2] == MLA_PREFILL_D_QK and q.shape[1] > 0,
+             f"q must be a bf16 / fp16 device tensor [total_q, H, {MLA_PREFILL_D_QK}]")
+    total_q, H, _ = q.shape
+    total_k = k_nope.shape[0]
+    for name, t, shape in (("k_nope", k_nope, (total_k, H, MLA_PREFILL_D_NOPE)), ("k_pe", k_pe, (total_k, MLA_PREFILL_D_ROPE)),
+                           ("v", v, (total_k, H, MLA_PREFILL_D_V))):
+        _require(tuple(t.shape) == shape and t.dtype == q.dtype and t.device == q.device, f"{name} must be {list(shape)} in q's dtype on q's device")
+    _require(all(mla_rows_addressable(t) for t in (q, k_nope, k_pe, v)), "q / k_nope / k_pe / v need dense channels and 16-byte-aligned rows")
+    B = cu_seqlens_q.shape[0] - 1
+    dev = q.device
+    for name, t, n in (("cu_seqlens_q", cu_seqlens_q, B + 1), ("cu_seqlens_k", cu_seqlens_k, B + 1), ("seqused_k", seqused_k, B)):
+        _require((t is None and name == "seqused_k") or (t is not None and B >= 1 and t.dtype == torch.int32 and t.device == dev
+                                                          and tuple(t.shape) == (n,) and t.is_contiguous()),
+                 f"{name} must be a dense int32 [{n}] tensor on {dev}")
+    dense = ((H * MLA_PREFILL_D_QK, MLA_PREFILL_D_QK), (H * MLA_PREFILL_D_NOPE, MLA_PREFILL_D_NOPE), (MLA_PREFILL_D_ROPE,),
+             (H * MLA_PREFILL_D_V, MLA_PREFILL_D_V))     # (a dimension of size 1 has no stride of its own)
+    strides = (ctypes.c_longlong * 7)(*[t.stride(i) if t.shape[i] > 1 else d[i] for t, d in zip((q, k_nope, k_pe, v), dense) for i in range(len(d))])
+    L = lib()
+    with torch.cuda.device(dev):
+        out = torch.empty((total_q, H, MLA_PREFILL_D_V), dtype=q.dtype, device=dev)
+        lse = torch.empty((H, total_q), dtype=torch.float32, device=dev)
+        rq = bool(return_quantized)
+        q8 = torch.zeros((total_q, H, MLA_PREFILL_D_QK) if rq else (0,), dtype=torch.uint8, device=dev)
+        sq = torch.zeros((total_q, H) if rq else (0,), dtype=torch.float32, device=dev)
+        sk, sv = (torch.zeros((B, H) if rq else (0,), dtype=torch.float32, device=dev) for _ in range(2))
+        wsb = L.qattn_fp8_mla_prefill_varlen_workspace_bytes(B, H, total_q, total_k)
+        _require(wsb > 0, f"unsupported extents B={B}, H={H}, total_q={total_q}, total_k={total_k}")
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+        rc = L.qattn_fp8_mla_prefill_varlen_forward(
+            q.data_ptr(), k_nope.data_ptr(), k_pe.data_ptr(), v.data_ptr(), strides, fmt_of(q.dtype), out.data_ptr(), lse.data_ptr(),
+            cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), _ptr(seqused_k), B, H, total_q, total_k, fmt_of(fp8_dtype), int(bool(is_causal)),
+            float(sm_scale), *((q8.data_ptr(), sq.data_ptr(), sk.data_ptr(), sv.data_ptr()) if rq else (None,) * 4), ws.data_ptr(), wsb,
+            _stream(q))
+    _check(rc, "qattn_fp8_mla_prefill_varlen_forward")
+    return out, lse, (q8.view(torch.float8_e4m3fn) if rq else q8), sq, sk, sv

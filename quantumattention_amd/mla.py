@@ -17,8 +17,9 @@ a constant and q_pe by its inverse.  `scale` of the attention call is REQUIRED: 
 YaRN factor), never 1/sqrt(576).  q is quantised inside the kernel, token-wise, always to e4m3.  Table, lengths and clamping: paged.py.
 
 Package attributes, not names of `__all__`.  Not offered: packed variable-length q; windows, sinks, soft cap or trees on MLA; RoPE inside the
-append; the non-absorbed prefill form (ordinary MHA at D 192 / 128); precision "fast" / "auto"; per-token cache scales.  (The indexer of
-DeepSeek-V3.2's sparse attention -- its scores and the top-k selection -- is mla_index.py; the attention over the selected keys is below.)
+append; precision "fast" / "auto"; per-token cache scales.  (The indexer of DeepSeek-V3.2's sparse attention -- its scores and the top-k
+selection -- is mla_index.py; the attention over the selected keys is below.  The non-absorbed prefill form -- ordinary MHA at D 192 / 128 --
+is mla_prefill.py)
 
 SPARSE (top-k indexed) decode, the attention of DeepSeek-V3.2-style layers (include/qattn_mla_sparse.h):
 `alloc_paged_mla_row_cache_fp8`, `paged_mla_row_cache_append_fp8`, `fp8_mla_paged_sparse_func`.  The cache is ROW-MAJOR -- a key is one

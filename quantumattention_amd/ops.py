@@ -1600,3 +1600,35 @@ def mla_index_select_split_forward(logits: torch.Tensor, seqused_k: torch.Tensor
 @_register_fake("quantumattention_amd::mla_index_select_split_forward")
 def _(logits, seqused_k, topk, num_splits, is_causal=True):
     return logits.new_empty((logits.shape[0], logits.shape[1], topk), dtype=torch.int32)
+
+
+@_custom_op("quantumattention_amd::fp8_mla_prefill_varlen_forward", mutates_args=(), device_types=("cuda",))
+def fp8_mla_prefill_varlen_forward(
+    query: torch.Tensor,
+    k_nope: torch.Tensor,
+    k_pe: torch.Tensor,
+    value: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    cu_seqlens_k: torch.Tensor,
+    seqused_k: Optional[torch.Tensor],
+    scale: float,
+    fp8_format: str = "e4m3",
+    is_causal: bool = True,
+    return_quantized: bool = False,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The non-absorbed prefill form of multi-head latent attention on packed sequences (include/qattn_mla_prefill.h): query
+    [total_q, H, 192], k_nope / value [total_k, H, 128], k_pe [total_k, 64] shared by all heads; bottom-right causal.  Returns (out
+    [total_q, H, 128], lse [H, total_q], q8, scale_q, scale_k, scale_v).  Reference implementation: mla_prefill._prefill_eager.  Arguments
+    are validated by mla_prefill.fp8_mla_prefill_varlen_func."""
+    return _native.fp8_mla_prefill_varlen(query, k_nope, k_pe, value, cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous(),
+                                          None if seqused_k is None else seqused_k.contiguous(), is_causal=is_causal, sm_scale=scale,
+                                          fp8_dtype=_native.fp8_dtype_of(fp8_format), return_quantized=return_quantized)
+
+
+@_register_fake("quantumattention_amd::fp8_mla_prefill_varlen_forward")
+def _(query, k_nope, k_pe, value, cu_seqlens_q, cu_seqlens_k, seqused_k, scale, fp8_format="e4m3", is_causal=True, return_quantized=False):
+    total_q, H, D = query.shape
+    B = cu_seqlens_q.shape[0] - 1
+    f32 = lambda *shape: query.new_empty(shape if return_quantized else (0,), dtype=torch.float32)
+    q8 = query.new_empty((total_q, H, D), dtype=torch.float8_e4m3fn) if return_quantized else query.new_empty((0,), dtype=torch.uint8)
+    return query.new_empty((total_q, H, value.shape[2])), query.new_empty((H, total_q), dtype=torch.float32), q8, f32(total_q, H), f32(B, H), f32(B, H)
