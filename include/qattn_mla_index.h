@@ -51,8 +51,8 @@
  * non-negative (q, k: multiples of 8); workspace_bytes large enough; formats: QATTN_ERR_UNSUPPORTED_FMT.
  *
  * Not offered: per-key cache scales (DeepSeek's own 132-byte index row: 128 fp8 bytes + an fp32 scale); RoPE or the LayerNorm of the index
- * key (the caller applies them before the append); packed variable-length q.  (A selection that cuts a row across workgroups -- few rows over
- * many keys: at B Sq = 1 one CU selects here -- is include/qattn_mla_index_split.h.)
+ * key (the caller applies them before the append).  (A selection that cuts a row across workgroups -- few rows over many keys: at B Sq = 1
+ * one CU selects here -- is include/qattn_mla_index_split.h; packed variable-length q -- a prompt -- is include/qattn_mla_index_prefill.h.)
  */
 #ifndef QATTN_MLA_INDEX_H_
 #define QATTN_MLA_INDEX_H_

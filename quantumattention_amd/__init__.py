@@ -125,3 +125,6 @@ from .mla_index import (  # noqa: E402
 # ... and the NON-ABSORBED prefill form on packed sequences, head dims 192 / 128 with the rotary slice of K shared by all heads
 # (include/qattn_mla_prefill.h): package attributes, not in __all__
 from .mla_prefill import fp8_mla_prefill_varlen_func, mla_prefill_input_reason  # noqa: E402
+# ... and the lightning indexer on packed variable-length queries, the prompt's form (include/qattn_mla_index_prefill.h): package attributes,
+# not in __all__
+from .mla_index_prefill import fp8_mla_index_topk_varlen_func, mla_index_varlen_input_reason  # noqa: E402

@@ -75,6 +75,7 @@ EXPORTS = (
     "qattn_mla_index_select_split_workspace_bytes", "qattn_mla_index_select_auto_splits", "qattn_mla_index_select_split",
     "qattn_fp8_mla_index_topk_split_workspace_bytes", "qattn_fp8_mla_index_topk_split",
     "qattn_fp8_mla_prefill_varlen_workspace_bytes", "qattn_fp8_mla_prefill_varlen_forward",
+    "qattn_fp8_mla_index_varlen_workspace_bytes", "qattn_fp8_mla_index_scores_varlen", "qattn_fp8_mla_index_topk_varlen",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -89,6 +90,7 @@ MLA_INDEX_WG_KEYS, MLA_INDEX_LDS_CANDIDATES = 512, 8192
 MLA_INDEX_MAX_SELECT_SPLITS = 256                                    # QATTN_MLA_INDEX_MAX_SELECT_SPLITS (include/qattn_mla_index_split.h)
 MLA_INDEX_AUTO_MIN_SEG, MLA_INDEX_AUTO_MIN_KEYS = 2048, 16384         # QATTN_MLA_INDEX_AUTO_MIN_SEG, QATTN_MLA_INDEX_AUTO_MIN_KEYS
 MLA_INDEX_AUTO_MIN_SPLITS = 8                                         # QATTN_MLA_INDEX_AUTO_MIN_SPLITS
+MLA_INDEX_PREFILL_TOKENS, MLA_INDEX_PREFILL_KEYS, MLA_INDEX_PREFILL_WG_KEYS = 8, 128, 2048   # QATTN_MLA_INDEX_PREFILL_* (include/qattn_mla_index_prefill.h)
 MLA_PREFILL_D_QK, MLA_PREFILL_D_NOPE, MLA_PREFILL_D_ROPE, MLA_PREFILL_D_V = 192, 128, 64, 128   # QATTN_MLA_PREFILL_* (include/qattn_mla_prefill.h)
 
 
@@ -395,6 +397,13 @@ def lib() -> ctypes.CDLL:
     L.qattn_mla_index_select.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp]
     L.qattn_fp8_mla_index_topk.restype = i
     L.qattn_fp8_mla_index_topk.argtypes = [vp, i, vp, vp, vp, vp, vp, ll, i, i, i, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, sz, vp]
+    # ... its packed variable-length (prefill) form (include/qattn_mla_index_prefill.h)
+    L.qattn_fp8_mla_index_varlen_workspace_bytes.restype = sz
+    L.qattn_fp8_mla_index_varlen_workspace_bytes.argtypes = [i, i]
+    L.qattn_fp8_mla_index_scores_varlen.restype = i
+    L.qattn_fp8_mla_index_scores_varlen.argtypes = [vp, i, vp, vp, ll, vp, vp, ll, i, i, i, vp, vp, vp, i, i, i, i, i, i, vp, ll, i, vp, vp, vp, vp]
+    L.qattn_fp8_mla_index_topk_varlen.restype = i
+    L.qattn_fp8_mla_index_topk_varlen.argtypes = [vp, i, vp, vp, ll, vp, vp, ll, i, i, i, vp, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, sz, vp]
     # ... and its selection with one row cut across workgroups (include/qattn_mla_index_split.h)
     L.qattn_mla_index_select_split_workspace_bytes.restype = sz
     L.qattn_mla_index_select_split_workspace_bytes.argtypes = [i, i, i, i]
@@ -2215,6 +2224,53 @@ def fp8_mla_index_topk(q: torch.Tensor, weights: torch.Tensor, pool: torch.Tenso
             rc = L.qattn_fp8_mla_index_scores(*head, fmt_of(fp8_dtype), int(bool(is_causal)), logits.data_ptr(), None, 1, q8p, sqp, _stream(q))
     _check(rc, ("qattn_fp8_mla_index_topk_split" if ns > 1 else "qattn_fp8_mla_index_topk") if select else "qattn_fp8_mla_index_scores")
     return indices, logits, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq
+
+
+def fp8_mla_index_topk_varlen(q: torch.Tensor, weights: torch.Tensor, pool: torch.Tensor, scale: torch.Tensor, block_table: torch.Tensor,
+                              cu_seqlens_q: torch.Tensor, seqused_k: torch.Tensor, *, Skv: int, topk: int, num_pages: int, page_size: int,
+                              fp8_dtype=torch.float8_e4m3fn, is_causal: bool, return_logits: bool = False, return_q8: bool = False,
+                              select: bool = True):
+    """qattn_fp8_mla_index_topk_varlen (include/qattn_mla_index_prefill.h), or with select=False qattn_fp8_mla_index_scores_varlen alone
+    (logits with a filled tail): q [total_q, Hi, 128] (a view `mla_rows_addressable` accepts), weights fp32 [total_q, Hi], cu_seqlens_q
+    int32 [B + 1] read on the device.  Returns (indices int32 [total_q, topk], logits fp32 [total_q, Skv], q8 [total_q, Hi, 128] e4m3,
+    scale_q [total_q, Hi], kend int32 [total_q]); what was not asked for (or not computed) is empty."""
+    _require(q.is_cuda and q.dim() == 3 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[2] == MLA_INDEX_D and q.shape[0] > 0
+             and 1 <= q.shape[1] <= MLA_INDEX_MAX_HEADS, f"q must be a bf16 / fp16 device tensor [total_q >= 1, Hi <= {MLA_INDEX_MAX_HEADS}, {MLA_INDEX_D}]")
+    _require(mla_rows_addressable(q), "q needs dense channels and 16-byte-aligned rows")
+    total_q, Hi, _ = q.shape
+    dev, B = q.device, block_table.shape[0]
+    _require(weights.dtype == torch.float32 and weights.device == dev and tuple(weights.shape) == (total_q, Hi)
+             and (Hi == 1 or weights.stride(1) == 1) and (total_q == 1 or weights.stride(0) > 0),
+             f"weights must be a float32 [total_q={total_q}, Hi={Hi}] tensor on {dev} with dense heads")
+    _require(isinstance(topk, int) and 1 <= topk <= MLA_SPARSE_MAX_TOPK, f"topk must be in 1 .. {MLA_SPARSE_MAX_TOPK}, got {topk}")
+    max_pages, tstride = _mla_index_pool_checks(pool, block_table, scale, dev, B, num_pages, page_size)
+    _require(isinstance(Skv, int) and 1 <= Skv <= max_pages * page_size and Skv <= 2 ** 30, f"max_seqlen_k must be in 1 .. the capacity, got {Skv}")
+    _lens_check("seqused_k", seqused_k, B, dev)
+    _require(cu_seqlens_q.dtype == torch.int32 and cu_seqlens_q.device == dev and tuple(cu_seqlens_q.shape) == (B + 1,) and cu_seqlens_q.is_contiguous(),
+             f"cu_seqlens_q must be a dense int32 [B + 1 = {B + 1}] tensor on {dev}")
+    L = lib()
+    own = return_logits or not select
+    logits = torch.empty((total_q, Skv) if own else (0,), dtype=torch.float32, device=dev)
+    indices = torch.empty((total_q, topk) if select else (0,), dtype=torch.int32, device=dev)
+    q8 = torch.empty((total_q, Hi, MLA_INDEX_D) if return_q8 else (0,), dtype=torch.uint8, device=dev)
+    sq = torch.empty((total_q, Hi) if return_q8 else (0,), dtype=torch.float32, device=dev)
+    kend_bytes = (4 * total_q + 255) // 256 * 256
+    wsb = kend_bytes if own else L.qattn_fp8_mla_index_varlen_workspace_bytes(total_q, Skv)
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    kend = ws[: 4 * total_q].view(torch.int32)
+    s2 = None if q.is_contiguous() else (ctypes.c_longlong * 2)(*[q.stride(i) if q.shape[i] > 1 else (Hi * MLA_INDEX_D, MLA_INDEX_D)[i] for i in (0, 1)])
+    head = (q.data_ptr(), fmt_of(q.dtype), s2, weights.data_ptr(), weights.stride(0) if total_q > 1 else Hi, pool.data_ptr(), block_table.data_ptr(),
+            tstride, num_pages, page_size, max_pages, scale.data_ptr(), cu_seqlens_q.data_ptr(), seqused_k.data_ptr(), B, Hi, total_q, Skv)
+    q8p, sqp = (q8.data_ptr(), sq.data_ptr()) if return_q8 else (None, None)
+    with torch.cuda.device(dev):
+        if select:
+            rc = L.qattn_fp8_mla_index_topk_varlen(*head, topk, fmt_of(fp8_dtype), int(bool(is_causal)), indices.data_ptr(),
+                                                   logits.data_ptr() if own else None, q8p, sqp, ws.data_ptr(), wsb, _stream(q))
+        else:
+            rc = L.qattn_fp8_mla_index_scores_varlen(*head, fmt_of(fp8_dtype), int(bool(is_causal)), logits.data_ptr(), 0, 1, kend.data_ptr(), q8p, sqp,
+                                                     _stream(q))
+    _check(rc, "qattn_fp8_mla_index_topk_varlen" if select else "qattn_fp8_mla_index_scores_varlen")
+    return indices, logits, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq, kend
 
 
 def fp8_mla_prefill_varlen(q: torch.Tensor, k_nope: torch.Tensor, k_pe: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor,

@@ -19,7 +19,8 @@ the host by `_native.mla_index_resolve_splits` (1 unless the row has 16 384 keys
 ops and the library take the resolved count, 1 .. 256).  The indices are the same bit for bit for every value.
 
 Package attributes, not names of `__all__`.  Not offered: per-key cache scales (DeepSeek's own 132-byte index row); RoPE or the LayerNorm of
-the index key; packed variable-length q; the first selection histogram fused into the score sweep."""
+the index key; the first selection histogram fused into the score sweep.  (Packed variable-length q -- a prompt -- is
+`fp8_mla_index_topk_varlen_func`, mla_index_prefill.py.)"""
 from typing import Optional, Tuple
 
 import torch

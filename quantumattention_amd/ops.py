@@ -1602,6 +1602,44 @@ def _(logits, seqused_k, topk, num_splits, is_causal=True):
     return logits.new_empty((logits.shape[0], logits.shape[1], topk), dtype=torch.int32)
 
 
+@_custom_op("quantumattention_amd::fp8_mla_index_topk_varlen_forward", mutates_args=(), device_types=("cuda",))
+def fp8_mla_index_topk_varlen_forward(
+    query: torch.Tensor,
+    weights: torch.Tensor,
+    pool: torch.Tensor,
+    scale_k: torch.Tensor,
+    block_table: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    seqused_k: torch.Tensor,
+    seqlen_k: int,
+    topk: int,
+    num_pages: int,
+    page_size: int,
+    fp8_format: str = "e4m3",
+    is_causal: bool = True,
+    return_logits: bool = False,
+    return_q8: bool = False,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The lightning indexer on packed variable-length queries (include/qattn_mla_index_prefill.h): query [total_q, Hi, 128], weights
+    [total_q, Hi], slot b's tokens cu_seqlens_q[b] .. cu_seqlens_q[b+1] over its own cached keys.  Returns (indices int32 [total_q, topk],
+    logits, q8, scale_q).  Reference implementation: mla_index_prefill._varlen_eager.  Arguments are validated by
+    mla_index_prefill.fp8_mla_index_topk_varlen_func."""
+    return _native.fp8_mla_index_topk_varlen(query, weights, pool, scale_k, block_table, cu_seqlens_q.contiguous(), seqused_k.contiguous(),
+                                             Skv=seqlen_k, topk=topk, num_pages=num_pages, page_size=page_size,
+                                             fp8_dtype=_native.fp8_dtype_of(fp8_format), is_causal=is_causal, return_logits=return_logits,
+                                             return_q8=return_q8)[:4]
+
+
+@_register_fake("quantumattention_amd::fp8_mla_index_topk_varlen_forward")
+def _(query, weights, pool, scale_k, block_table, cu_seqlens_q, seqused_k, seqlen_k, topk, num_pages, page_size, fp8_format="e4m3",
+      is_causal=True, return_logits=False, return_q8=False):
+    total_q, Hi, D = query.shape
+    f32 = lambda *shape: query.new_empty(shape, dtype=torch.float32)
+    q8 = query.new_empty((total_q, Hi, D), dtype=torch.float8_e4m3fn) if return_q8 else query.new_empty((0,), dtype=torch.uint8)
+    return (query.new_empty((total_q, topk), dtype=torch.int32), f32(total_q, seqlen_k) if return_logits else f32(0), q8,
+            f32(total_q, Hi) if return_q8 else f32(0))
+
+
 @_custom_op("quantumattention_amd::fp8_mla_prefill_varlen_forward", mutates_args=(), device_types=("cuda",))
 def fp8_mla_prefill_varlen_forward(
     query: torch.Tensor,
