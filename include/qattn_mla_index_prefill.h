@@ -40,8 +40,8 @@
  * limits; table_stride >= max_pages; pointers non-NULL (q8, scale_q, logits of the topk entry excepted) and aligned (pool, q16, q8, workspace:
  * 16 bytes; the others: 4); strides non-negative (q: multiples of 8); workspace_bytes large enough; formats: QATTN_ERR_UNSUPPORTED_FMT.
  *
- * Not offered: packed q for qattn_fp8_mla_paged_sparse_forward (a prompt's indices[cu[b] .. cu[b+1]) feed that call per sequence, or directly
- * at B = 1); the selection's first histogram fused into the sweep; per-key index scales.
+ * (Packed q for the sparse attention over these lists: include/qattn_mla_sparse_prefill.h takes the indices tensor as it is.)
+ * Not offered: the selection's first histogram fused into the sweep; per-key index scales.
  */
 #ifndef QATTN_MLA_INDEX_PREFILL_H_
 #define QATTN_MLA_INDEX_PREFILL_H_

@@ -45,7 +45,7 @@
  * num_splits = 0 or ceil(topk / 2048) <= num_splits <= QATTN_MLA_MAX_SPLITS; sm_scale > 0 and finite; workspace_bytes large enough;
  * formats: QATTN_ERR_UNSUPPORTED_FMT.
  *
- * Not offered: dense attention over the row cache (the indexer: include/qattn_mla_index.h); physical (pre-resolved) indices; packed variable-length q;
+ * Not offered: dense attention over the row cache (the indexer: include/qattn_mla_index.h); physical (pre-resolved) indices; (packed variable-length q: include/qattn_mla_sparse_prefill.h);
  * per-token cache scales or a 656-byte row with 16-bit RoPE channels; windows, sinks, soft cap or trees on MLA.
  */
 #ifndef QATTN_MLA_SPARSE_H_

@@ -128,3 +128,6 @@ from .mla_prefill import fp8_mla_prefill_varlen_func, mla_prefill_input_reason  
 # ... and the lightning indexer on packed variable-length queries, the prompt's form (include/qattn_mla_index_prefill.h): package attributes,
 # not in __all__
 from .mla_index_prefill import fp8_mla_index_topk_varlen_func, mla_index_varlen_input_reason  # noqa: E402
+# ... and the sparse attention over those packed lists, one workgroup per token and 128 heads (include/qattn_mla_sparse_prefill.h): package
+# attributes, not in __all__
+from .mla_sparse_prefill import fp8_mla_paged_sparse_varlen_func, mla_sparse_varlen_input_reason  # noqa: E402

@@ -76,6 +76,7 @@ EXPORTS = (
     "qattn_fp8_mla_index_topk_split_workspace_bytes", "qattn_fp8_mla_index_topk_split",
     "qattn_fp8_mla_prefill_varlen_workspace_bytes", "qattn_fp8_mla_prefill_varlen_forward",
     "qattn_fp8_mla_index_varlen_workspace_bytes", "qattn_fp8_mla_index_scores_varlen", "qattn_fp8_mla_index_topk_varlen",
+    "qattn_fp8_mla_paged_sparse_varlen_forward",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -85,6 +86,7 @@ SPLITKV_MAX_SPLITS = 64    # QATTN_SPLITKV_MAX_SPLITS (include/qattn_splitkv.h)
 MLA_D, MLA_D_LATENT, MLA_D_ROPE, MLA_MAX_SPLITS = 576, 512, 64, 64   # QATTN_MLA_* (include/qattn_mla.h)
 MLA_SPARSE_SPLIT_ENTRIES = 2048                                      # QATTN_MLA_SPARSE_SPLIT_ENTRIES (include/qattn_mla_sparse.h)
 MLA_SPARSE_MAX_TOPK = MLA_SPARSE_SPLIT_ENTRIES * MLA_MAX_SPLITS      # QATTN_MLA_SPARSE_MAX_TOPK
+MLA_SPARSE_PREFILL_ROWS = 128                                        # QATTN_MLA_SPARSE_PREFILL_ROWS (include/qattn_mla_sparse_prefill.h)
 MLA_INDEX_D, MLA_INDEX_MAX_HEADS = 128, 64                           # QATTN_MLA_INDEX_* (include/qattn_mla_index.h)
 MLA_INDEX_WG_KEYS, MLA_INDEX_LDS_CANDIDATES = 512, 8192
 MLA_INDEX_MAX_SELECT_SPLITS = 256                                    # QATTN_MLA_INDEX_MAX_SELECT_SPLITS (include/qattn_mla_index_split.h)
@@ -384,6 +386,9 @@ def lib() -> ctypes.CDLL:
     L.qattn_fp8_mla_paged_sparse_forward.restype = i
     L.qattn_fp8_mla_paged_sparse_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, vp, i, vp, vp, vp, i, i, i, i, i, f, i, vp, vp, vp, vp,
                                                      vp, sz, vp]
+    # ... for packed variable-length queries (include/qattn_mla_sparse_prefill.h)
+    L.qattn_fp8_mla_paged_sparse_varlen_forward.restype = i
+    L.qattn_fp8_mla_paged_sparse_varlen_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, ll, i, vp, vp, vp, vp, i, i, i, i, i, f, vp, vp, vp]
     # the lightning indexer of sparse multi-head latent attention (include/qattn_mla_index.h)
     L.qattn_mla_index_pool_bytes.restype = sz
     L.qattn_mla_index_pool_bytes.argtypes = [i, i]
@@ -2074,6 +2079,47 @@ def fp8_mla_paged_sparse_attention(q: torch.Tensor, pool: torch.Tensor, scale: t
                                                   pl.data_ptr() if parts else None, _ptr(ws), wsb, _stream(q))
     _check(rc, "qattn_fp8_mla_paged_sparse_forward")
     return out, lse, po, pl, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq
+
+
+def fp8_mla_paged_sparse_varlen_attention(q: torch.Tensor, pool: torch.Tensor, scale: torch.Tensor, block_table: torch.Tensor,
+                                          seqused_k: torch.Tensor, indices: torch.Tensor, cu_seqlens_q: torch.Tensor, *, num_pages: int,
+                                          page_size: int, fp8_dtype=torch.float8_e4m3fn, is_causal: bool, sm_scale: float,
+                                          return_q8: bool = False):
+    """qattn_fp8_mla_paged_sparse_varlen_forward (include/qattn_mla_sparse_prefill.h): q [total_q, Hq, 576] (a view with dense channels is
+    read through its strides), indices int32 [total_q, topk] with a dense last dimension, cu_seqlens_q int32 [B + 1].  Returns (out
+    [total_q, Hq, 512], lse [Hq, total_q], q8, scale_q); the last two are empty unless asked for."""
+    _require(q.is_cuda and q.dim() == 3 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[2] == MLA_D and q.shape[0] > 0 and q.shape[1] > 0,
+             f"q must be a bf16 / fp16 device tensor [total_q, Hq, {MLA_D}]")
+    _require(mla_rows_addressable(q), "q needs dense channels and 16-byte-aligned rows")
+    total_q, Hq, _ = q.shape
+    dev = q.device
+    _require(indices.dtype == torch.int32 and indices.device == dev and indices.dim() == 2 and indices.shape[0] == total_q
+             and 1 <= indices.shape[1] <= MLA_SPARSE_MAX_TOPK and (indices.shape[1] == 1 or indices.stride(1) == 1)
+             and (total_q == 1 or indices.stride(0) >= 0),
+             f"indices must be an int32 [total_q={total_q}, 1 <= topk <= {MLA_SPARSE_MAX_TOPK}] tensor on {dev} with a dense last dimension")
+    topk = indices.shape[1]
+    B = block_table.shape[0] if block_table.dim() == 2 else 0
+    _require(cu_seqlens_q.dtype == torch.int32 and cu_seqlens_q.device == dev and cu_seqlens_q.is_contiguous()
+             and tuple(cu_seqlens_q.shape) == (B + 1,), f"cu_seqlens_q must be a dense int32 [B + 1 = {B + 1}] tensor on {dev}")
+    L = lib()
+    max_pages, tstride = _mla_row_pool_checks(L, pool, block_table, scale, dev, B, num_pages, page_size)
+    _lens_check("seqused_k", seqused_k, B, dev)
+    out = torch.empty((total_q, Hq, MLA_D_LATENT), dtype=q.dtype, device=dev)
+    lse = torch.empty((Hq, total_q), dtype=torch.float32, device=dev)
+    q8 = torch.empty((total_q, Hq, MLA_D) if return_q8 else (0,), dtype=torch.uint8, device=dev)
+    sq = torch.empty((total_q, Hq) if return_q8 else (0,), dtype=torch.float32, device=dev)
+    dense = (Hq * MLA_D, MLA_D)
+    s2 = None if q.is_contiguous() else (ctypes.c_longlong * 2)(*[q.stride(i) if q.shape[i] > 1 else dense[i] for i in (0, 1)])
+    with torch.cuda.device(dev):
+        rc = L.qattn_fp8_mla_paged_sparse_varlen_forward(q.data_ptr(), fmt_of(q.dtype), s2, pool.data_ptr(), block_table.data_ptr(), tstride,
+                                                         num_pages, page_size, max_pages, scale.data_ptr(), indices.data_ptr(),
+                                                         indices.stride(0) if total_q > 1 else topk, topk, cu_seqlens_q.data_ptr(),
+                                                         out.data_ptr(), lse.data_ptr(), seqused_k.data_ptr(), B, total_q, Hq,
+                                                         fmt_of(fp8_dtype), int(bool(is_causal)), float(sm_scale),
+                                                         q8.data_ptr() if return_q8 else None, sq.data_ptr() if return_q8 else None,
+                                                         _stream(q))
+    _check(rc, "qattn_fp8_mla_paged_sparse_varlen_forward")
+    return out, lse, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq
 
 
 def _mla_index_pool_checks(pool, block_table, scale, dev, B, num_pages, page_size):

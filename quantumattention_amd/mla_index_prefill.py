@@ -10,7 +10,7 @@ L_b = clamp(seqused_k[b], 0, max_seqlen_k); everything else is `fp8_mla_index_to
 and scale_q equal that call on the slot's tokens bit for bit.  On the device the score sweep shares every 128-key tile among 8 tokens
 through LDS, where the dense entry's sweep pulls the keys once per token.
 
-Package attributes, not names of `__all__`.  Not offered: packed q for `fp8_mla_paged_sparse_func`; the first selection histogram fused into
+Package attributes, not names of `__all__`.  (Packed q for the sparse attention: mla_sparse_prefill.py.)  Not offered: the first selection histogram fused into
 the sweep; per-key index scales."""
 from typing import Optional, Tuple
 

@@ -1481,6 +1481,41 @@ def _(query, pool, scale_kv, block_table, seqused_k, indices, num_pages, page_si
     return query.new_empty((B, Hq, Sq, 512)), f32(B, Hq, Sq), po, pl, q8, (f32(B, Hq, Sq) if return_q8 else f32(0))
 
 
+@_custom_op("quantumattention_amd::fp8_mla_paged_sparse_varlen_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_mla_paged_sparse_varlen_attention_forward(
+    query: torch.Tensor,
+    pool: torch.Tensor,
+    scale_kv: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    indices: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    num_pages: int,
+    page_size: int,
+    scale: float,
+    fp8_format: str = "e4m3",
+    is_causal: bool = True,
+    return_q8: bool = False,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Sparse absorbed multi-head latent attention of packed query [total_q, Hq, 576] over the keys indices int32 [total_q, topk] name in the
+    row-major paged FP8 latent cache (include/qattn_mla_sparse_prefill.h); scale the model's softmax scale.  Returns (out [total_q, Hq, 512],
+    lse [Hq, total_q], q8, scale_q).  Reference implementation: mla_sparse_prefill._varlen_eager.  Arguments are validated by
+    mla_sparse_prefill.fp8_mla_paged_sparse_varlen_func."""
+    return _native.fp8_mla_paged_sparse_varlen_attention(query, pool, scale_kv, block_table, seqused_k.contiguous(), indices,
+                                                         cu_seqlens_q.contiguous(), num_pages=num_pages, page_size=page_size,
+                                                         fp8_dtype=_native.fp8_dtype_of(fp8_format), is_causal=is_causal, sm_scale=scale,
+                                                         return_q8=return_q8)
+
+
+@_register_fake("quantumattention_amd::fp8_mla_paged_sparse_varlen_attention_forward")
+def _(query, pool, scale_kv, block_table, seqused_k, indices, cu_seqlens_q, num_pages, page_size, scale, fp8_format="e4m3", is_causal=True,
+      return_q8=False):
+    total_q, Hq, D = query.shape
+    f32 = lambda *shape: query.new_empty(shape, dtype=torch.float32)
+    q8 = query.new_empty((total_q, Hq, D), dtype=torch.float8_e4m3fn) if return_q8 else query.new_empty((0,), dtype=torch.uint8)
+    return query.new_empty((total_q, Hq, 512)), f32(Hq, total_q), q8, (f32(total_q, Hq) if return_q8 else f32(0))
+
+
 @_custom_op("quantumattention_amd::fp8_paged_mla_index_cache_append_", mutates_args=("pool", "seqlens"), device_types=("cuda",))
 def fp8_paged_mla_index_cache_append_(
     pool: torch.Tensor,
