@@ -155,7 +155,8 @@
  *   block_table  the entries lo_i / page_size .. ceil(L_i / page_size) - 1 of row i at the most, each clamped before it forms an address;
  *              the leading entries may hold anything (their pages may have been handed to another sequence).
  *
- * qattn_paged_mla_cache_append_fp8 and qattn_fp8_mla_paged_forward (qattn_mla.h; held by tests/test_gpu_mla.py): the table, lengths and
+ * qattn_paged_mla_cache_append_fp8 and qattn_fp8_mla_paged_forward (qattn_mla.h; held by tests/test_gpu_mla_buffer_contract.py, at
+ * addresses above 2^32 by tests/test_gpu_mla_large_offsets.py): the table, lengths and
  * clamping lines of the paged entries above, with ONE pool and no head axis.
  *   pool       qattn_mla_pool_bytes(num_pages, page_size) = num_pages (page_size / 64) 36 864 bytes, 16-byte aligned.  The append writes the
  *              576 bytes of every appended key, as 36 stores of 16 bytes, and no other byte; the attention reads the chunks
@@ -170,6 +171,55 @@
  *   partial_o, partial_lse  optional: fp32 [ns, B, Hq, Sq, 512] and [ns, B, Hq, Sq]; every element written when ns > 1, none otherwise.
  *   workspace  qattn_fp8_mla_paged_workspace_bytes(B, Hq, Sq, ns) bytes with the resolved ns, 16-byte aligned; 0 bytes (NULL allowed) for
  *              one split.  It holds the partials the caller did not provide.
+ *
+ * qattn_paged_mla_row_cache_append_fp8, qattn_fp8_mla_paged_sparse_forward (qattn_mla_sparse.h) and
+ * qattn_fp8_mla_paged_sparse_varlen_forward (qattn_mla_sparse_prefill.h; all three held by tests/test_gpu_mla_buffer_contract.py and
+ * tests/test_gpu_mla_large_offsets.py): scale, ckv16, kpe16, q16, out, lse, q8, scale_q, partial_o, partial_lse as the dense pair above, and
+ *   pool       qattn_mla_row_pool_bytes(num_pages, page_size) = num_pages page_size 576 bytes, 16-byte aligned, any page_size >= 1.  The
+ *              append writes the 576 bytes of every appended key (36 stores of 16 bytes) and no other byte.  The attention reads the rows
+ *              of the VALID list entries and row 0 of the pool (where the load of an invalid entry is redirected); no other row.
+ *   indices    int32 [B, Sq, topk] through {batch, position} element strides (idx_strides2, NULL: dense) / [total_q, topk] through
+ *              idx_stride, 4-byte aligned, the last dimension dense.  Read: the topk entries of every row (the packed entry: of the rows a
+ *              slot owns); not the pads between rows.  An entry may hold ANY int: -1, INT32_MIN, a position at or behind the limit.
+ *   workspace  qattn_fp8_mla_paged_sparse_workspace_bytes(B, Hq, Sq, ns), 16-byte aligned, 0 bytes for one split or caller-provided
+ *              partials.  The packed entry takes NO workspace.
+ *   packed     q16 [total_q, Hq, 576] through {token, head} strides; cu_seqlens_q int32 [B + 1], 4-byte aligned.  out [total_q, Hq, 512],
+ *              lse [Hq, total_q], q8 [total_q, Hq, 576], scale_q [total_q, Hq]: EVERY element written -- a row at or behind cu[B] (a padded
+ *              bucket) is a zero row with lse -inf, q8 and scale_q zero; its q and its list are not read.
+ *
+ * qattn_paged_mla_index_cache_append_fp8, qattn_fp8_mla_index_scores, qattn_mla_index_select, qattn_fp8_mla_index_topk (qattn_mla_index.h),
+ * qattn_mla_index_select_split, qattn_fp8_mla_index_topk_split (qattn_mla_index_split.h), qattn_fp8_mla_index_scores_varlen and
+ * qattn_fp8_mla_index_topk_varlen (qattn_mla_index_prefill.h; all eight held by tests/test_gpu_mla_index_buffer_contract.py and
+ * tests/test_gpu_mla_large_offsets.py):
+ *   pool       qattn_mla_index_pool_bytes(num_pages, page_size) = num_pages page_size 128 bytes, 16-byte aligned.  The append writes the 128
+ *              bytes of every appended key (8 stores of 16 bytes) and no other byte; the scores read the rows below kend of each slot at
+ *              the most, through key tiles of 128 keys whose bytes at or behind kend influence no result.
+ *   k16, q16   [B, T, 128] / [B, Hi, Sq, 128] / [total_q, Hi, 128] 16-bit rows through element strides (multiples of 8), 16-byte aligned, read.
+ *   weights    fp32 [B, Sq, Hi] through w_strides2 / [total_q, Hi] through w_stride, 4-byte aligned, heads dense; read, not the pads.
+ *   logits     fp32 [B, Sq, max_seqlen_k] through logits_strides2 / [total_q, max_seqlen_k] through logits_stride, 4-byte aligned.
+ *              Written: the elements j < kend of every row; with fill_tail != 0 also kend <= j < max_seqlen_k, as -inf.  With
+ *              fill_tail = 0 NO element at or behind kend is stored, the tail of the key group that kend cuts included.  The pads
+ *              between rows are never stored.  The selection reads the elements below kend and no other.
+ *   q8, scale_q  optional: e4m3 [B, Hi, Sq, 128] / [total_q, Hi, 128], 16-byte aligned, and fp32 [B, Hi, Sq] / [total_q, Hi]; every element
+ *              written, the rows of a padded bucket as zeros.
+ *   indices    int32 [B, Sq, topk] / [total_q, topk] dense, 4-byte aligned: every element written, positions and then -1 (a padded row:
+ *              all -1).
+ *   kend       int32 [total_q], 4-byte aligned: written for EVERY row, 0 for the rows of a padded bucket.
+ *   workspace  16-byte aligned, prior contents influence no result.  qattn_fp8_mla_index_workspace_bytes: the logits rows (0 bytes with
+ *              the caller's logits); qattn_mla_index_select_split_workspace_bytes: histograms and counts, cleared inside the call;
+ *              qattn_fp8_mla_index_topk_split_workspace_bytes: the rows (own_logits = 0), then the selection's;
+ *              qattn_fp8_mla_index_varlen_workspace_bytes: kend (rounded up to 256 bytes), then the rows (rounded up to 256 bytes); with
+ *              the caller's logits only kend's section.  Rows kept in a workspace get no tail fill.
+ *
+ * qattn_fp8_mla_prefill_varlen_forward (qattn_mla_prefill.h; held by tests/test_gpu_mla_prefill_buffer_contract.py):
+ *   q, k_nope, k_pe, v  16-bit through strides7 (multiples of 8), bases 16-byte aligned.  Read: the rows of sequences (k: of their USED
+ *              keys); not the pads, not the keys behind a used length, not the tokens behind cu_seqlens[B].
+ *   out, lse, q8, scale_q  dense [total_q, H, 128], [H, total_q], [total_q, H, 192], [total_q, H]; out and q8 16-byte aligned.  Written: every
+ *              element of the rows of sequences and NO other -- the rows behind cu_seqlens_q[B] keep what they held (the packed
+ *              convention of qattn_varlen.h: no work item exists for them).
+ *   scale_k, scale_v  optional fp32 [B, H], 4-byte aligned, every element written (an empty sequence: the 2^-23 floor).
+ *   workspace  qattn_fp8_mla_prefill_varlen_workspace_bytes(B, H, total_q, total_k) bytes, 16-byte aligned: the images, the scales that are
+ *              not caller-provided and the abs-max words, which the call clears itself.  Prior contents influence no result.
  */
 #ifndef QATTN_BUFFERS_H_
 #define QATTN_BUFFERS_H_

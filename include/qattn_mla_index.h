@@ -21,9 +21,9 @@
  * in fp32: the 128-channel products on v_mfma_f32_32x32x64_f8f6f4, the head sum as fused multiply-adds in the order of the accumulator rows
  * (a NaN score counts as 0: the maximum is v_max_f32).  No softmax, no LSE.  logits is fp32 [B, Sq, max_seqlen_k], element strides
  * logits_strides2 = {batch, position} (NULL: dense).  Elements j < kend hold the logits; with fill_tail != 0 every element kend <= j <
- * max_seqlen_k is written -inf, else those elements are left as they are.  Keys at or behind kend and never-written pages (NaN bytes
- * included) influence no element below kend: a key is one column of the matrix product.  One workgroup per (b, i, range of
- * QATTN_MLA_INDEX_WG_KEYS keys); a range at or behind kend only fills.  No merge, no splits.
+ * max_seqlen_k is written -inf, else those elements are left as they are (ALL of them: the tail of the key group that kend cuts too).
+ * Keys at or behind kend and never-written pages (NaN bytes included) influence no element below kend: a key is one column of the matrix
+ * product.  One workgroup per (b, i, range of QATTN_MLA_INDEX_WG_KEYS keys); a range at or behind kend only fills.  No merge, no splits.
  *
  * SELECTION (the contract).  indices int32 [B, Sq, topk] (dense) receives, per (b, i), the positions of the min(topk, kend) largest logits
  * among j < kend in ASCENDING position order, then -1 up to topk.  A larger logit wins; equal logits are won by the LOWER position; -0.0

@@ -12,7 +12,8 @@
  *   strides7 = element strides {q token, q head, k_nope token, k_nope head, k_pe token, v token, v head}, NULL: dense.  Non-negative multiples
  *   of 8.  k_nope and v may be the two halves of one [total_k, H, 256] projection.  MHA only: one head count H.
  *   out     [total_q, H, 128] dense, in_fmt;   lse fp32 [H, total_q] (may be NULL): the natural log-sum-exp of the scaled scores, the packed
- *   layout of include/qattn_varlen.h, which qattn_attention_state_merge (include/qattn_merge.h) takes as it is.
+ *   layout of include/qattn_varlen.h, which qattn_attention_state_merge (include/qattn_merge.h) takes as it is.  out and lse are written
+ *   for the rows of sequences only: a token at or behind cu_seqlens_q[B] (a padded bucket) has no work item and keeps what it held.
  *
  * TABLES.  cu_seqlens_q / cu_seqlens_k int32 [B + 1], seqused_k int32 [B] or NULL, on the device; every extent is clamped as in
  * include/qattn_varlen.h (start = clamp(cu[i], 0, total), end = clamp(cu[i + 1], start, total), used keys clamp(seqused_k[i], 0, end - start)).

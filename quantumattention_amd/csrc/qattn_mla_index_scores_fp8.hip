@@ -197,7 +197,8 @@ __global__ __launch_bounds__(256) void mla_index_scores_kernel(const IndexScoreA
                 const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc), __float_as_uint(acc), false, false);
                 acc = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
             }
-            if (hh == 0 && j < a.N) lrow[j] = j < kend ? acc * scale_k : -INFINITY;
+            if (hh == 0 && j < kend) lrow[j] = acc * scale_k;   // (kend <= N)
+            else if (hh == 0 && a.fill && j < a.N) lrow[j] = -INFINITY;   // the group that kend cuts: its tail is the caller's unless asked for
         } else if (a.fill) {
             if (hh == 0 && j < a.N) lrow[j] = -INFINITY;
         }

@@ -27,6 +27,7 @@ POISON = {
     "fp32": (0x00, 0x00, 0xC0, 0x7F),    # 0x7FC00000: NaN
     "fp8": (0x7F,),                      # NaN in e4m3fn and e5m2; the quantisers clamp to +-fmax and never produce it
     "path": (0xA5,),                     # no QATTN_PATH_* code
+    "int32": (0xA7, 0xA6, 0xA5, 0xA4),   # 0xA4A5A6A7 = -1532647769: indices are -1 or >= 0, kend and seqlens >= 0 -- no entry produces it
 }
 # guards (and view pads) of an input
 HOSTILE = {

@@ -144,3 +144,37 @@ def test_pads_of_a_strided_view_carry_the_input_pattern():
     assert torch.isnan(whole[..., 8:]).all()
     r.load_view(x, strides, hostile=False)
     assert (whole[..., 8:] == 0).all() and torch.equal(whole[..., :8], x)
+
+
+# ---- int32 outputs (indices, kend, seqlens): the poison is a value no entry can produce
+IDX_ROWS, IDX_TOPK, IDX_STRIDE = 5, 6, 8
+
+
+def _fake_select(fault=None):
+    """indices int32 [IDX_ROWS, IDX_TOPK] through a row stride of IDX_STRIDE: positions 0 .. 3, then -1; the pads are not the kernel's"""
+    r = A.carve(4 * ((IDX_ROWS - 1) * IDX_STRIDE + IDX_TOPK), device="cpu", align=4, row_bytes=4 * IDX_STRIDE, role="out", kind="int32")
+    flat = r.view(torch.int32)
+    logical = torch.as_strided(flat, (IDX_ROWS, IDX_TOPK), (IDX_STRIDE, 1))
+    logical.copy_(torch.tensor([0, 1, 2, 3, -1, -1], dtype=torch.int32).expand(IDX_ROWS, IDX_TOPK))
+    if fault == "skip_element":
+        flat[2 * IDX_STRIDE + 4] = torch.tensor(list(A.POISON["int32"]), dtype=torch.uint8).view(torch.int32)[0]
+    if fault == "pad_overwritten":
+        flat[IDX_STRIDE + IDX_TOPK] = -1            # the first pad element behind row 1
+    return r, logical.contiguous().view(-1).view(torch.uint8)
+
+
+def test_the_int32_poison_is_no_index_no_kend_and_no_length():
+    r = A.carve(64, device="cpu", align=4, role="out", kind="int32")
+    v = r.view(torch.int32)
+    assert (v == v[0]).all() and int(v[0]) < -1 and r.poison_left() == 16 and r.ptr % 512 == 4
+    assert A.KIND_OF_DTYPE[torch.int32] == "int32" and len(A.POISON["int32"]) == 4
+
+
+def test_an_int32_output_reports_an_unwritten_element_and_an_overwritten_pad():
+    pads = (IDX_ROWS - 1) * (IDX_STRIDE - IDX_TOPK)
+    r, logical = _fake_select()
+    assert r.poison_left(logical) == 0 and r.poison_left() == pads and r.changed_guard_bytes() is None
+    r, logical = _fake_select("skip_element")
+    assert r.poison_left(logical) == 1 and r.poison_left() == pads + 1, "the element nobody wrote still holds the poison"
+    r, logical = _fake_select("pad_overwritten")
+    assert r.poison_left(logical) == 0 and r.poison_left() == pads - 1, "a store between the rows eats one pad element's poison"
