@@ -172,6 +172,19 @@
  *   workspace  qattn_fp8_mla_paged_workspace_bytes(B, Hq, Sq, ns) bytes with the resolved ns, 16-byte aligned; 0 bytes (NULL allowed) for
  *              one split.  It holds the partials the caller did not provide.
  *
+ * qattn_fp8_mla_paged_varlen_forward (qattn_mla_varlen.h; held by tests/test_gpu_mla_varlen.py against the dense entry): pool, table,
+ * lengths, scale as the dense pair above, and
+ *   q16        [total_q, Hq, 576] through {token, head} element strides (multiples of 8; NULL: dense), 16-byte aligned.  Read: the rows of the
+ *              tokens a slot owns; not the rows at or behind cu_seqlens_q[B].
+ *   cu_seqlens_q  int32 [B + 1], 4-byte aligned; read, every entry clamped into [0, total_q].
+ *   out, lse, q8, scale_q  dense [total_q, Hq, 512] in q16's format, fp32 [Hq, total_q], e4m3 [total_q, Hq, 576], fp32 [total_q, Hq]; out and
+ *              q8 16-byte aligned; lse, q8, scale_q optional.  EVERY element written (cu[0] = 0) -- a row at or behind cu[B] is a zero row
+ *              with lse -inf, q8 and scale_q zero.
+ *   partial_o, partial_lse  optional: fp32 [ns, total_q, Hq, 512] and [ns, total_q, Hq] by output row; every element written when ns > 1 (the
+ *              rows behind cu[B]: zeros and -inf), none otherwise.
+ *   workspace  qattn_fp8_mla_paged_varlen_workspace_bytes(total_q, Hq, ns) bytes with the resolved ns, 16-byte aligned; 0 bytes (NULL
+ *              allowed) for one split.  It holds the partials the caller did not provide; prior contents influence no result.
+ *
  * qattn_paged_mla_row_cache_append_fp8, qattn_fp8_mla_paged_sparse_forward (qattn_mla_sparse.h) and
  * qattn_fp8_mla_paged_sparse_varlen_forward (qattn_mla_sparse_prefill.h; all three held by tests/test_gpu_mla_buffer_contract.py and
  * tests/test_gpu_mla_large_offsets.py): scale, ckv16, kpe16, q16, out, lse, q8, scale_q, partial_o, partial_lse as the dense pair above, and

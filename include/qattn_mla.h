@@ -54,8 +54,8 @@
  * ckv16, kpe16, out, q8: 16 bytes); strides non-negative multiples of 8; 0 <= num_splits <= QATTN_MLA_MAX_SPLITS; sm_scale > 0; workspace_bytes
  * large enough; formats: QATTN_ERR_UNSUPPORTED_FMT.  Buffers: include/qattn_buffers.h.
  *
- * Not offered: packed variable-length q; windows, sinks, soft cap or trees on MLA; RoPE inside the append (the caller rotates k_pe);
- * precision "fast" / "auto"; per-token cache scales.  (DeepSeek-V3.2's sparse indexer: include/qattn_mla_index.h.  The non-absorbed prefill
+ * Not offered: windows, sinks, soft cap or trees on MLA; RoPE inside the append (the caller rotates k_pe);
+ * precision "fast" / "auto"; per-token cache scales.  (Packed variable-length q: include/qattn_mla_varlen.h.  DeepSeek-V3.2's sparse indexer: include/qattn_mla_index.h.  The non-absorbed prefill
  * form -- ordinary MHA at D 192 / 128 -- is include/qattn_mla_prefill.h)
  */
 #ifndef QATTN_MLA_H_

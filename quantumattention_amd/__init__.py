@@ -131,3 +131,6 @@ from .mla_index_prefill import fp8_mla_index_topk_varlen_func, mla_index_varlen_
 # ... and the sparse attention over those packed lists, one workgroup per token and 128 heads (include/qattn_mla_sparse_prefill.h): package
 # attributes, not in __all__
 from .mla_sparse_prefill import fp8_mla_paged_sparse_varlen_func, mla_sparse_varlen_input_reason  # noqa: E402
+# ... and the DENSE absorbed form on packed variable-length queries over the one-image cache, a 128-row tile per workgroup
+# (include/qattn_mla_varlen.h): package attributes, not in __all__
+from .mla_varlen import fp8_mla_paged_varlen_func, mla_varlen_input_reason  # noqa: E402

@@ -77,6 +77,7 @@ EXPORTS = (
     "qattn_fp8_mla_prefill_varlen_workspace_bytes", "qattn_fp8_mla_prefill_varlen_forward",
     "qattn_fp8_mla_index_varlen_workspace_bytes", "qattn_fp8_mla_index_scores_varlen", "qattn_fp8_mla_index_topk_varlen",
     "qattn_fp8_mla_paged_sparse_varlen_forward",
+    "qattn_mla_varlen_auto_splits", "qattn_fp8_mla_paged_varlen_workspace_bytes", "qattn_fp8_mla_paged_varlen_forward",
 )
 FMT_FP32 = 4               # QATTN_FMT_FP32 (include/qattn_merge.h): a partial / the output of the state merge, no other entry takes it
 MERGE_MAX_PARTIALS = 8     # QATTN_MERGE_MAX_PARTIALS
@@ -87,7 +88,8 @@ MLA_D, MLA_D_LATENT, MLA_D_ROPE, MLA_MAX_SPLITS = 576, 512, 64, 64   # QATTN_MLA
 MLA_SPARSE_SPLIT_ENTRIES = 2048                                      # QATTN_MLA_SPARSE_SPLIT_ENTRIES (include/qattn_mla_sparse.h)
 MLA_SPARSE_MAX_TOPK = MLA_SPARSE_SPLIT_ENTRIES * MLA_MAX_SPLITS      # QATTN_MLA_SPARSE_MAX_TOPK
 MLA_SPARSE_PREFILL_ROWS = 128                                        # QATTN_MLA_SPARSE_PREFILL_ROWS (include/qattn_mla_sparse_prefill.h)
-MLA_INDEX_D, MLA_INDEX_MAX_HEADS = 128, 64                           # QATTN_MLA_INDEX_* (include/qattn_mla_index.h)
+MLA_VARLEN_ROWS = 128                                                # QATTN_MLA_VARLEN_ROWS (include/qattn_mla_varlen.h)
+MLA_INDEX_D, MLA_INDEX_MAX_HEADS = 128, 64                         # QATTN_MLA_INDEX_* (include/qattn_mla_index.h)
 MLA_INDEX_WG_KEYS, MLA_INDEX_LDS_CANDIDATES = 512, 8192
 MLA_INDEX_MAX_SELECT_SPLITS = 256                                    # QATTN_MLA_INDEX_MAX_SELECT_SPLITS (include/qattn_mla_index_split.h)
 MLA_INDEX_AUTO_MIN_SEG, MLA_INDEX_AUTO_MIN_KEYS = 2048, 16384         # QATTN_MLA_INDEX_AUTO_MIN_SEG, QATTN_MLA_INDEX_AUTO_MIN_KEYS
@@ -389,6 +391,14 @@ def lib() -> ctypes.CDLL:
     # ... for packed variable-length queries (include/qattn_mla_sparse_prefill.h)
     L.qattn_fp8_mla_paged_sparse_varlen_forward.restype = i
     L.qattn_fp8_mla_paged_sparse_varlen_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, ll, i, vp, vp, vp, vp, i, i, i, i, i, f, vp, vp, vp]
+    # dense multi-head latent attention for packed variable-length queries (include/qattn_mla_varlen.h)
+    L.qattn_mla_varlen_auto_splits.restype = i
+    L.qattn_mla_varlen_auto_splits.argtypes = [i, i, i]
+    L.qattn_fp8_mla_paged_varlen_workspace_bytes.restype = sz
+    L.qattn_fp8_mla_paged_varlen_workspace_bytes.argtypes = [i, i, i]
+    L.qattn_fp8_mla_paged_varlen_forward.restype = i
+    L.qattn_fp8_mla_paged_varlen_forward.argtypes = [vp, i, vp, vp, vp, ll, i, i, i, vp, vp, i, vp, vp, vp, i, i, i, i, i, i, f, i, vp, vp, vp, vp,
+                                                     vp, sz, vp]
     # the lightning indexer of sparse multi-head latent attention (include/qattn_mla_index.h)
     L.qattn_mla_index_pool_bytes.restype = sz
     L.qattn_mla_index_pool_bytes.argtypes = [i, i]
@@ -2120,6 +2130,60 @@ def fp8_mla_paged_sparse_varlen_attention(q: torch.Tensor, pool: torch.Tensor, s
                                                          _stream(q))
     _check(rc, "qattn_fp8_mla_paged_sparse_varlen_forward")
     return out, lse, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq
+
+
+def mla_varlen_tile_slots(B: int, total_q: int, Hq: int) -> int:
+    """the host bound of the packed dense entry's tile grid (include/qattn_mla_varlen.h): ceil(total_q Hq / 128) + B"""
+    return -(-total_q * Hq // MLA_VARLEN_ROWS) + B
+
+
+def mla_varlen_auto_splits(tile_slots: int, Skv: int, num_cus: int) -> int:
+    """qattn_mla_varlen_auto_splits (include/qattn_mla_varlen.h): a pure function of its arguments (no device needed)."""
+    return lib().qattn_mla_varlen_auto_splits(tile_slots, Skv, num_cus)
+
+
+def fp8_mla_paged_varlen_attention(q: torch.Tensor, pool: torch.Tensor, scale: torch.Tensor, block_table: torch.Tensor, seqused_k: torch.Tensor,
+                                   cu_seqlens_q: torch.Tensor, *, max_seqlen_q: int, Skv: int, num_pages: int, page_size: int,
+                                   fp8_dtype=torch.float8_e4m3fn, is_causal: bool, sm_scale: float, num_splits: int,
+                                   return_partials: bool = False, return_q8: bool = False):
+    """qattn_fp8_mla_paged_varlen_forward (include/qattn_mla_varlen.h) with num_splits >= 1 resolved by the caller: q [total_q, Hq, 576] (a view
+    with dense channels is read through its strides), cu_seqlens_q int32 [B + 1].  Returns (out [total_q, Hq, 512], lse [Hq, total_q],
+    partial_o [ns, total_q, Hq, 512], partial_lse [ns, total_q, Hq], q8, scale_q); the last four are empty unless asked for (partials: and
+    num_splits > 1)."""
+    _require(q.is_cuda and q.dim() == 3 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[2] == MLA_D and q.shape[0] > 0 and q.shape[1] > 0,
+             f"q must be a bf16 / fp16 device tensor [total_q, Hq, {MLA_D}]")
+    _require(mla_rows_addressable(q), "q needs dense channels and 16-byte-aligned rows")
+    _require(isinstance(num_splits, int) and 1 <= num_splits <= MLA_MAX_SPLITS, f"num_splits must be in 1 .. {MLA_MAX_SPLITS} here, got {num_splits}")
+    total_q, Hq, _ = q.shape
+    _require(isinstance(max_seqlen_q, int) and 1 <= max_seqlen_q <= total_q, f"max_seqlen_q must be in 1 .. total_q = {total_q}, got {max_seqlen_q}")
+    dev = q.device
+    B = block_table.shape[0] if block_table.dim() == 2 else 0
+    _require(cu_seqlens_q.dtype == torch.int32 and cu_seqlens_q.device == dev and cu_seqlens_q.is_contiguous()
+             and tuple(cu_seqlens_q.shape) == (B + 1,), f"cu_seqlens_q must be a dense int32 [B + 1 = {B + 1}] tensor on {dev}")
+    L = lib()
+    max_pages, tstride = _mla_pool_checks(L, pool, block_table, scale, dev, B, num_pages, page_size)
+    _lens_check("seqused_k", seqused_k, B, dev)
+    _require(isinstance(Skv, int) and 1 <= Skv <= max_pages * page_size, f"Skv must be in 1 .. max_pages * page_size, got {Skv}")
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = torch.empty((total_q, Hq, MLA_D_LATENT), dtype=q.dtype, device=dev)
+    lse = f32(Hq, total_q)
+    parts = num_splits > 1 and return_partials
+    po, pl = (f32(num_splits, total_q, Hq, MLA_D_LATENT), f32(num_splits, total_q, Hq)) if parts else (f32(0), f32(0))
+    q8 = torch.empty((total_q, Hq, MLA_D) if return_q8 else (0,), dtype=torch.uint8, device=dev)
+    sq = f32(total_q, Hq) if return_q8 else f32(0)
+    wsb = 0 if parts else L.qattn_fp8_mla_paged_varlen_workspace_bytes(total_q, Hq, num_splits)
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev) if wsb else None
+    dense = (Hq * MLA_D, MLA_D)
+    s2 = None if q.is_contiguous() else (ctypes.c_longlong * 2)(*[q.stride(i) if q.shape[i] > 1 else dense[i] for i in (0, 1)])
+    with torch.cuda.device(dev):
+        rc = L.qattn_fp8_mla_paged_varlen_forward(q.data_ptr(), fmt_of(q.dtype), s2, pool.data_ptr(), block_table.data_ptr(), tstride, num_pages,
+                                                  page_size, max_pages, scale.data_ptr(), cu_seqlens_q.data_ptr(), max_seqlen_q, out.data_ptr(),
+                                                  lse.data_ptr(), seqused_k.data_ptr(), B, total_q, Hq, Skv, fmt_of(fp8_dtype),
+                                                  int(bool(is_causal)), float(sm_scale), num_splits, q8.data_ptr() if return_q8 else None,
+                                                  sq.data_ptr() if return_q8 else None, po.data_ptr() if parts else None,
+                                                  pl.data_ptr() if parts else None, _ptr(ws), wsb, _stream(q))
+    _check(rc, "qattn_fp8_mla_paged_varlen_forward")
+    return out, lse, po, pl, (q8.view(torch.float8_e4m3fn) if return_q8 else q8), sq
 
 
 def _mla_index_pool_checks(pool, block_table, scale, dev, B, num_pages, page_size):

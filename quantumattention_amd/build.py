@@ -29,7 +29,8 @@ SOURCES = ["qattn_quant.hip", "qattn_attn_v2.hip", "qattn_attn_v4.hip", "qattn_a
            "qattn_splitkv_softcap_fp8.hip", "qattn_paged_splitkv_softcap_fp8.hip", "qattn_paged_varlen_splitkv_softcap_fp8.hip",
            "qattn_mla_append.hip", "qattn_mla_splitkv_fp8.hip", "qattn_mla_row_append.hip", "qattn_mla_sparse_fp8.hip",
            "qattn_mla_index_append.hip", "qattn_mla_index_scores_fp8.hip", "qattn_mla_index_select.hip", "qattn_mla_index_select_split.hip",
-           "qattn_mla_prefill_fp8.hip", "qattn_mla_index_scores_prefill_fp8.hip", "qattn_mla_sparse_prefill_fp8.hip"]
+           "qattn_mla_prefill_fp8.hip", "qattn_mla_index_scores_prefill_fp8.hip", "qattn_mla_sparse_prefill_fp8.hip",
+           "qattn_mla_varlen_fp8.hip"]
 # (source, extra flags, object name): the two big kernel files are compiled once per operand format / head dimension so that
 # the build runs in parallel (the longest single translation unit sets the wall time)
 # (a unit with a define is compiled through a two-line wrapper file named after the unit, so that -save-temps leaves one .s
@@ -110,6 +111,9 @@ UNITS = [
     ("qattn_mla_index_scores_prefill_fp8.hip", [], "qattn_mla_index_scores_prefill_fp8"),
     # sparse MLA for packed variable-length queries (include/qattn_mla_sparse_prefill.h): one 8-wave workgroup per token and 128 heads
     ("qattn_mla_sparse_prefill_fp8.hip", [], "qattn_mla_sparse_prefill_fp8"),
+    # dense absorbed MLA for packed variable-length queries over the one-image cache (include/qattn_mla_varlen.h): one 8-wave workgroup per
+    # 128-row tile of a slot and key split
+    ("qattn_mla_varlen_fp8.hip", [], "qattn_mla_varlen_fp8"),
 ]
 # extra compiler flags of a unit, by object name.  The MLA units are compiled with the selection of packed fp32 instructions
 # (v_pk_mul_f32, v_pk_add_f32, v_pk_fma_f32) switched off: their fp32 arithmetic is the scalar instructions only.  A conservative setting
@@ -119,7 +123,8 @@ UNITS = [
 # the same hipcc line says that it ignores it.)
 UNIT_FLAGS = {name: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] for name in ("qattn_mla_append", "qattn_mla_splitkv_fp8", "qattn_mla_row_append", "qattn_mla_sparse_fp8",
                        "qattn_mla_index_append", "qattn_mla_index_scores_fp8", "qattn_mla_index_select", "qattn_mla_index_select_split",
-                       "qattn_mla_prefill_fp8", "qattn_mla_index_scores_prefill_fp8", "qattn_mla_sparse_prefill_fp8")}
+                       "qattn_mla_prefill_fp8", "qattn_mla_index_scores_prefill_fp8", "qattn_mla_sparse_prefill_fp8",
+                       "qattn_mla_varlen_fp8")}
 # (Until round 5 `--dev` built a second library with -DQATTN_DEV: timing-only ablation instantiations, per-segment cycle stamps, work logs and
 # QATTN_* environment switches.  Round 6 took that scaffolding out of the sources -- identical product ISA, profiles/r06/isa_identity_*.log;
 # the measurements it produced are in profiles/r01 .. r05 and docs/.  What remains for experiments: `--variant=<name> -DKNOB=value`.)
@@ -163,7 +168,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = False, 
     os.makedirs(build_dir, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("qattn.h", "qattn_measure.h", "qattn_varlen.h", "qattn_block_sparse.h", "qattn_smooth.h", "qattn_window.h", "qattn_merge.h", "qattn_rope.h", "qattn_splitkv.h", "qattn_kvcache.h", "qattn_paged.h", "qattn_paged_varlen.h", "qattn_splitkv_window.h", "qattn_paged_varlen_append.h", "qattn_paged_varlen_rope.h", "qattn_sinks.h", "qattn_paged_varlen_tree.h", "qattn_paged_varlen_tree_window.h", "qattn_paged_varlen_rope_pos.h", "qattn_softcap.h", "qattn_mla.h", "qattn_mla_sparse.h", "qattn_mla_index.h", "qattn_mla_index_split.h", "qattn_mla_prefill.h", "qattn_mla_index_prefill.h", "qattn_mla_sparse_prefill.h")]
+    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("qattn.h", "qattn_measure.h", "qattn_varlen.h", "qattn_block_sparse.h", "qattn_smooth.h", "qattn_window.h", "qattn_merge.h", "qattn_rope.h", "qattn_splitkv.h", "qattn_kvcache.h", "qattn_paged.h", "qattn_paged_varlen.h", "qattn_splitkv_window.h", "qattn_paged_varlen_append.h", "qattn_paged_varlen_rope.h", "qattn_sinks.h", "qattn_paged_varlen_tree.h", "qattn_paged_varlen_tree_window.h", "qattn_paged_varlen_rope_pos.h", "qattn_softcap.h", "qattn_mla.h", "qattn_mla_sparse.h", "qattn_mla_index.h", "qattn_mla_index_split.h", "qattn_mla_prefill.h", "qattn_mla_index_prefill.h", "qattn_mla_sparse_prefill.h", "qattn_mla_varlen.h")]
     objs, jobs = [], []
     for src, defines, name in UNITS:
         s = os.path.join(CSRC, src)

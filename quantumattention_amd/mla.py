@@ -16,8 +16,8 @@ The cache has ONE fixed fp32 scale per slot for all 576 channels.  A caller whos
 a constant and q_pe by its inverse.  `scale` of the attention call is REQUIRED: MLA's softmax scale is the model's (1/sqrt(192) times its
 YaRN factor), never 1/sqrt(576).  q is quantised inside the kernel, token-wise, always to e4m3.  Table, lengths and clamping: paged.py.
 
-Package attributes, not names of `__all__`.  Not offered: packed variable-length q; windows, sinks, soft cap or trees on MLA; RoPE inside the
-append; precision "fast" / "auto"; per-token cache scales.  (The indexer of DeepSeek-V3.2's sparse attention -- its scores and the top-k
+Package attributes, not names of `__all__`.  Not offered: windows, sinks, soft cap or trees on MLA; RoPE inside the
+append; precision "fast" / "auto"; per-token cache scales.  (Packed variable-length q: mla_varlen.py.  The indexer of DeepSeek-V3.2's sparse attention -- its scores and the top-k
 selection -- is mla_index.py; the attention over the selected keys is below.  The non-absorbed prefill form -- ordinary MHA at D 192 / 128 --
 is mla_prefill.py)
 

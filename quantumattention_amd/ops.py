@@ -1516,6 +1516,46 @@ def _(query, pool, scale_kv, block_table, seqused_k, indices, cu_seqlens_q, num_
     return query.new_empty((total_q, Hq, 512)), f32(Hq, total_q), q8, (f32(total_q, Hq) if return_q8 else f32(0))
 
 
+@_custom_op("quantumattention_amd::fp8_mla_paged_varlen_attention_forward", mutates_args=(), device_types=("cuda",))
+def fp8_mla_paged_varlen_attention_forward(
+    query: torch.Tensor,
+    pool: torch.Tensor,
+    scale_kv: torch.Tensor,
+    block_table: torch.Tensor,
+    seqused_k: torch.Tensor,
+    cu_seqlens_q: torch.Tensor,
+    max_seqlen_q: int,
+    seqlen_k: int,
+    num_pages: int,
+    page_size: int,
+    num_splits: int,
+    scale: float,
+    fp8_format: str = "e4m3",
+    is_causal: bool = True,
+    return_partials: bool = False,
+    return_q8: bool = False,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Absorbed multi-head latent attention of packed query [total_q, Hq, 576] under cu_seqlens_q int32 [B + 1] over the one-image paged FP8
+    latent cache (include/qattn_mla_varlen.h); num_splits >= 1 (resolved by the caller), scale the model's softmax scale.  Returns (out
+    [total_q, Hq, 512], lse [Hq, total_q], partial_o, partial_lse, q8, scale_q).  Reference implementation: mla_varlen._varlen_eager.
+    Arguments are validated by mla_varlen.fp8_mla_paged_varlen_func."""
+    return _native.fp8_mla_paged_varlen_attention(query, pool, scale_kv, block_table, seqused_k.contiguous(), cu_seqlens_q.contiguous(),
+                                                  max_seqlen_q=max_seqlen_q, Skv=seqlen_k, num_pages=num_pages, page_size=page_size,
+                                                  fp8_dtype=_native.fp8_dtype_of(fp8_format), is_causal=is_causal, sm_scale=scale,
+                                                  num_splits=num_splits, return_partials=return_partials, return_q8=return_q8)
+
+
+@_register_fake("quantumattention_amd::fp8_mla_paged_varlen_attention_forward")
+def _(query, pool, scale_kv, block_table, seqused_k, cu_seqlens_q, max_seqlen_q, seqlen_k, num_pages, page_size, num_splits, scale,
+      fp8_format="e4m3", is_causal=True, return_partials=False, return_q8=False):
+    total_q, Hq, D = query.shape
+    f32 = lambda *shape: query.new_empty(shape, dtype=torch.float32)
+    n = num_splits if (num_splits > 1 and return_partials) else 0
+    po, pl = (f32(n, total_q, Hq, 512), f32(n, total_q, Hq)) if n else (f32(0), f32(0))
+    q8 = query.new_empty((total_q, Hq, D), dtype=torch.float8_e4m3fn) if return_q8 else query.new_empty((0,), dtype=torch.uint8)
+    return query.new_empty((total_q, Hq, 512)), f32(Hq, total_q), po, pl, q8, (f32(total_q, Hq) if return_q8 else f32(0))
+
+
 @_custom_op("quantumattention_amd::fp8_paged_mla_index_cache_append_", mutates_args=("pool", "seqlens"), device_types=("cuda",))
 def fp8_paged_mla_index_cache_append_(
     pool: torch.Tensor,
